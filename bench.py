@@ -15,6 +15,9 @@ window counts) per second / the measured v_mad_u64_u32 issue peak — a hardware
 unit (textbook CIOS on the 4096-bit integers) is reported beside it as `alg_unit_*`; it exceeds the peak because the
 kernel computes the same residues with ~0.46x those MACs.
 `roofline_secondary[]` / `whole_step`: the same accounting for every other profiled kernel and for the whole step.
+A plain run stops there: set-up, warm-up, the timed steps, --dump-outputs if given, the line.  With --full the line also carries
+the checks and the other measurements below, made after the timed region.
+--dump-outputs DIR: the last timed step's r, s, recid and status as DIR/<name>.npy (float64; the inputs depend only on the arguments).
 `openssl_verified`: every signature of the timed batch under OpenSSL's ECDSA_do_verify (after the timed region; tests/ossl.py).
 `configs`: c2 (65 536 Paillier encrypt + decrypt, 16 keys), c3 (262 144 EC scalar multiplications and PDL-with-slack
 prove + verify, prefix checked against the oracle and OpenSSL, 1 % corrupted proofs all rejected), c3b (65 536 BobProof generate +
@@ -31,8 +34,8 @@ session mode — the node's Paillier ops/s.  --share-device: every rank on cuda:
   --mode session (default): sessions sharded across ranks, no data-path collective (independent units, SURVEY.md §8e A);
   --mode party: the parties of a session live on different GPUs (party p of session block s on rank (s + p) % N) and
   every round's messages travel through one all-gather (BASELINE config 5); same per-GPU work.
-At N > 1 the line of the timed region is assembled before the collective sections that follow it (per-rank oracle parity, `mode_b{}`, config 2 on
-every GPU); if one of those wedges, a per-rank watchdog (MPE_BENCH_POST_TIMEOUT_S, default 420 s) makes rank 0 print that line with
+At N > 1 the line of the timed region is assembled before the collective sections that follow it with --full (per-rank oracle parity, `mode_b{}`,
+config 2 on every GPU); if one of those wedges, a per-rank watchdog (MPE_BENCH_POST_TIMEOUT_S, default 420 s) makes rank 0 print that line with
 `post_timing_sections{completed: false}` and every rank leave with status 0.
 --dump-launches adds the timed region's profiled launches (kind, modulus bits, exponent words, batch, ms) — what tools/ab_*.sh compare.
 Prints ONE JSON line (rank 0).
@@ -260,6 +263,26 @@ def make_device_nonces(gen, dev, B, L, S, n):
 
 def _host(nonces):
     return {f: np.ascontiguousarray(v.cpu().numpy().view(np.uint32)) for f, v in nonces.items()}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, out_host, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: what the timed path hands its caller from its last step — r and s (the 32-bit words of each signature
+    half), recid and status — as path/<name>.npy in float64, exact for every word.  Above `limit` bytes in all, every array
+    keeps the same fraction of its rows, a fixed seeded sample, and path/<name>_rows.npy holds the indices of the rows kept."""
+    r, s, recid, status = out_host
+    arrays = {"r": r.view(np.uint32), "s": s.view(np.uint32), "recid": recid, "status": status}
+    total = sum(a.size * 8 for a in arrays.values())
+    keep = 1.0 if total <= limit else (limit // 2) / total      # the other half of the budget covers the row indices
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        if keep < 1.0:
+            rows = np.sort(np.random.default_rng(20241016).choice(a.shape[0], max(1, int(a.shape[0] * keep)), replace=False))
+            a = a[rows]
+            np.save(os.path.join(path, f"{name}_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def host_cores():
@@ -1284,6 +1307,12 @@ def main():
     ap.add_argument("--stream-lanes", type=int, default=4, help="c4_stream_1024: passes in flight (mpe_gg20_pipeline lanes; 4 since round 6: "
                     "16.85 k signatures/s at p50 0.97 s against 16.1 - 16.3 k at 1.02 s with 2, profiles/r06/ab_stream12.jsonl)")
     ap.add_argument("--stream-group", type=int, default=4, help="c4_stream_1024: batches coalesced per pass")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run what the headline does not need: the CPU baseline and the oracle / OpenSSL "
+                         "checks, the host hand-over figure, the config sections (c2 ... f3) and, at N > 1, the per-rank parity, the "
+                         "party-sharded pass and config 2 on every GPU (--no-cpu-baseline, --no-configs, --only and --no-mode-b narrow it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the last timed step's outputs (r, s, recid, status) as DIR/<name>.npy in float64")
     ap.add_argument("--dump-launches", action="store_true", help="add the timed region's heavy launches (kind, bits, batch, ms) to the line")
     ap.add_argument("--only", default="", help="comma list of config sections to run after the timed region (default: all)")
     ap.add_argument("--no-mode-b", action="store_true", help="N > 1, session mode: skip the party-sharded (config 5 shape) pass after the timed region")
@@ -1385,7 +1414,8 @@ def main():
         # party p of session block s on rank (s + p) % world: this rank hosts S (block, party) pairs of B sessions each —
         # the same per-GPU work as B whole sessions; the messages of every round travel through one all-gather
         comm = make_comm(ctx, E, rank, world, share, distributed)
-        pm = PartyMode(ctx, E, G, mpe_dist, lk, arrays, T, N_PARTIES, SIGNERS, B, dev, world, parity_sessions=0 if args.no_cpu_baseline else 8, comm=comm)
+        pm = PartyMode(ctx, E, G, mpe_dist, lk, arrays, T, N_PARTIES, SIGNERS, B, dev, world,
+                       parity_sessions=8 if args.full and not args.no_cpu_baseline else 0, comm=comm)
         engines = pm.engines
         gather_test = pm.ps.layout_self_test()                 # the gather layout on the real backend, before anything is timed
         ps_holder = {"ps": pm.ps}
@@ -1544,10 +1574,12 @@ def main():
     # driver's node: if any of it wedges, every rank gives up at the same deadline and rank 0 still prints the Mode-A line it has —
     # marked as such — instead of the whole scaling run ending in the launcher's timeout with nothing.
     out_host = [o.cpu().numpy() for o in out]
-    watchdog = PostTimingWatchdog(rank, float(os.environ.get("MPE_BENCH_POST_TIMEOUT_S", "420")), core_line if rank == 0 else None) if (distributed and world > 1) else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out_host)
+    watchdog = PostTimingWatchdog(rank, float(os.environ.get("MPE_BENCH_POST_TIMEOUT_S", "420")), core_line if rank == 0 else None) if (distributed and world > 1 and args.full) else None
     # (c) a parity sample against the GMP oracle on EVERY rank at N > 1 (at N = 1 the cpu_baseline leg below does it on 256+ sessions)
     rank_parity = None
-    if distributed and not args.no_cpu_baseline:
+    if distributed and args.full and not args.no_cpu_baseline:
         if watchdog is not None:
             watchdog.at("per-rank oracle parity")
         if args.mode == "session":
@@ -1569,9 +1601,9 @@ def main():
 
     # (b) Mode B in the SAME line: after the session-sharded timed region a short party-sharded pass at BASELINE config 5's
     # per-GPU share (t=2, n=5: S=3 signers; party p of session block s on rank (s+p) % N; one all-gather per round), so that
-    # the driver's one command `bench.py --gpus N` exercises the RCCL data path and reports its rate beside Mode A's
+    # `bench.py --gpus N --full` exercises the RCCL data path and reports its rate beside Mode A's
     mode_b = None
-    want_b = (world > 1 or os.environ.get("MPE_BENCH_FORCE_MODE_B")) and distributed and args.mode == "session" and not args.no_mode_b
+    want_b = (world > 1 or os.environ.get("MPE_BENCH_FORCE_MODE_B")) and distributed and args.mode == "session" and args.full and not args.no_mode_b
     if want_b:
         if watchdog is not None:
             watchdog.at("mode_b (party-sharded pass over mpe_comm_*)")
@@ -1622,9 +1654,9 @@ def main():
             mode_b = {"error": repr(e_b)}
 
     # north_star asks for Paillier ops/s at 1, 2, 4 and 8 GPUs too: at N > 1 every rank runs BASELINE config 2 at the same time
-    # (after the timed signing region) and the rates add up; at N = 1 it is the c2 section below
+    # (after the timed signing region, --full) and the rates add up; at N = 1 it is the c2 section below
     node_paillier = None
-    if distributed and (world > 1 or os.environ.get("MPE_BENCH_FORCE_NODE_PAILLIER")) and args.mode == "session" and not args.no_configs:
+    if distributed and (world > 1 or os.environ.get("MPE_BENCH_FORCE_NODE_PAILLIER")) and args.mode == "session" and args.full and not args.no_configs:
         if watchdog is not None:
             watchdog.at("config 2 on every GPU")
         dist.barrier()
@@ -1650,9 +1682,11 @@ def main():
         # the other configs and the CPU baseline belong to the single-GPU line (rank 0 at N=1 only): at N>1 the other ranks
         # would just wait for them
         single = world == 1 and args.mode == "session"
+        full = single and args.full                      # a plain run prints the timed region's line and nothing else
+        res["full"] = bool(args.full)
         usable, quota = host_cores()
         threads = min(usable, 64)
-        if single and not args.no_cpu_baseline:
+        if full and not args.no_cpu_baseline:
             sample = min(B, max(1024, 16 * threads))     # >= BASELINE config 4's full size: the driver's line alone carries its parity
             host_nonces = _host({f: v[: sample * (v.shape[0] // B)] for f, v in nonces.items()})
             one = min(4, sample)
@@ -1676,14 +1710,14 @@ def main():
                                "steps_sampled": len(sampler["events"]), "rejection_loops_given_up": int(sampler["fail"].item()),
                                "bytes_sampled_per_step": int(sum(v.numel() * 4 for f_, v in nonces.items() if f_ != "msg"))}
             res["config"]["sampling_share_of_step"] = res["sampling"]["share_of_step"]
-            if single and not args.no_cpu_baseline:
+            if full and not args.no_cpu_baseline:
                 # the oracle expands the SAME (seed, counter) of the last step: identical arrays (oracle/sampler_oracle.c)
                 k_ = min(B, 64)
                 want_, wf_ = G.oracle_sample_nonces(lk, k_, sampler["seed"], sampler["counter"])
                 got_ = _host({f_: v[: k_ * (v.shape[0] // B)] for f_, v in nonces.items() if f_ != "msg"})
                 res["sampling"]["oracle_expands_the_seed_to_the_same_values"] = bool(wf_ == 0 and all(np.array_equal(got_[f_], want_[f_]) for f_ in got_))
                 res["sampling"]["sessions_compared"] = k_
-        if single:
+        if full:
             # A host that samples for itself and hands its values over for every batch (mpe_gg20_sign with caller arrays): the measured cost of moving
             # the step's inputs in (pinned host memory -> HBM) and its signatures out.  Reported beside the line, never part of `value`.
             try:
@@ -1711,7 +1745,7 @@ def main():
             # every signature of the timed batch under OpenSSL (not only "status == 0", which is the device's own verdict)
             res["openssl"] = openssl_verify_all(lk["arrays"]["y"][0], nonces["msg"], r, s, threads)
             res["openssl_verified"] = res["openssl"]["openssl_verified"]
-        if single and not args.no_configs and (T, N_PARTIES) == (1, 3):
+        if full and not args.no_configs and (T, N_PARTIES) == (1, 3):
             gk.close()
             cfg, took = {}, {}
 

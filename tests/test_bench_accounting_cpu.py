@@ -202,3 +202,30 @@ def test_distinct_wallet_moduli_are_distinct_and_well_formed():
     for a, b, n, x, y in zip(P, Q_, NT, H1, H2):
         assert a.bit_length() == 1024 and b.bit_length() == 1024 and (a * b).bit_length() in (2047, 2048) and a != b
         assert n.bit_length() in (2047, 2048) and 1 < x < n and 1 < y < n
+
+
+def test_dump_outputs_are_exact_float64_and_stay_under_the_limit(tmp_path):
+    """--dump-outputs: every word of r / s and every recid / status survives as float64; above the limit the same fixed rows of
+    every array are kept (their indices beside them) and the files stay under it"""
+    import numpy as np
+    rng = np.random.default_rng(5)
+    n = 3000
+    out = [rng.integers(-2**31, 2**31, (n, 8), dtype=np.int64).astype(np.int32), rng.integers(-2**31, 2**31, (n, 8), dtype=np.int64).astype(np.int32),
+           rng.integers(0, 4, n).astype(np.int32), rng.integers(-3, 1, n).astype(np.int32)]
+    whole = tmp_path / "whole"
+    B.dump_outputs(str(whole), out)
+    assert sorted(p.name for p in whole.iterdir()) == ["r.npy", "recid.npy", "s.npy", "status.npy"]
+    for name, a in zip(("r", "s", "recid", "status"), out):
+        got = np.load(whole / f"{name}.npy")
+        want = a.view(np.uint32) if a.ndim == 2 else a
+        assert got.dtype == np.float64 and np.array_equal(got, want.astype(np.float64))
+    limit = 100_000
+    part = tmp_path / "part"
+    B.dump_outputs(str(part), out, limit=limit)
+    assert sum(p.stat().st_size for p in part.iterdir()) <= limit + 8 * 128        # (+ the .npy headers)
+    rows = np.load(part / "r_rows.npy").astype(np.int64)
+    assert 0 < len(rows) < n and np.array_equal(rows, np.load(part / "status_rows.npy"))
+    assert np.array_equal(np.load(part / "s.npy"), out[1].view(np.uint32)[rows].astype(np.float64))
+    again = tmp_path / "again"
+    B.dump_outputs(str(again), out, limit=limit)
+    assert all(np.array_equal(np.load(part / p.name), np.load(again / p.name)) for p in part.iterdir())

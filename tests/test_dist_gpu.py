@@ -383,14 +383,14 @@ def test_bench_self_spawns_two_ranks(mode, shape):
 
 
 def test_the_drivers_one_command_tells_both_modes_and_checks_itself():
-    """`bench.py --gpus 2` exactly as the driver starts it (plus --share-device: one GPU here) prints ONE line that carries the
+    """`bench.py --gpus 2 --full` (plus --share-device: one GPU here) prints ONE line that carries the
     session-sharded headline, a per-rank parity sample against the oracle, the all-gather LAYOUT self-test on the real backend,
     and a party-sharded pass at BASELINE config 5's shape (t=2, n=5) with its own rate, all-gather share, bytes per round and
     parity — nothing else is needed from the driver to learn about Mode B."""
     env = dict(os.environ)
     env.pop("RANK", None); env.pop("WORLD_SIZE", None); env.pop("LOCAL_RANK", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-device", "--steps", "1", "--warmup", "1",
-           "--sessions", "128", "--no-configs", "--mode-b-sessions", "32", "--mode-b-steps", "1"]
+           "--sessions", "128", "--full", "--no-configs", "--mode-b-sessions", "32", "--mode-b-steps", "1"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

@@ -17,7 +17,7 @@ cd /tmp && export TMPDIR=/tmp
 BENCH="python $ROOT/bench.py"
 LIGHT="--no-cpu-baseline --no-configs --steps 1"
 
-timeout 900 $BENCH > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
+timeout 900 $BENCH --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
 tail -c 300 "$OUT/bench_default.json"; echo
 
 for mode in session party; do
@@ -31,11 +31,11 @@ done
 # (round 4: the session-mode line carries the all-gather layout self-test, a per-rank parity sample against the oracle and the
 #  party-sharded pass at BASELINE config 5's shape — mode_b{} — so it runs WITH the oracle legs)
 for mode in session party; do
-  timeout 900 $BENCH --gpus 2 --share-device --mode $mode --sessions 16384 --mode-b-sessions 2048 --steps 1 --warmup 1 --no-configs \
+  timeout 900 $BENCH --gpus 2 --share-device --mode $mode --sessions 16384 --mode-b-sessions 2048 --steps 1 --warmup 1 --full --no-configs \
     > "$OUT/bench_2ranks_shared_device_$mode.json" 2> "$OUT/bench_2ranks_shared_device_$mode.err"
   tail -c 200 "$OUT/bench_2ranks_shared_device_$mode.json"; echo
 done
-MPE_FB_WINDOW_BITS=10 timeout 900 $BENCH --gpus 8 --share-device --sessions 512 --mode-b-sessions 256 --steps 1 --warmup 1 --no-configs \
+MPE_FB_WINDOW_BITS=10 timeout 900 $BENCH --gpus 8 --share-device --sessions 512 --mode-b-sessions 256 --steps 1 --warmup 1 --full --no-configs \
   > "$OUT/bench_8ranks_shared_device_session.json" 2> "$OUT/bench_8ranks_shared_device_session.err"
 tail -c 200 "$OUT/bench_8ranks_shared_device_session.json"; echo
 

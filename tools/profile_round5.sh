@@ -20,7 +20,7 @@ for mode in session party; do
     $ROOT/bench.py --gpus 1 --mode $mode $LIGHT --warmup 1 > "$OUT/bench_torchrun1_$mode.json" 2> "$OUT/bench_torchrun1_$mode.err"
   tail -c 200 "$OUT/bench_torchrun1_$mode.json"; echo
 done
-timeout 900 $BENCH --gpus 2 --share-device --mode session --sessions 16384 --mode-b-sessions 2048 --steps 1 --warmup 1 --no-configs \
+timeout 900 $BENCH --gpus 2 --share-device --mode session --sessions 16384 --mode-b-sessions 2048 --steps 1 --warmup 1 --full --no-configs \
   > "$OUT/bench_2ranks_shared_device_session.json" 2> "$OUT/bench_2ranks_shared_device_session.err"
 tail -c 200 "$OUT/bench_2ranks_shared_device_session.json"; echo
 

@@ -51,7 +51,7 @@ for mode in session party; do
     $ROOT/bench.py --gpus 1 --mode $mode $LIGHT --warmup 1 > "$OUT/bench_torchrun1_$mode.json" 2> "$OUT/bench_torchrun1_$mode.err"
   tail -c 200 "$OUT/bench_torchrun1_$mode.json"; echo
 done
-timeout 1500 $BENCH --gpus 8 --share-device --mode session --sessions 4096 --mode-b-sessions 512 --steps 1 --warmup 1 --no-configs --no-cpu-baseline \
+timeout 1500 $BENCH --gpus 8 --share-device --mode session --sessions 4096 --mode-b-sessions 512 --steps 1 --warmup 1 --full --no-configs --no-cpu-baseline \
   > "$OUT/bench_8ranks_shared_device_session.json" 2> "$OUT/bench_8ranks_shared_device_session.err"
 tail -c 300 "$OUT/bench_8ranks_shared_device_session.json"; echo
 timeout 900 $BENCH --gpus 2 --share-device --config5 --sessions 1024 --steps 1 --warmup 1 --no-configs --no-cpu-baseline \

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """How much do the batches of bench.py's c4_stream section overlap on the device?  Input: a rocprofv3 --kernel-trace CSV of
-`bench.py --sessions 1024 --steps 1 --warmup 0 --no-cpu-baseline --only c4_stream`.  The section's window = the last `win_ms`
+`bench.py --sessions 1024 --steps 1 --warmup 0 --full --no-cpu-baseline --only c4_stream`.  The section's window = the last `win_ms`
 of GPU activity (default 1200).  Per queue: launches, busy time; union busy time, pairwise overlap, and a coarse timeline
 (10 ms buckets: which queues had a kernel running).  Usage: trace_streams.py <kernel_trace.csv> [win_ms]"""
 import csv
