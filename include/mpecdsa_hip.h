@@ -79,7 +79,7 @@ int mpe_ctx_set_device_share(mpe_ctx* ctx, int contexts);
  *                  round 1 needs / MessageB's DLog proofs go behind the ladders again)  no_pdl_ahead (round 4 computes the PDL
  *                  proofs' beta^N itself instead of finding it done)  no_prio (no s_setprio in the ladder kernels)
  *                  no_crt_n (the provers' r^e mod N on the 2048-bit ladder instead of through p | q)
- *   integers       fb_window_bits 4..16 | window_bits 0 (auto), 4..6 | wide_div 1..64 | xwide_div 0 (off).. | waves_per_cu 1..8
+ *   integers       fb_window_bits 4..16 | window_bits 0 (auto), 2..6 | wide_div 1..64 | xwide_div 0 (off).. | waves_per_cu 1..8
  *                  fb_budget_mb | fb_split 0 (auto)..64 | sampler_max_attempts 1.. (default 128)
  *   names          grid = equal | full | hybrid
  * MPE_E_ARG (and mpe_last_error) for an unknown key or a value out of range.  mpe_ctx_get_option returns the integer form;

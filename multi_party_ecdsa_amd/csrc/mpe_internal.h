@@ -15,7 +15,7 @@ struct mpe_ctx {
   int device = 0;
   int cus = 256;
   int fb_window_bits = 13;        // window width of the fixed-base tables of h1, h2 (mpe_fixedbase.h); 0.5 GB per base at 13
-  int window_bits = 0;            // 0 = choose per exponent length (4/5/6); 4..6 = force (A/B runs)
+  int window_bits = 0;            // 0 = choose per exponent length (4/5/6); 2..6 = force (A/B runs; 1 is refused)
   bool ec_lane_groups = true;     // small batches: a group of lanes per party in the EC round kernels (mpe_gg20.h)
   bool adaptive_lanes = true;     // small batches: twice the lanes per exponentiation (mpe_pair*.hip)
   bool use_pown = true;           // key holders: x^N mod p^2 as (x^(q mod (p-1)) mod p)^p (mpe_paillier.h modexp_nn)

@@ -334,7 +334,7 @@ static const CtxOption kCtxOptions[] = {
     MPE_OPT_BOOL_OFF("no_merge_xn", merge_xn),               // round 0's x^N in separate launches
     MPE_OPT_BOOL_OFF("no_merge_r1", merge_r1),               // round 1's verification and MessageB ladders in separate launches
     MPE_OPT_INT("fb_window_bits", 4, 16, fb_window_bits),
-    MPE_OPT_INT("window_bits", 0, 6, window_bits),           // 0 = per exponent length
+    MPE_OPT_INT("window_bits", 0, 6, window_bits),           // 0 = per exponent length; 1 is refused below
     MPE_OPT_INT("wide_div", 1, 64, wide_div),
     MPE_OPT_INT("merge_r1_quarters", 0, 64, merge_r1_quarters),
     MPE_OPT_INT("no_r1_inversion_ahead", 0, 1, no_r1_inversion_ahead),
@@ -380,6 +380,8 @@ int mpe_ctx_set_option(mpe_ctx* ctx, const char* key, const char* value) {
       mpe_set_error_msg((std::string("mpe_ctx_set_option: ") + key + " takes an integer in [" + std::to_string(o.lo) + ", " + std::to_string(o.hi) + "]").c_str());
       return MPE_E_ARG;
     }
+    // (the table phase of both ladder kernels writes entry 2 of a window table without asking: a 1-bit window has entries 0 and 1 only)
+    if (!strcmp(key, "window_bits") && v == 1) { mpe_set_error_msg("mpe_ctx_set_option: window_bits takes 0 (auto) or 2..6"); return MPE_E_ARG; }
     o.set(ctx, v);
     return MPE_OK;
   }

@@ -117,7 +117,8 @@ def test_config2_full_size_roundtrip(pk, keys, gpu_ctx):
 
 
 @pytest.mark.parametrize("env", [{"no_pair": 1}, {"no_crt": 1}, {"no_pown": 1}, {"no_pair": 1, "no_crt": 1},
-                                 {"window_bits": 4}, {"window_bits": 5}, {"no_adaptive_lanes": 1}])
+                                 {"window_bits": 2}, {"window_bits": 3}, {"window_bits": 4}, {"window_bits": 5}, {"window_bits": 6},
+                                 {"no_adaptive_lanes": 1}])                    # (window_bits = 1 is refused: tests/test_sampler_gpu.py)
 def test_every_arithmetic_route_gives_the_same_ciphertexts(pk, keys, env):
     """The A/B switches select different algorithms for the same residues (N-adic pairs vs the 4096-bit kernel, the
     holder's p^2|q^2 halves, x^N through a^p, window widths): all of them must agree with the default route, which

@@ -1,6 +1,8 @@
 """The code paths LARGE batches take (one stream, 18 limbs per lane, one-item-per-lane EC round kernels, two-base verifier
 ladders), exercised on small parity cases through a context pinned to them (conftest.gpu_ctx_serial): the ordinary GPU tests
-run tiny batches and therefore the small-batch variants (forks, 5- and 9-limb lanes, lane-group kernels, split inversions)."""
+run tiny batches and therefore the small-batch variants (forks, 5- and 9-limb lanes, lane-group kernels, split inversions).
+Every batch here signs in full; failing sessions beside clean ones on the lock-step schedule and on this context are in
+tests/test_lockstep_failures_gpu.py."""
 import numpy as np
 import pytest
 

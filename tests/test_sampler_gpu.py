@@ -189,6 +189,13 @@ def test_options_are_the_only_switch(gpu_ctx):
         ctx.set_option("wide_div", 0)
     with pytest.raises(E.N_.MpeError):
         ctx.set_option("grid", "diagonal")
+    # window_bits: 0 (chosen per exponent length) or 2..6 — the ladder kernels' table phase has no 1-bit form
+    for bad in (1, 7, -1):
+        with pytest.raises(E.N_.MpeError):
+            ctx.set_option("window_bits", bad)
+    for good in (2, 3, 4, 5, 6, 0):
+        ctx.set_option("window_bits", good)
+        assert ctx.get_option("window_bits") == good
     n = E.N_.lib.mpe_ctx_option_count()
     names = [E.N_.lib.mpe_ctx_option_name(i).decode() for i in range(n)]
     assert {"no_par", "wide_div", "fb_window_bits", "sampler_max_attempts", "grid_mode"} <= set(names)
