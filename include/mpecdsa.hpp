@@ -153,7 +153,21 @@ class DecryptionKeys {
   mpe_paillier* h_ = nullptr;
 };
 
+// `Paillier::keypair()` x count: the minted key material (p, q secret; n = p q)
+struct Keypairs { Batch p, q, n; int failed = 0; };
+
 struct Paillier {
+  // `Paillier::keypair()` (party_i.rs:160) x count, on the device: p, q from streams counter | 0 << 56, counter | 1 << 56 of `seed` (32 bytes,
+  // never reused with the same counter); a key whose search gave up is all zero and counts in `failed`
+  static Keypairs keypair(Context& ctx, const uint8_t* seed32, uint64_t counter, int count) {
+    Dev<uint32_t> dp((size_t)count * W_PRIME, true), dq((size_t)count * W_PRIME, true), dn((size_t)count * W_N);
+    Dev<int32_t> df(std::vector<int32_t>(1, 0));
+    check(mpe_paillier_keygen(ctx.get(), count, seed32, counter, 0, dp.get(), dq.get(), dn.get(), df.get(), nullptr), "mpe_paillier_keygen");
+    ctx.sync();
+    Keypairs k{down(dp, W_PRIME), down(dq, W_PRIME), down(dn, W_N), 0};
+    k.failed = df.download()[0];
+    return k;
+  }
   // `Paillier::encrypt_with_chosen_randomness(&ek, RawPlaintext::from(m), &Randomness::from(r))`   mta/mod.rs:68-75,133-137
   template <class Keys>
   static Batch encrypt_with_chosen_randomness(Context& ctx, const Keys& ek, const Index& key_idx, const Batch& m, const Batch& r) {
@@ -214,6 +228,20 @@ class DLogStatements {
   int count_ = 0;
 };
 }  // namespace zk_paillier
+
+// `generate_h1_h2_N_tilde()` (party_i.rs:137-156) x count, on the device: (N~, h1, h2) and the two secrets xhi = phi - xi,
+// xhi_inv = phi - xi^-1 that the CompositeDLogProofs of keygen round 1 prove knowledge of; streams counter | 2..5 << 56 of `seed`
+struct H1H2NTilde { Batch n_tilde, h1, h2, xhi, xhi_inv; int failed = 0; };
+inline H1H2NTilde generate_h1_h2_N_tilde(Context& ctx, const uint8_t* seed32, uint64_t counter, int count) {
+  const size_t n = (size_t)count * W_N;
+  Dev<uint32_t> a(n), b(n), c(n), d(n, true), e(n, true);
+  Dev<int32_t> df(std::vector<int32_t>(1, 0));
+  check(mpe_ntilde_generate(ctx.get(), count, seed32, counter, 0, a.get(), b.get(), c.get(), d.get(), e.get(), df.get(), nullptr), "mpe_ntilde_generate");
+  ctx.sync();
+  H1H2NTilde o{down(a, W_N), down(b, W_N), down(c, W_N), down(d, W_N), down(e, W_N), 0};
+  o.failed = df.download()[0];
+  return o;
+}
 
 namespace curv {
 // `DLogProof<Secp256k1, Sha256>{pk, pk_t_rand_commitment, challenge_response}`

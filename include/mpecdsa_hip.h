@@ -654,7 +654,7 @@ int mpe_correct_key_verify(mpe_ctx* ctx, int batch, const uint32_t* d_N, const u
 int mpe_composite_dlog_verify(mpe_ctx* ctx, int batch, const uint32_t* d_N, const uint32_t* d_g, const uint32_t* d_ni,
                               const uint32_t* d_x, const uint32_t* d_y, uint8_t* d_ok, void* stream);
 /* The PROVE side of the same two proofs (what a party sends in keygen round 1, party_i.rs:219-258); key generation itself
- * (prime search) stays on the host.
+ * (the prime search) is further down: mpe_paillier_keygen / mpe_ntilde_generate.
  * `NiCorrectKeyProof::proof(dk, SALT_STRING)` for EVERY key of a private key set: d_sigma [nkeys][11][64],
  *   sigma_i = rho_i^(N^-1 mod phi(N)) mod N. */
 int mpe_correct_key_prove(mpe_ctx* ctx, const mpe_paillier* sk, uint32_t* d_sigma, void* stream);
@@ -687,6 +687,31 @@ int mpe_keygen_verify_round1(mpe_ctx* ctx, int batch, int n_parties, const mpe_k
                              void* stream);
 int mpe_keygen_verify_round2(mpe_ctx* ctx, int batch, int n_parties, int t1, const uint32_t* d_commits, const uint32_t* d_share,
                              const int32_t* d_index, const uint32_t* d_y, uint8_t* d_ok, uint32_t* d_bad_actors, void* stream);
+
+/* ---- key MATERIAL: `Keys::create` (party_i.rs:159-177) = `Paillier::keypair()` + `generate_h1_h2_N_tilde()` (:137-156) ----------- */
+/* Batched primality verdict for any value in [0, 2^1024): d_n [batch][32], d_ok [batch].  0 for n < 2 and even n > 2; trial division
+ * by every odd prime below 6370 (a table prime itself is prime, anything below 6370^2 is decided by the table alone); otherwise
+ * `rounds` (1..16) strong-probable-prime (Miller-Rabin) tests.  The bases are FIXED — 2, 3, 5, 7, ... (the first `rounds` primes) —
+ * so this serves self-generated candidates and fixtures, NOT adversarially chosen numbers. */
+int mpe_is_probable_prime(mpe_ctx* ctx, int batch, const uint32_t* d_n, int rounds, uint8_t* d_ok, void* stream);
+/* kzen-paillier `sample_prime` [RECALLED]: attempt a = 0, 1, ... of item g is BigInt::sample(1024) taken from bytes [128 a, 128 a + 128)
+ * of the item's ChaCha20 stream (the sampler's stream definition above), with bit 0 and bit 1023 set — fresh draws, no incremental
+ * search.  d_out [batch][32] = the candidate of the LOWEST attempt < max_attempts (0 = 16384) that passes mpe_is_probable_prime with
+ * 8 rounds, d_attempt [batch] (may be NULL) = that attempt.  DELIBERATE DIVERGENCE from the reference's unbounded loop: an item
+ * without such an attempt gets a zero row, attempt -1, and adds 1 to *d_fail (may be NULL).  An item's result depends on neither
+ * `batch` nor the other items.  bits must be 1024.  Synchronises the stream (once per pass over the unfinished items). */
+int mpe_sample_prime(mpe_ctx* ctx, int batch, const uint8_t* h_seed32, uint64_t stream_id, int bits, int max_attempts, uint32_t* d_out,
+                     int32_t* d_attempt, int32_t* d_fail, void* stream);
+/* Field f of these two calls draws stream `counter | f << 56` (counter < 2^56; the convention of mpe_gg20_sample_nonces), item = row:
+ * f = 0 p, 1 q, 2 p~, 3 q~, 4 h1, 5 xi.  A failed prime or draw zeroes EVERY output row of that item and adds 1 to *d_fail.
+ * `Paillier::keypair()`: d_p, d_q [nkeys][32], d_N [nkeys][64] = p q (as in the reference: no retry for a 2047-bit product or p == q). */
+int mpe_paillier_keygen(mpe_ctx* ctx, int nkeys, const uint8_t* h_seed32, uint64_t counter, int max_attempts, uint32_t* d_p, uint32_t* d_q,
+                        uint32_t* d_N, int32_t* d_fail, void* stream);
+/* `generate_h1_h2_N_tilde()`: N~ = p~ q~, phi = (p~ - 1)(q~ - 1), h1 = sample_below(N~), xi = sample_below(phi) redrawn with fresh
+ * bytes (bounded by option sampler_max_attempts) until gcd(xi, phi) = 1, h2 = h1^xi mod N~; outputs xhi = phi - xi and
+ * xhi_inv = phi - xi^-1 mod phi (the secrets of the two CompositeDLogProofs).  All rows [count][64]. */
+int mpe_ntilde_generate(mpe_ctx* ctx, int count, const uint8_t* h_seed32, uint64_t counter, int max_attempts, uint32_t* d_Nt, uint32_t* d_h1,
+                        uint32_t* d_h2, uint32_t* d_xhi, uint32_t* d_xhi_inv, int32_t* d_fail, void* stream);
 
 /* ---- Lindell'17 two-party ECDSA, signing ---------------------------------------------- */
 /* Party two, `PartialSig::compute(ek, encrypted_secret_share, local_share, ephemeral_local_share,

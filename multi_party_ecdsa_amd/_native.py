@@ -235,6 +235,10 @@ def _load():
         "mpe_gg20_pipeline_latency_ms": (ip, [vp, C.c_uint64, C.POINTER(C.c_float)]),
         "mpe_gg20_pipeline_pass_ms": (ip, [vp, C.c_uint64, C.POINTER(C.c_float)]),
         "mpe_gg20_pipeline_sampler_failures": (ip, [vp, C.POINTER(C.c_int32)]),
+        "mpe_is_probable_prime": (ip, [vp, ip, u32p, ip, vp, vp]),
+        "mpe_sample_prime": (ip, [vp, ip, C.c_char_p, C.c_uint64, ip, ip, u32p, i32p, i32p, vp]),
+        "mpe_paillier_keygen": (ip, [vp, ip, C.c_char_p, C.c_uint64, ip, u32p, u32p, u32p, i32p, vp]),
+        "mpe_ntilde_generate": (ip, [vp, ip, C.c_char_p, C.c_uint64, ip, u32p, u32p, u32p, u32p, u32p, i32p, vp]),
         "mpe_gg20_sample_nonces": (ip, [vp, vp, ip, ip, C.POINTER(C.c_int32), i32p, C.c_char_p, C.c_uint64, C.POINTER(Gg20Nonces), i32p, vp]),
     }
     for name, (res, args) in sig.items():
@@ -273,7 +277,8 @@ EXPORTED = ["mpe_version", "mpe_last_error", "mpe_ctx_create", "mpe_ctx_destroy"
             "mpe_comm_layout_self_test", "mpe_gg20_shard_where", "mpe_gg20_shard_blocks", "mpe_gg20_shard_per_rank", "mpe_gg20_shard_in_off",
             "mpe_gg20_round_exchange", "mpe_gg20_session_abort", "mpe_ctx_set_option", "mpe_ctx_get_option", "mpe_ctx_option_count",
             "mpe_ctx_option_name", "mpe_comm_library", "mpe_gg20_pipeline_ticket_rc", "mpe_gg20_pipeline_inject_fault",
-            "mpe_gg20_pipeline_set_deadline_us", "mpe_gg20_pipeline_set_eager", "mpe_gg20_pipeline_poll", "mpe_gg20_pipeline_counters"]
+            "mpe_gg20_pipeline_set_deadline_us", "mpe_gg20_pipeline_set_eager", "mpe_gg20_pipeline_poll", "mpe_gg20_pipeline_counters",
+            "mpe_is_probable_prime", "mpe_sample_prime", "mpe_paillier_keygen", "mpe_ntilde_generate"]
 
 
 def check(rc, what):

@@ -4,7 +4,7 @@
 //   :322-367  VerifiableSS::validate_share (Feldman), commitments[0] == y_i
 //   :405-438  DLogProof::verify + get_commitments_to_xi
 // and the PROVE side of the two zk-paillier proofs (party_i.rs:219-258: NiCorrectKeyProof::proof, CompositeDLogProof::prove) —
-// modexp-shaped as well.  Prime generation stays on the host: sequential and data dependent, SURVEY.md §2 row 7.
+// modexp-shaped as well.  Prime generation — the key material itself — is in mpe_primes.h (a wide filter-then-modexp search).
 // The two zk-paillier 0.4.3 proofs are un-vendored: their definitions are recalled.  Every key is its own
 // modulus here (one modulus per item), so the moduli set is built per call.  Included by mpe_lib.hip.
 #pragma once

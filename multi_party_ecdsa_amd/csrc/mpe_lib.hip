@@ -269,13 +269,15 @@ static int launch_pair_modexp(mpe_ctx* ctx, const mpe_pairset* ps, int batch, Ro
 #include "mpe_sigma.h"
 #include "mpe_blame.h"
 #include "mpe_keygen.h"
+#include "mpe_primes.h"
 #include "mpe_lindell.h"
 
 extern "C" {
 
 // 0.4: mpe_prof_rec grew (sliding_frac); 0.5: sampler, pipeline, comm, keygen verdicts, session abort; 0.6: options instead of
-// environment switches, per-ticket pass status + grouping rules of the pipeline, status 91, RCCL bound at run time, mpe_comm_library
-const char* mpe_version(void) { return "mpecdsa-hip 0.6.0 (gfx950)"; }
+// environment switches, per-ticket pass status + grouping rules of the pipeline, status 91, RCCL bound at run time, mpe_comm_library;
+// 0.7: key material on the device (mpe_is_probable_prime, mpe_sample_prime, mpe_paillier_keygen, mpe_ntilde_generate)
+const char* mpe_version(void) { return "mpecdsa-hip 0.7.0 (gfx950)"; }
 const char* mpe_last_error(void) { return g_last_error.c_str(); }
 
 void mpe_encoding_default(mpe_encoding* e) {

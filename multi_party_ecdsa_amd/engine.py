@@ -223,8 +223,9 @@ class PaillierKeys:
         self.ctx = ctx
         h = C.c_void_p()
         if p is not None:
-            self.d_p = _dev_u32(ints_to_words(p, 32), ctx.device)
-            self.d_q = _dev_u32(ints_to_words(q, 32), ctx.device)
+            # Python ints, or device word tensors [nkeys, 32] (what paillier_keygen returns)
+            self.d_p = p if torch.is_tensor(p) else _dev_u32(ints_to_words(p, 32), ctx.device)
+            self.d_q = q if torch.is_tensor(q) else _dev_u32(ints_to_words(q, 32), ctx.device)
             N_.check(N_.lib.mpe_paillier_create_private(ctx.h, len(p), _ptr(self.d_p), _ptr(self.d_q), C.byref(h),
                                                         ctx.stream()), "mpe_paillier_create_private")
             self.private = True
@@ -370,7 +371,7 @@ class Statements:
 
     def __init__(self, ctx, Nt, h1, h2):
         self.ctx = ctx
-        self.d = [dev(ctx, v, 64) for v in (Nt, h1, h2)]
+        self.d = [v if torch.is_tensor(v) else dev(ctx, v, 64) for v in (Nt, h1, h2)]      # ints, or device word tensors [count, 64]
         h = C.c_void_p()
         N_.check(N_.lib.mpe_statements_create(ctx.h, len(Nt), _ptr(self.d[0]), _ptr(self.d[1]), _ptr(self.d[2]),
                                               C.byref(h), ctx.stream()), "mpe_statements_create")
@@ -834,6 +835,44 @@ def gg20_sample_nonces(ctx, keys, B, seed, batch_counter, local=None, keyset=Non
     N_.check(N_.lib.mpe_gg20_sample_nonces(ctx.h, keys.h, B, len(local), lc, _ptr(keyset), _seed(seed), int(batch_counter), C.byref(nn), _ptr(fail),
                                            ctx.stream()), "mpe_gg20_sample_nonces")
     return out, fail
+
+
+# ---- key material (mpe_primes.h): `Keys::create` = Paillier::keypair() + generate_h1_h2_N_tilde() (party_i.rs:137-177) ----
+def is_probable_prime(ctx, d_n, rounds=8):
+    """d_n: device words [B, 32] -> uint8 [B]: trial division below 6370, then `rounds` Miller-Rabin tests to the FIXED bases 2, 3, 5, ..."""
+    ok = _flags(ctx, d_n.shape[0])
+    N_.check(N_.lib.mpe_is_probable_prime(ctx.h, d_n.shape[0], _ptr(d_n), rounds, _ptr(ok), ctx.stream()), "mpe_is_probable_prime")
+    return ok
+
+
+def sample_prime(ctx, batch, seed, stream_id, bits=1024, max_attempts=0):
+    """kzen-paillier sample_prime per item: (primes [batch, 32], attempt [batch] (-1: gave up), failures [1])"""
+    out = _new(ctx, batch, bits // 32)
+    attempt = torch.zeros((batch,), dtype=torch.int32, device=ctx.device)
+    fail = torch.zeros((1,), dtype=torch.int32, device=ctx.device)
+    N_.check(N_.lib.mpe_sample_prime(ctx.h, batch, _seed(seed), stream_id, bits, max_attempts, _ptr(out), _ptr(attempt), _ptr(fail), ctx.stream()),
+             "mpe_sample_prime")
+    return out, attempt, fail
+
+
+def paillier_keygen(ctx, nkeys, seed, counter, max_attempts=0):
+    """`Paillier::keypair()` x nkeys: device (p [nkeys, 32], q [nkeys, 32], N [nkeys, 64], failures [1]); PaillierKeys(ctx, p=p, q=q) takes p, q"""
+    p, q, n = _new(ctx, nkeys, 32), _new(ctx, nkeys, 32), _new(ctx, nkeys, 64)
+    fail = torch.zeros((1,), dtype=torch.int32, device=ctx.device)
+    N_.check(N_.lib.mpe_paillier_keygen(ctx.h, nkeys, _seed(seed), int(counter), max_attempts, _ptr(p), _ptr(q), _ptr(n), _ptr(fail), ctx.stream()),
+             "mpe_paillier_keygen")
+    return p, q, n, fail
+
+
+def ntilde_generate(ctx, count, seed, counter, max_attempts=0):
+    """`generate_h1_h2_N_tilde()` x count: dict of device [count, 64] tensors Nt, h1, h2 (Statements(ctx, Nt, h1, h2) takes them), xhi, xhi_inv
+    and the failures [1]"""
+    o = {f: _new(ctx, count, 64) for f in ("Nt", "h1", "h2", "xhi", "xhi_inv")}
+    fail = torch.zeros((1,), dtype=torch.int32, device=ctx.device)
+    N_.check(N_.lib.mpe_ntilde_generate(ctx.h, count, _seed(seed), int(counter), max_attempts, _ptr(o["Nt"]), _ptr(o["h1"]), _ptr(o["h2"]), _ptr(o["xhi"]),
+                                        _ptr(o["xhi_inv"]), _ptr(fail), ctx.stream()), "mpe_ntilde_generate")
+    o["fail"] = fail
+    return o
 
 
 # ---- keygen verification math (gg_2020/party_i.rs:260-438) ----
