@@ -69,6 +69,9 @@ def test_ec_ops_vs_oracle(gpu_ctx):
 
 
 def test_modinv_vs_oracle(gpu_ctx, keys):
+    """B = 24 with three moduli: the LANE-SERIAL kernel (`B <= 32 && ms->count > 1` in launch_modinv).  The batched route — counting
+    sort, sweeps, wave-cooperative gcd, chunk fallback — is compared with the oracle in tests/test_modinv_gpu.py, on the case table of
+    tests/modinv_cases.py."""
     e = E()
     r = F.Rng("gpu-modinv")
     for bits in (2048, 4096):
@@ -159,12 +162,14 @@ def test_alice_proof_golden_and_oracle(gpu_ctx, keys, env):
         assert e.host(pr[f]) == [H(g["proof"][f]) for g in gold], f
 
 
-def test_alice_verify_on_hostile_proof_values(gpu_ctx, keys, env):
+@pytest.mark.parametrize("B", [12, 44])
+def test_alice_verify_on_hostile_proof_values(gpu_ctx, keys, env, B):
     """A prover may send anything: s = N, 0, N - 1, 2^2048 - 1 (>= N), z = N~ or 0, a ciphertext that is a multiple of
-    N, of p, or not reduced.  The GPU verifier must return exactly the oracle's verdicts (all rejections here)."""
+    N, of p, or not reduced.  The GPU verifier must return exactly the oracle's verdicts (all rejections here).
+    B = 12 inverts on the lane-serial kernel; at B = 44 the inversions take the batched route (mpe_modinv.h), where the non-unit
+    ciphertexts share chunks with honest proofs: rows 12.. are honest and must be accepted."""
     e = E()
     pk, stm, tabs = env
-    B = 12
     kidx, sidx, a, rr, c, nn = _alice_inputs(keys, B, "gpu-alice-hostile")
     nw = {f: F.words([n[f] for n in nn], w) for f, w in e.ALICE_NONCE_WORDS.items()}
     di = lambda v: torch.tensor(v, dtype=torch.int32, device=gpu_ctx.device)
@@ -190,15 +195,19 @@ def test_alice_verify_on_hostile_proof_values(gpu_ctx, keys, env):
     ok = e.alice_verify(gpu_ctx, pk, stm, c2, bad, di(kidx), di(sidx))
     want_ok = orc.alice_verify(tabs["N"], tabs["Nt"], tabs["h1"], tabs["h2"], kidx, sidx, npw(c2), {f: npw(v) for f, v in bad.items()})
     assert list(ok.cpu().numpy()) == list(want_ok)
+    want_ok, honest = want_ok[:12], want_ok[12:]             # the hostile rows are the first twelve at every batch size
     assert sum(want_ok[:8]) == 0 and sum(want_ok[10:]) == 0
+    assert list(honest) == [1] * (B - 12) and list(ok.cpu().numpy()[12:]) == [1] * (B - 12)
 
 
-def test_pdl_proof_oracle_and_soundness(gpu_ctx, keys, env):
-    """zk_pdl_with_slack/test.rs:11-68 (prove -> verify) and :70-129 (ciphertext of x+1 -> reject)"""
+@pytest.mark.parametrize("B", [19, 41])
+def test_pdl_proof_oracle_and_soundness(gpu_ctx, keys, env, B):
+    """zk_pdl_with_slack/test.rs:11-68 (prove -> verify) and :70-129 (ciphertext of x+1 -> reject).
+    B = 19 inverts on the lane-serial kernel; at B = 41 the inversions take the batched route (mpe_modinv.h), where the hostile
+    block's non-unit ciphertext shares a chunk with honest proofs."""
     e = E()
     pk, stm, tabs = env
     r = F.Rng("gpu-pdl")
-    B = 19
     kidx, sidx = [i % 4 for i in range(B)], [(i // 3) % 3 for i in range(B)]
     x = [r.below(pyref.Q) for _ in range(B)]
     rr = [r.below(keys[k].N) for k in kidx]
@@ -247,6 +256,8 @@ def test_pdl_proof_oracle_and_soundness(gpu_ctx, keys, env):
                        F.point_words(G), {k: npw(v) for k, v in bad.items()})
     assert list(ok.cpu().numpy()) == list(w)
     assert sum(w[i] for i in (0, 1, 3, 5, 6, 7, 8)) == 0
+    honest = [i for i in range(B) if i not in (0, 1, 2, 3, 5, 6, 7, 8)]      # (row 2 encrypts x + 1)
+    assert all(w[i] == 1 for i in honest) and all(int(ok[i]) == 1 for i in honest)
 
 
 def test_config3_full_size(gpu_ctx, keys):
