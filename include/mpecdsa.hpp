@@ -16,6 +16,8 @@
 //                                                                                 src/protocols/two_party_ecdsa/lindell_2017/party_two.rs:390-423, party_one.rs:519-565
 //   gg_2020::state_machine::sign::{OfflineStage, CompletedOfflineStage, SignManual}  gg_2020/state_machine/sign.rs:66-330,540-646
 //       (one party of `batch` concurrent signing sessions: `RoundN::proceed`, state_machine/sign/rounds.rs:68-692)
+//   gg_2020::{VerifiableSS::share, Keys::{phase2_verify_vss, phase2_construct_keypair_phase3_pok_dlog,
+//             verify_dlog_proofs_check_against_vss}}                             gg_2020/party_i.rs:260-438
 //
 // Values sampled from OsRng inside the reference's primitives are explicit arguments (`*Nonces`), which is what makes a bit-exact
 // comparison possible; `bool` / `Result<(), _>` returns become one flag per item (a bad item never aborts the batch — the
@@ -541,6 +543,65 @@ struct LocalKey {
   Batch pk_vec;                                 // [n][16]  X_j = x_j G
   Batch x_i;                                    // [1][8]   `keys_linear.x_i`
   Batch p, q;                                   // [1][32]  `paillier_dk`
+};
+
+// ---- keygen: dealing, the key pair and the verdicts of rounds 2 and 3 (gg_2020/party_i.rs:260-438), batched ----
+// curv `VerifiableSS<Secp256k1>` x batch: `commitments` [batch][t + 1][16]
+struct VerifiableSS {
+  uint16_t threshold = 0, share_count = 0;
+  Batch commitments;
+  // `VerifiableSS::share(t, n, &secret)` with the sampled coefficients an input: coef [batch][t + 1][8], coef[.][0] = the secret.
+  // Returns the scheme and the shares [batch][n][8] (shares[.][j] goes to party j + 1).
+  static std::pair<VerifiableSS, Batch> share(Context& ctx, uint16_t t, uint16_t n, const Batch& coef) {
+    const int t1 = t + 1, B = (int)(coef.w.size() / ((size_t)t1 * W_SCALAR));
+    Dev<uint32_t> c = up_secret(coef), com((size_t)B * t1 * W_POINT), sh((size_t)B * n * W_SCALAR, true);
+    check(mpe_vss_share(ctx.get(), B, t1, n, c.get(), com.get(), sh.get(), nullptr), "mpe_vss_share");
+    ctx.sync();
+    return {VerifiableSS{t, n, down(com, t1 * W_POINT)}, down(sh, n * W_SCALAR)};
+  }
+};
+struct SharedKeys { Batch y, x_i; };           // [batch][16], [batch][8]
+struct Keys {
+  // the verdict of `Keys::phase2_verify_vss_construct_keypair_phase3_pok_dlog` (party_i.rs:335-348) over items = (verifier, dealer):
+  // commitments [batch][t + 1][16], secret_shares [batch][8], index [batch] (the verifier's), y [batch][16]; `n` consecutive items
+  // form one call of the reference, bad_actors (if given) gets one mask per call
+  static Flags phase2_verify_vss(Context& ctx, uint16_t n, const VerifiableSS& vss, const Batch& secret_shares, const Index& index, const Batch& y,
+                                 std::vector<uint32_t>* bad_actors = nullptr) {
+    const int B = (int)secret_shares.size();
+    Dev<uint32_t> c = up(vss.commitments), s = up_secret(secret_shares), yy = up(y), bad((size_t)(B / n));
+    Dev<int32_t> ix(index);
+    Dev<uint8_t> ok((size_t)B);
+    check(mpe_keygen_verify_round2(ctx.get(), B, n, vss.threshold + 1, c.get(), s.get(), ix.get(), yy.get(), ok.get(), bad.get(), nullptr), "mpe_keygen_verify_round2");
+    ctx.sync();
+    if (bad_actors) *bad_actors = bad.download();
+    return ok.download();
+  }
+  // its OK branch (party_i.rs:355-363) over items = receiving party: secret_shares [batch][n][8] in dealer order, y_vec [batch][n][16],
+  // the DLogProof nonce [batch][8] an input -> (SharedKeys{y, x_i}, DLogProof::prove(&x_i))
+  static std::pair<SharedKeys, curv::DLogProof> phase2_construct_keypair_phase3_pok_dlog(Context& ctx, uint16_t n, const Batch& secret_shares, const Batch& y_vec,
+                                                                                        const Batch& nonce) {
+    const int B = (int)nonce.size();
+    Dev<uint32_t> s = up_secret(secret_shares), yv = up(y_vec), k = up_secret(nonce), x((size_t)B * W_SCALAR, true), y((size_t)B * W_POINT),
+                  pk((size_t)B * W_POINT), R((size_t)B * W_POINT), z((size_t)B * W_SCALAR);
+    check(mpe_keygen_construct_keypair(ctx.get(), B, n, s.get(), yv.get(), k.get(), x.get(), y.get(), pk.get(), R.get(), z.get(), nullptr),
+          "mpe_keygen_construct_keypair");
+    ctx.sync();
+    return {SharedKeys{down(y, W_POINT), down(x, W_SCALAR)}, curv::DLogProof{down(pk, W_POINT), down(R, W_POINT), down(z, W_SCALAR)}};
+  }
+  // `Keys::verify_dlog_proofs_check_against_vss` (party_i.rs:405-438): item (s, i) = dealer i's scheme and party i's proof, `n` consecutive
+  // items form one session; one flag per party, bad_actors (if given) one mask per session
+  static Flags verify_dlog_proofs_check_against_vss(Context& ctx, uint16_t n, const curv::DLogProof& dlog_proofs_vec, const VerifiableSS& vss_vec,
+                                                    std::vector<uint32_t>* bad_actors = nullptr) {
+    const int B = (int)dlog_proofs_vec.pk.size();
+    Dev<uint32_t> c = up(vss_vec.commitments), pk = up(dlog_proofs_vec.pk), R = up(dlog_proofs_vec.pk_t_rand_commitment),
+                  z = up(dlog_proofs_vec.challenge_response), bad((size_t)(B / n));
+    Dev<uint8_t> ok((size_t)B);
+    check(mpe_keygen_verify_round3(ctx.get(), B, n, vss_vec.threshold + 1, c.get(), pk.get(), R.get(), z.get(), ok.get(), bad.get(), nullptr, nullptr),
+          "mpe_keygen_verify_round3");
+    ctx.sync();
+    if (bad_actors) *bad_actors = bad.download();
+    return ok.download();
+  }
 };
 
 // Every value ONE party samples from OsRng while signing, for `batch` sessions: the C-ABI's mpe_gg20_nonces with one local party

@@ -687,6 +687,33 @@ int mpe_keygen_verify_round1(mpe_ctx* ctx, int batch, int n_parties, const mpe_k
                              void* stream);
 int mpe_keygen_verify_round2(mpe_ctx* ctx, int batch, int n_parties, int t1, const uint32_t* d_commits, const uint32_t* d_share,
                              const int32_t* d_index, const uint32_t* d_y, uint8_t* d_ok, uint32_t* d_bad_actors, void* stream);
+/* The rest of keygen: dealing, the key pair, and the verdict of round 3.  Sampled values are inputs; all three run on the caller's
+ * stream without synchronising it.
+ * mpe_vss_share = `VerifiableSS::share(t, n, &u_i)` (the dealing of party_i.rs:260-320), item = one dealer of one session:
+ *   d_coef [batch][t1][8]: coef[0] = the secret u_i, coef[1..t] the sampled coefficients, each reduced mod q as read;
+ *   d_commits [batch][t1][16] = coef[k] G (comb tables of the generator);  d_shares [batch][n][8], shares[j] = f(j + 1) mod q.
+ *   A coefficient that is 0 mod q gives the neutral (all-zero) commitment row: mpe_vss_validate_share refuses every share of such
+ *   a sharing, and mpe_keygen_verify_round3 its session (the reference samples non-zero coefficients).
+ * mpe_keygen_construct_keypair = the OK branch of `phase2_verify_vss_construct_keypair_phase3_pok_dlog` (party_i.rs:355-363), item =
+ *   (session, receiving party): d_shares [batch][n][8] = the n shares that party received, in dealer order, d_y [batch][n][16] = y_vec,
+ *   d_nonce [batch][8];  d_x = x_i = sum of the shares mod q, d_ysum = y = sum of y_vec (exact for equal and opposite summands; the
+ *   neutral element is the all-zero row), (d_pk, d_R, d_z) = `DLogProof::prove(&x_i)` — the words mpe_dlog_prove gives for (x_i, nonce)
+ *   under the context's encoding.  No verdict here: that is mpe_keygen_verify_round2.
+ * mpe_keygen_verify_round3 = `Keys::verify_dlog_proofs_check_against_vss` (party_i.rs:405-438), item (s, i) = dealer i's commitments
+ *   d_commits [batch][t1][16] and party i's proof (d_pk, d_R [batch][16], d_z [batch][8]); `n_parties` consecutive items form a session:
+ *   ok = DLogProof::verify(proof_i) (as mpe_dlog_verify)  &&  xi_commit[s][i] == pk_i,  xi_commit[s][i] = sum_k (i + 1)^k sum_j C[s][j][k]
+ *   (`get_commitments_to_xi`, :369-388; the inner sums are formed once per session).  d_bad_actors [batch / n_parties] (may be NULL) as
+ *   in rounds 1 and 2; d_xi_commit [batch][16] (may be NULL) receives the commitments.  `y_vec` is only length-checked by the reference
+ *   and is no argument.  n_parties <= 32.
+ *   DELIBERATE DIVERGENCE: the reference cannot hold a point that is off the curve (curv refuses it when it deserialises).  Here a
+ *   commitment row that is no valid point (off the curve, not canonical, or neutral) refuses EVERY item of its session — all n bits of
+ *   the mask — and that session's d_xi_commit rows are neutral; an invalid pk or R refuses its own item only. */
+int mpe_vss_share(mpe_ctx* ctx, int batch, int t1, int n, const uint32_t* d_coef, uint32_t* d_commits, uint32_t* d_shares, void* stream);
+int mpe_keygen_construct_keypair(mpe_ctx* ctx, int batch, int n, const uint32_t* d_shares, const uint32_t* d_y, const uint32_t* d_nonce,
+                                 uint32_t* d_x, uint32_t* d_ysum, uint32_t* d_pk, uint32_t* d_R, uint32_t* d_z, void* stream);
+int mpe_keygen_verify_round3(mpe_ctx* ctx, int batch, int n_parties, int t1, const uint32_t* d_commits, const uint32_t* d_pk,
+                             const uint32_t* d_R, const uint32_t* d_z, uint8_t* d_ok, uint32_t* d_bad_actors, uint32_t* d_xi_commit,
+                             void* stream);
 
 /* ---- key MATERIAL: `Keys::create` (party_i.rs:159-177) = `Paillier::keypair()` + `generate_h1_h2_N_tilde()` (:137-156) ----------- */
 /* Batched primality verdict for any value in [0, 2^1024): d_n [batch][32], d_ok [batch].  0 for n < 2 and even n > 2; trial division

@@ -205,6 +205,9 @@ def _load():
         "mpe_paillier_mul": (ip, [vp, vp, ip, i32p, u32p, u32p, ip, u32p, vp]),
         "mpe_keygen_verify_round1": (ip, [vp, ip, ip, C.POINTER(KeygenRound1), vp, u32p, vp]),
         "mpe_keygen_verify_round2": (ip, [vp, ip, ip, ip, u32p, u32p, i32p, u32p, vp, u32p, vp]),
+        "mpe_vss_share": (ip, [vp, ip, ip, ip, u32p, u32p, u32p, vp]),
+        "mpe_keygen_construct_keypair": (ip, [vp, ip, ip, u32p, u32p, u32p, u32p, u32p, u32p, u32p, u32p, vp]),
+        "mpe_keygen_verify_round3": (ip, [vp, ip, ip, ip, u32p, u32p, u32p, u32p, vp, u32p, u32p, vp]),
         "mpe_comm_unique_id": (ip, [C.c_char_p]),
         "mpe_comm_create": (ip, [vp, C.c_char_p, ip, ip, C.POINTER(vp)]),
         "mpe_comm_destroy": (ip, [vp]),
@@ -278,7 +281,8 @@ EXPORTED = ["mpe_version", "mpe_last_error", "mpe_ctx_create", "mpe_ctx_destroy"
             "mpe_gg20_round_exchange", "mpe_gg20_session_abort", "mpe_ctx_set_option", "mpe_ctx_get_option", "mpe_ctx_option_count",
             "mpe_ctx_option_name", "mpe_comm_library", "mpe_gg20_pipeline_ticket_rc", "mpe_gg20_pipeline_inject_fault",
             "mpe_gg20_pipeline_set_deadline_us", "mpe_gg20_pipeline_set_eager", "mpe_gg20_pipeline_poll", "mpe_gg20_pipeline_counters",
-            "mpe_is_probable_prime", "mpe_sample_prime", "mpe_paillier_keygen", "mpe_ntilde_generate"]
+            "mpe_is_probable_prime", "mpe_sample_prime", "mpe_paillier_keygen", "mpe_ntilde_generate",
+            "mpe_vss_share", "mpe_keygen_construct_keypair", "mpe_keygen_verify_round3"]
 
 
 def check(rc, what):

@@ -269,6 +269,7 @@ static int launch_pair_modexp(mpe_ctx* ctx, const mpe_pairset* ps, int batch, Ro
 #include "mpe_sigma.h"
 #include "mpe_blame.h"
 #include "mpe_keygen.h"
+#include "mpe_keygen_deal.h"
 #include "mpe_primes.h"
 #include "mpe_lindell.h"
 

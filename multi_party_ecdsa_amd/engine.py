@@ -939,6 +939,116 @@ def vss_point_commitment(ctx, t1, d_commits, d_index):
     return out
 
 
+# ---- the rest of keygen: dealing, the key pair, round 3 (gg_2020/party_i.rs:260-438) ----
+def vss_share(ctx, n, d_coef):
+    """`VerifiableSS::share(t, n, &u_i)` per dealer: d_coef [B, t+1, 8] (coef[0] = u_i) -> (commits [B, t+1, 16], shares [B, n, 8]),
+    shares[b, j] = f_b(j + 1).  A zero coefficient gives a neutral commitment row, which vss_validate_share refuses."""
+    B, t1 = d_coef.shape[0], d_coef.shape[1]
+    commits = torch.empty((B, t1, 16), dtype=torch.int32, device=ctx.device)
+    shares = torch.empty((B, n, 8), dtype=torch.int32, device=ctx.device)
+    N_.check(N_.lib.mpe_vss_share(ctx.h, B, t1, n, _ptr(d_coef), _ptr(commits), _ptr(shares), ctx.stream()), "mpe_vss_share")
+    return commits, shares
+
+
+def keygen_construct_keypair(ctx, d_shares, d_y, d_nonce):
+    """the OK branch of `phase2_verify_vss_construct_keypair_phase3_pok_dlog` (party_i.rs:355-363) over items = (session, receiving party):
+    d_shares [B, n, 8] received shares in dealer order, d_y [B, n, 16], d_nonce [B, 8] -> (x, ysum, pk, R, z); (pk, R, z) = dlog_prove(x, nonce)"""
+    B, n = d_shares.shape[0], d_shares.shape[1]
+    x, ysum, pk, R, z = _new(ctx, B, 8), _new(ctx, B, 16), _new(ctx, B, 16), _new(ctx, B, 16), _new(ctx, B, 8)
+    N_.check(N_.lib.mpe_keygen_construct_keypair(ctx.h, B, n, _ptr(d_shares), _ptr(d_y), _ptr(d_nonce), _ptr(x), _ptr(ysum), _ptr(pk), _ptr(R), _ptr(z),
+                                                 ctx.stream()), "mpe_keygen_construct_keypair")
+    return x, ysum, pk, R, z
+
+
+def keygen_verify_round3(ctx, n_parties, d_commits, d_pk, d_R, d_z, want_xi=False):
+    """`Keys::verify_dlog_proofs_check_against_vss` (party_i.rs:405-438) over items (session, i) = dealer i's commitments
+    d_commits [B, t+1, 16] and party i's proof.  Returns (ok [B] uint8, bad_actors [B / n_parties] int32 masks[, xi_commit [B, 16]])."""
+    B, t1 = d_commits.shape[0], d_commits.shape[1]
+    ok = _flags(ctx, B)
+    bad = torch.zeros((B // n_parties,), dtype=torch.int32, device=ctx.device)
+    xi = _new(ctx, B, 16) if want_xi else None
+    N_.check(N_.lib.mpe_keygen_verify_round3(ctx.h, B, n_parties, t1, _ptr(d_commits), _ptr(d_pk), _ptr(d_R), _ptr(d_z), _ptr(ok), _ptr(bad), _ptr(xi),
+                                             ctx.stream()), "mpe_keygen_verify_round3")
+    return (ok, bad, xi) if want_xi else (ok, bad)
+
+
+KEYGEN_MATERIAL_FIELDS = ("p", "q", "pt", "qt", "h1", "xi")        # rows [B*n, 32] x 4, [B*n, 64] x 2
+
+
+def gg20_keygen(ctx, t, n, B, seed, counter=0, material=None, _fault=None):
+    """`Keygen` (gg_2020/state_machine/keygen/rounds.rs) for B wallets in lock step with all n parties local, the counterpart of gg20_sign:
+    a chain of C-ABI calls, rows = (wallet, party).
+      material: None = mint the Paillier / N~ material on the device (streams counter | 0..5 << 56 of `seed`); or a dict of uint32
+                arrays KEYGEN_MATERIAL_FIELDS (p, q, p~, q~ [B n, 32]; h1, xi [B n, 64]) taken as generate_h1_h2_N_tilde would have
+                drawn them (N, N~, h2 = h1^xi and the two proof secrets are derived on the host).
+      u_i, blind factors, VSS coefficients, the DLog nonces and the two CompositeDLog nonces: streams counter | 8..13 << 56.
+      _fault:   a test aid, not part of the interface: (wallet, dealer, party) flips bit 0 of the share that dealer sends to that party
+                before round 2, as Gg20Session.fault_inject does for signing (tests/test_keygen_deal_gpu.py walks the blame path with it).
+    Returns a dict: ok [B] uint8 (all three verdicts of every party), bad1 [B] (provers of round 1), bad2 [B, n] (per receiving party,
+    the dealers round 2 blames), bad3 [B] (round 3), commits [B n, t+1, 16], xi_commit [B n, 16], failures (sampler / prime search
+    give-ups) and `arrays`, the layout Gg20Keys takes with nkeysets = B."""
+    P, t1 = B * n, t + 1
+    if counter >> 56:
+        raise ValueError("counter < 2^56")
+    sid = lambda f: int(counter) | (f << 56)
+    fails = []
+    if material is None:
+        p, q, N, f = paillier_keygen(ctx, P, seed, counter)
+        nt = ntilde_generate(ctx, P, seed, counter)
+        Nt, h1, h2, xhi, xhi_inv = nt["Nt"], nt["h1"], nt["h2"], nt["xhi"], nt["xhi_inv"]
+        fails += [f, nt["fail"]]
+    else:
+        m = {f: words_to_ints(np.ascontiguousarray(material[f])) for f in KEYGEN_MATERIAL_FIELDS}
+        if any(len(v) != P for v in m.values()):
+            raise ValueError("material: B * n rows per field")
+        phi = [(a - 1) * (b - 1) for a, b in zip(m["pt"], m["qt"])]
+        nts = [a * b for a, b in zip(m["pt"], m["qt"])]
+        up = lambda vals, w: dev(ctx, vals, w)
+        p, q, N = up(m["p"], 32), up(m["q"], 32), up([a * b for a, b in zip(m["p"], m["q"])], 64)
+        Nt, h1 = up(nts, 64), up(m["h1"], 64)
+        h2 = up([pow(h, x, nn) for h, x, nn in zip(m["h1"], m["xi"], nts)], 64)
+        xhi = up([f_ - x for f_, x in zip(phi, m["xi"])], 64)
+        xhi_inv = up([f_ - pow(x, -1, f_) for f_, x in zip(phi, m["xi"])], 64)
+    u, f = sample_scalar(ctx, P, seed, sid(8))
+    fails.append(f)
+    blind = sample_bits(ctx, P, seed, sid(9), 256, 8)
+    coef = u.reshape(P, 1, 8)
+    if t:
+        a, f = sample_scalar(ctx, P * t, seed, sid(10))
+        fails.append(f)
+        coef = torch.cat([coef, a.reshape(P, t, 8)], dim=1).contiguous()
+    nonce, f = sample_scalar(ctx, P, seed, sid(11))
+    fails.append(f)
+    r1, r2 = sample_bits(ctx, P, seed, sid(12), 512, 16), sample_bits(ctx, P, seed, sid(13), 512, 16)
+    # round 1 (party_i.rs:219-320): y_i = u_i G, its hash commitment, NiCorrectKeyProof, the two CompositeDLogProofs; every prover is verified
+    y = ec_mul_base(ctx, u)
+    sk = PaillierKeys(ctx, p=p, q=q)
+    msgs = dict(y=y, blind=blind, com=hash_commit_point(ctx, y, blind), N=N, sigma=correct_key_prove(ctx, sk).reshape(P, 11 * 64), Nt=Nt, h1=h1, h2=h2)
+    msgs["x_h1"], msgs["y_h1"] = composite_dlog_prove(ctx, Nt, h1, h2, xhi, r1)
+    msgs["x_h2"], msgs["y_h2"] = composite_dlog_prove(ctx, Nt, h2, h1, xhi_inv, r2)
+    ok1, bad1 = keygen_verify_round1(ctx, n, msgs)
+    sk.close()
+    # round 2 (:322-367): deal, then party r checks dealer j's share: items ((wallet, r), j)
+    commits, shares = vss_share(ctx, n, coef)
+    recv = shares.reshape(B, n, n, 8).transpose(1, 2).contiguous()                     # [wallet, receiver, dealer]
+    if _fault is not None:
+        w_, j_, r_ = _fault
+        recv[w_, r_, j_, 0] ^= 1
+    c_it = commits.reshape(B, 1, n, t1 * 16).expand(B, n, n, t1 * 16).reshape(P * n, t1 * 16).contiguous()
+    y_it = y.reshape(B, 1, n, 16).expand(B, n, n, 16).contiguous()
+    idx = (torch.arange(n, dtype=torch.int32, device=ctx.device) + 1).reshape(1, n, 1).expand(B, n, n).reshape(P * n).contiguous()
+    ok2, bad2 = keygen_verify_round2(ctx, n, t1, c_it, recv.reshape(P * n, 8), idx, y_it.reshape(P * n, 16))
+    # :355-363 and round 3 (:405-438)
+    x, ysum, pk, R, z = keygen_construct_keypair(ctx, recv.reshape(P, n, 8), y_it.reshape(P, n, 16), nonce)
+    ok3, bad3, xi = keygen_verify_round3(ctx, n, commits, pk, R, z, want_xi=True)
+    ok = ok1.reshape(B, n).bool().all(1) & ok2.reshape(B, n * n).bool().all(1) & ok3.reshape(B, n).bool().all(1)
+    ctx.sync()
+    arrays = {f: _to_np_u32(v) for f, v in dict(x=x, p=p, q=q, N=N, Nt=Nt, h1=h1, h2=h2, X=pk).items()}
+    arrays["y"] = np.ascontiguousarray(_to_np_u32(ysum).reshape(B, n, 16)[:, 0])
+    return dict(ok=ok.to(torch.uint8), bad1=bad1, bad2=bad2.reshape(B, n), bad3=bad3, commits=commits, xi_commit=xi,
+                failures=int(sum(int(f.item()) for f in fails)), arrays=arrays)
+
+
 # ---- identifiable abort (gg_2020/blame.rs) ----
 def gg20_blame5(ctx, keys, B, opened, keyset=None):
     """opened: dict of device tensors (fields _native.Blame5In) -> bad_actors bit masks [B] (device int32)"""
