@@ -1,4 +1,4 @@
-// Internal definitions shared by the parts of libmpecdsa_hip.so (one translation unit: mpe_lib.hip).
+// Internal definitions shared by the parts of libmpecdsa_hip.so (three translation units: mpe_lib.hip, mpe_pair2048.hip, mpe_pair1024.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -17,7 +17,7 @@ struct mpe_ctx {
   int fb_window_bits = 13;        // window width of the fixed-base tables of h1, h2 (mpe_fixedbase.h); 0.5 GB per base at 13
   int window_bits = 0;            // 0 = choose per exponent length (4/5/6); 2..6 = force (A/B runs; 1 is refused)
   bool ec_lane_groups = true;     // small batches: a group of lanes per party in the EC round kernels (mpe_gg20.h)
-  bool adaptive_lanes = true;     // small batches: twice the lanes per exponentiation (mpe_pair*.hip)
+  bool adaptive_lanes = true;     // small batches: more lanes per exponentiation (mpe_pairexp.h pair_modexp_dispatch)
   bool use_pown = true;           // key holders: x^N mod p^2 as (x^(q mod (p-1)) mod p)^p (mpe_paillier.h modexp_nn)
   bool use_pair = true;           // arithmetic modulo N^2 / p^2 in N-adic pair form (mpe_pairexp.h): half the multiplies
   bool use_multiexp = true;       // verifiers: s^N * (c^-1)^e on one ladder instead of two exponentiations (same residue)
@@ -29,7 +29,7 @@ struct mpe_ctx {
                                   // would put two waves on every SIMD (38 ms) — re-measured with the scheduler of round 6 (rounds 2-5: 2)
   int device_share = 1;           // contexts expected to run on this device AT THE SAME TIME (mpe_ctx_set_device_share): the small-batch
                                   // heuristics below compare a launch with 1/device_share of the chip, not with all of it
-  int xwide_div = 16;             // the 4x-lanes (5 limbs per lane) layout: xwide_div * batch <= the resident groups; 0 = off (MPE_XWIDE_DIV)
+  int xwide_div = 16;             // the 4x-lanes (5 limbs per lane) layout: xwide_div * batch <= the resident groups; 0 = off (option xwide_div)
   bool merge_xn = true;           // round 0: every x^N of the key holders in ONE launch (MPE_NO_MERGE_XN switches it off)
   int use_prio = 1;               // wave priorities in the small-batch schedule (option no_prio; the pipelined engine's lanes run without)
   int ladder_prio = 1;            // s_setprio of the NEXT ladder launches (mpe_sched.h wave_priority): 1 = the default of ladders, 2 = the pair

@@ -9,23 +9,7 @@ int pairset_create_1024(int count, const uint32_t* d_moduli, mpe_pairset** out, 
 }
 int pair_modexp_1024(mpe_ctx* ctx, const mpe_pairset* ps, int batch, Rows mod_sel, Rows base, Rows exps, int exp_words,
                      Rows base2, Rows exps2, int exp2_words, int half, uint32_t* out, hipStream_t st, int public_exp) {
-  // A launch lasts as long as ONE exponentiation however few there are.  When the batch fills less than half of
-  // the resident groups, spread every integer over twice the lanes (9 limbs per lane): the same limbs, the same
-  // per-modulus constants, about half the latency.
-  using Wide = Cfg<1024, MPE_W, MPE_L / 2, 4>;
-  static_assert(Wide::K == Cfg1024::K, "the two layouts share the limb arrays");
-  const long resident = (long)ctx->cus * ctx->modexp_waves_per_cu * Cfg1024::GROUPS / ctx->device_share;   // this context's share of the chip
-  // ... and a really small batch (a sixteenth of the resident groups) over four times the lanes (5 limbs per lane: the same
-  // constants, zero-padded).  Measured (profiles/r03/xwide_sweep.json): -6 % per batch at 256 sessions, nothing at 1 024 and
-  // +13 % when the threshold lets mid-size launches take it: with 10 MACs per step the quotient-digit dependency chain
-  // (mad -> mul_lo -> three DPP moves -> mad) is no longer hidden, so the layout only pays while the chip is nearly empty.
-  using XWide = Cfg<1024, MPE_W, 5, 8>;
-  const int xdiv = ctx->xwide_div;                            // MPE_XWIDE_DIV, read when the context was created; 0 switches the layout off
-  if (ctx->adaptive_lanes && xdiv > 0 && (long)xdiv * batch <= resident)
-    return pair_modexp_impl<XWide>(ctx, ps, batch, mod_sel, base, exps, exp_words, base2, exps2, exp2_words, half, out, st, public_exp);
-  if (ctx->adaptive_lanes && (long)ctx->wide_div * batch <= resident)
-    return pair_modexp_impl<Wide>(ctx, ps, batch, mod_sel, base, exps, exp_words, base2, exps2, exp2_words, half, out, st, public_exp);
-  return pair_modexp_impl<Cfg1024>(ctx, ps, batch, mod_sel, base, exps, exp_words, base2, exps2, exp2_words, half, out, st, public_exp);
+  return pair_modexp_dispatch<1024, 2>(ctx, ps, batch, mod_sel, base, exps, exp_words, base2, exps2, exp2_words, half, out, st, public_exp);
 }
 
 }  // namespace mpe

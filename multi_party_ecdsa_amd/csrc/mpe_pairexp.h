@@ -806,4 +806,29 @@ int pair_modexp_impl(mpe_ctx* ctx, const mpe_pairset* ps, int batch, Rows mod_se
   return MPE_OK;
 }
 
+// The lane layout of a launch: BITS-bit moduli on TPI lanes of 18 limbs, or on 2 TPI lanes of 9, or on 4 TPI lanes of 5.
+// A launch lasts as long as ONE exponentiation however few there are.  When the batch fills less than 1 / wide_div of the resident
+// groups (option `wide_div`, mpe_internal.h), every integer is spread over twice the lanes (9 limbs per lane): the same limbs, the
+// same per-modulus constants, about half the latency.  A really small batch (1 / xwide_div of the resident groups: a sixteenth;
+// option `xwide_div`, 0 switches the layout off) goes over four times the lanes (5 limbs per lane: the same constants,
+// zero-padded).  Measured (profiles/r03/xwide_sweep.json): -6 % per batch at 256 sessions, nothing at 1 024 and +13 % when the
+// threshold lets mid-size launches take it: with 10 MACs per step the quotient-digit dependency chain (mad -> mul_lo -> three DPP
+// moves -> mad) is no longer hidden, so the layout only pays while the chip is nearly empty.
+template <int BITS, int TPI>
+int pair_modexp_dispatch(mpe_ctx* ctx, const mpe_pairset* ps, int batch, Rows mod_sel, Rows base, Rows exps, int exp_words,
+                         Rows base2, Rows exps2, int exp2_words, int half, uint32_t* out, hipStream_t st, int public_exp) {
+  using Base = Cfg<BITS, MPE_W, MPE_L, TPI>;
+  using Wide = Cfg<BITS, MPE_W, MPE_L / 2, 2 * TPI>;
+  using XWide = Cfg<BITS, MPE_W, 5, 4 * TPI>;
+  static_assert(std::is_same<Base, Cfg2048>::value || std::is_same<Base, Cfg1024>::value, "the 18-limb layout is the one of mpe_bigint.h");
+  static_assert(Wide::K == Base::K, "the two layouts share the limb arrays");
+  const long resident = (long)ctx->cus * ctx->modexp_waves_per_cu * Base::GROUPS / ctx->device_share;   // this context's share of the chip
+  const int xdiv = ctx->xwide_div;
+  if (ctx->adaptive_lanes && xdiv > 0 && (long)xdiv * batch <= resident)
+    return pair_modexp_impl<XWide>(ctx, ps, batch, mod_sel, base, exps, exp_words, base2, exps2, exp2_words, half, out, st, public_exp);
+  if (ctx->adaptive_lanes && (long)ctx->wide_div * batch <= resident)
+    return pair_modexp_impl<Wide>(ctx, ps, batch, mod_sel, base, exps, exp_words, base2, exps2, exp2_words, half, out, st, public_exp);
+  return pair_modexp_impl<Base>(ctx, ps, batch, mod_sel, base, exps, exp_words, base2, exps2, exp2_words, half, out, st, public_exp);
+}
+
 }  // namespace mpe

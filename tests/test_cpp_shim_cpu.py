@@ -5,11 +5,12 @@ status 1, no crash, no CPU fallback.  The -m gpu counterpart (tests/test_cpp_shi
 import os
 import subprocess
 
+import cpp_build
 import cpp_shim
 
 
 def test_cpp_host_layer_builds_and_fails_loudly_without_a_gpu(tmp_path, keys):
-    exe = cpp_shim.build(str(tmp_path))
+    exe = cpp_build.build("test_shim", str(tmp_path))
     fx = os.path.join(str(tmp_path), "fixture.bin")
     arrays = cpp_shim.write_fixture(fx, keys)
     assert arrays["al_alpha"].shape == (12, 24) and os.path.getsize(fx) > 10000

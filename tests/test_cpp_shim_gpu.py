@@ -12,13 +12,14 @@ import subprocess
 
 import pytest
 
+import cpp_build
 import cpp_shim
 
 pytestmark = pytest.mark.gpu
 
 
 def test_reference_unit_tests_over_the_cpp_host_layer(tmp_path, keys):
-    exe = cpp_shim.build(str(tmp_path))
+    exe = cpp_build.build("test_shim", str(tmp_path))
     fx = os.path.join(str(tmp_path), "fixture.bin")
     cpp_shim.write_fixture(fx, keys)
     p = subprocess.run([exe, fx], capture_output=True, text=True, timeout=600)
@@ -41,7 +42,7 @@ def test_party_sharded_over_rccl_between_two_gpus_compiled_host(tmp_path, keys):
     import torch
     if torch.cuda.device_count() < 2:
         pytest.skip("needs two GPUs (the driver's multi-GPU node); the world-1 form runs in the test above")
-    exe = cpp_shim.build(str(tmp_path))
+    exe = cpp_build.build("test_shim", str(tmp_path))
     fx = os.path.join(str(tmp_path), "fixture.bin")
     cpp_shim.write_fixture(fx, keys)
     idf = os.path.join(str(tmp_path), "rccl.id")

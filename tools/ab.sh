@@ -1,6 +1,7 @@
 #!/bin/bash
 # A/B builds of the pair-engine units: tools/ab.sh NAME [extra hipcc flags]  ->  tools/ab/NAME.so (linked against build/mpe_lib.o)
 # Run a variant with MPE_LIB_PATH=tools/ab/NAME.so python bench.py ...   (the .so files travel with gpurun, not with git)
+# The unit list and the flags below are a copy: __graft_entry__.py (HIP_SOURCES, HIPCC_FLAGS, REPORT_FLAGS) owns them - keep the two in step.
 set -e
 cd "$(dirname "$0")/.."
 NAME=$1; shift
