@@ -21,6 +21,7 @@
 #include <cstdio>
 #include <cstdlib>
 
+#include "mpe_gg20_msg.h"
 #include "mpe_proofs.h"
 
 namespace mpe {
@@ -67,20 +68,6 @@ struct mpe_gg20_keys {
 
 namespace mpe {
 namespace gg {
-
-constexpr int SUB0 = 256, SUB1 = 208, W2 = 96, W3 = 24, SUB4 = 450, W5 = 64, W6 = 8;
-inline int msg_words(int S, int n, int round) {
-  switch (round) {
-    case 0: return SUB0 * (n + 1);
-    case 1: return SUB1 * 2 * (S - 1);
-    case 2: return W2;
-    case 3: return W3;
-    case 4: return SUB4 * S;
-    case 5: return W5;
-    case 7: return W6;
-    default: return 0;
-  }
-}
 
 // V: range-proof verifications per MessageB pair (2 faithful / 1 dedup); PV: verifiers of the PDL proofs (L / 1)
 struct Dim {
@@ -195,17 +182,17 @@ __global__ void __launch_bounds__(64) validate_kernel(Dim d, Slab in, int round,
     if (round == 2) {
       for (int v = 0; v < 2; ++v) {
         const uint32_t* mb = m + (size_t)(jme_of(i, j) * 2 + v) * SUB1;
-        good = good && pt_ok(mb + 128) && pt_ok(mb + 144) && pt_ok(mb + 168) && pt_ok(mb + 184);
+        good = good && pt_ok(mb + M1.b_pk.off) && pt_ok(mb + M1.b_R.off) && pt_ok(mb + M1.bt_pk.off) && pt_ok(mb + M1.bt_R.off);
       }
     } else if (round == 3) {
-      good = pt_ok(m + 8) && pt_ok(m + 32) && pt_ok(m + 48) && pt_ok(m + 64);
+      good = pt_ok(m + M2.T.off) && pt_ok(m + M2.a1.off) && pt_ok(m + M2.a2.off) && pt_ok(m + M2.com.off);
     } else if (round == 4) {
-      good = pt_ok(m + 8);
+      good = pt_ok(m + M3.g_gamma.off);
     } else if (round == 5) {
-      for (int jj = 0; jj < P1; ++jj) good = good && pt_ok(m + (size_t)jj * SUB4 + 64);
-      good = good && pt_ok(m + (size_t)P1 * SUB4);
+      for (int jj = 0; jj < P1; ++jj) good = good && pt_ok(m + (size_t)jj * SUB4 + M4P.u1.off);
+      good = good && pt_ok(m + (size_t)P1 * SUB4 + M4R.R_dash.off);
     } else if (round == 6) {
-      good = pt_ok(m) && pt_ok(m + 16) && pt_ok(m + 32);
+      good = pt_ok(m + M5.S.off) && pt_ok(m + M5.T.off) && pt_ok(m + M5.A3.off);
     }
     if (!good) mask |= 1u << j;
   }
@@ -345,15 +332,15 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r2a_kernel(Dim d, const int32_t
   const uint32_t* m = in1 + (size_t)sub1_rv[rv] * SUB1;
   const ec::U256 al = ec::sc_reduce(alpha_full + (size_t)rv * 64, 64);
   ec::u256_store(alpha + (size_t)rv * 8, al);
-  const ec::Aff Bpk = ec::aff_load(m + 128), BTpk = ec::aff_load(m + 168);
+  const ec::Aff Bpk = ec::aff_load(m + M1.b_pk.off), BTpk = ec::aff_load(m + M1.bt_pk.off);
   const ec::Jac g_alpha = ec::jac_mul_gen(al);
   const ec::Jac ba_btag = ec::jac_add_aff(ec::jac_mul(ec::u256_load(kq + (size_t)pi * 8), Bpk), BTpk);
   bool good = ec::jac_eq(g_alpha, ba_btag);
   {  // DLogProof::verify x2
-    const ec::Aff R1 = ec::aff_load(m + 144), R2 = ec::aff_load(m + 184);
+    const ec::Aff R1 = ec::aff_load(m + M1.b_R.off), R2 = ec::aff_load(m + M1.bt_R.off);
     const ec::U256 c1 = dlog_challenge(R1, Bpk, d.enc), c2 = dlog_challenge(R2, BTpk, d.enc);
-    const ec::Jac l1 = ec::jac_add(ec::jac_mul_gen(ec::sc_reduce(m + 160, 8)), ec::jac_mul(c1, Bpk));
-    const ec::Jac l2 = ec::jac_add(ec::jac_mul_gen(ec::sc_reduce(m + 200, 8)), ec::jac_mul(c2, BTpk));
+    const ec::Jac l1 = ec::jac_add(ec::jac_mul_gen(ec::sc_reduce(m + M1.b_z.off, 8)), ec::jac_mul(c1, Bpk));
+    const ec::Jac l2 = ec::jac_add(ec::jac_mul_gen(ec::sc_reduce(m + M1.bt_z.off, 8)), ec::jac_mul(c2, BTpk));
     good = good && ec::jac_eq_aff(l1, R1) && ec::jac_eq_aff(l2, R2);
   }
   r2a_finish(d, rv, v, pp, b, ind, Bpk, good, gw, bpk_in, code);
@@ -420,7 +407,6 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r2b_kernel(Dim d, const uint32_
 }
 
 // ---- Round 3: T_i == proof.com, delta^-1, every PedersenProof (rounds.rs:347-402) -----------------------------------
-// M2 record: delta 0 | T 8 | e 24 | a1 32 | a2 48 | com 64 | z1 80 | z2 88
 __device__ __forceinline__ bool words_eq(const uint32_t* a, const uint32_t* b, int n) {
   uint32_t o = 0;
   for (int i = 0; i < n; ++i) o |= a[i] ^ b[i];
@@ -445,12 +431,12 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r3_kernel(Dim d, Slab in2, uint
   bool com_ok = true, ped_ok = true;
   for (int j = 0; j < d.S; ++j) {
     const uint32_t* m = rec_of(in2, j, b);
-    sum = ec::sc_add(sum, ec::sc_reduce(m, 8));
-    com_ok = com_ok && words_eq(m + 8, m + 64, 16);
-    const ec::Aff C = ec::aff_load(m + 64), a1 = ec::aff_load(m + 32), a2 = ec::aff_load(m + 48);
+    sum = ec::sc_add(sum, ec::sc_reduce(m + M2.delta.off, 8));
+    com_ok = com_ok && words_eq(m + M2.T.off, m + M2.com.off, M2.T.words);
+    const ec::Aff C = ec::aff_load(m + M2.com.off), a1 = ec::aff_load(m + M2.a1.off), a2 = ec::aff_load(m + M2.a2.off);
     const ec::Aff hp[5] = {G, H, C, a1, a2};
     const ec::U256 e = hash_points(hp, d.enc, d.enc.ord_pedersen);
-    const ec::Jac lhs = ec::jac_add(ec::jac_mul_gen(ec::sc_reduce(m + 80, 8)), ec::jac_mul_h2(ec::sc_reduce(m + 88, 8)));
+    const ec::Jac lhs = ec::jac_add(ec::jac_mul_gen(ec::sc_reduce(m + M2.z1.off, 8)), ec::jac_mul_h2(ec::sc_reduce(m + M2.z2.off, 8)));
     const ec::Jac rhs = ec::jac_add_aff(ec::jac_add_aff(ec::jac_mul(e, C), a1), a2);
     ped_ok = ped_ok && ec::jac_eq(lhs, rhs);
   }
@@ -458,7 +444,6 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r3_kernel(Dim d, Slab in2, uint
 }
 
 // ---- Round 4: phase4 -> R, R_dash (party_i.rs:642-687, rounds.rs:452) --------------------------------
-// M3 record: blind 0 | g_gamma 8
 __global__ void __launch_bounds__(64) MPE_EC_OCC r4_kernel(Dim d, Slab in3, const uint32_t* __restrict__ dinv, const uint32_t* __restrict__ com_all,
                           const uint32_t* __restrict__ bpk_in, const uint32_t* __restrict__ kq, uint32_t* __restrict__ R,
                           uint32_t* __restrict__ Rbar, int32_t* __restrict__ status, uint32_t* __restrict__ bad, int with_rbar) {
@@ -470,14 +455,14 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r4_kernel(Dim d, Slab in3, cons
   for (int jj = 0; jj < P1; ++jj) {
     const int ind = ind_of(i, jj);
     const uint32_t* m = rec_of(in3, ind, b);
-    const ec::Aff gg = ec::aff_load(m + 8);
+    const ec::Aff gg = ec::aff_load(m + M3.g_gamma.off);
     bool good = ec::aff_eq(ec::aff_load(bpk_in + ((size_t)pi * P1 + jj) * 16), gg);
-    good = good && ec::u256_eq(commit_point(gg, m, d.enc), ec::u256_load(com_all + ((size_t)ind * d.B + b) * 8));
+    good = good && ec::u256_eq(commit_point(gg, m + M3.blind.off, d.enc), ec::u256_load(com_all + ((size_t)ind * d.B + b) * 8));
     if (!good) mask |= 1u << ind;
   }
   if (mask) fail(status, bad, pi, 401, mask);
   ec::Jac acc = ec::jac_inf();
-  for (int j = 0; j < d.S; ++j) acc = ec::jac_add(acc, ec::jac_from_aff(ec::aff_load(rec_of(in3, j, b) + 8)));
+  for (int j = 0; j < d.S; ++j) acc = ec::jac_add(acc, ec::jac_from_aff(ec::aff_load(rec_of(in3, j, b) + M3.g_gamma.off)));
   const ec::Aff Rp = mul_aff(ec::u256_load(dinv + (size_t)pi * 8), ec::jac_to_aff(acc));
   ec::aff_store(R + (size_t)pi * 16, Rp);
   if (with_rbar) ec::aff_store(Rbar + (size_t)pi * 16, mul_aff(ec::u256_load(kq + (size_t)pi * 8), Rp));
@@ -491,7 +476,6 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r4_rbar_kernel(Dim d, const uin
 }
 
 // ---- Round 5 -------------------------------------------------------------------------------------------------------
-// M4 record: S sub-records of 450: proof for peer slot jj (z 0 | u1 64 | u2 80 | u3 208 | s1 272 | s2 297 | s3 361); the last: R_dash
 __global__ void idx5_kernel(Dim d, Slab in4, int32_t* __restrict__ sub4_pv, int32_t* __restrict__ rdash_pv) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
   const int P1 = d.S - 1;
@@ -514,7 +498,7 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r5_status_kernel(Dim d, Slab in
       if (!pdl_ok[(((size_t)b * d.PV + vo) * d.S + i) * P1 + jj]) mask = 1u << i;
   if (mask) fail(status, bad, pi, 501, mask);
   ec::Jac acc = ec::jac_inf();
-  for (int j = 0; j < d.S; ++j) acc = ec::jac_add(acc, ec::jac_from_aff(ec::aff_load(rec_of(in4, j, b) + (size_t)P1 * SUB4)));
+  for (int j = 0; j < d.S; ++j) acc = ec::jac_add(acc, ec::jac_from_aff(ec::aff_load(rec_of(in4, j, b) + (size_t)P1 * SUB4 + M4R.R_dash.off)));
   if (!ec::jac_eq_aff(acc, ec::aff_gen())) fail(status, bad, pi, 502, 0);                  // phase5_check_R_dash_sum
 }
 // S_i and HomoELGamalProof::prove: independent of the verifications above (small batches run it beside them)
@@ -539,7 +523,6 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r5_prove_kernel(Dim d, const ui
 }
 
 // ---- Round 6: every HomoELGamalProof; sum S_i == y (party_i.rs:801-848) --------------------------------------------
-// M5 record: S_i 0 | T 16 | A3 32 | z1 48 | z2 56
 __global__ void __launch_bounds__(64) MPE_EC_OCC r6_kernel(Dim d, Slab in5, const uint32_t* __restrict__ R, const uint32_t* __restrict__ tvec,
                           const uint32_t* __restrict__ y, int32_t* __restrict__ status, uint32_t* __restrict__ bad) {
   const int pi = blockIdx.x * blockDim.x + threadIdx.x;
@@ -550,10 +533,10 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r6_kernel(Dim d, Slab in5, cons
   ec::Jac acc = ec::jac_inf();
   for (int j = 0; j < d.S; ++j) {
     const uint32_t* m = rec_of(in5, j, b);
-    const ec::Aff E = ec::aff_load(m), TT = ec::aff_load(m + 16), A3 = ec::aff_load(m + 32),
+    const ec::Aff E = ec::aff_load(m + M5.S.off), TT = ec::aff_load(m + M5.T.off), A3 = ec::aff_load(m + M5.A3.off),
                   D = ec::aff_load(tvec + ((size_t)j * d.B + b) * 16);
     const ec::Aff hp[7] = {TT, A3, Rp, H, G, D, E};
-    const ec::U256 e = hash_points(hp, d.enc, d.enc.ord_heg), z1 = ec::sc_reduce(m + 48, 8), z2 = ec::sc_reduce(m + 56, 8);
+    const ec::U256 e = hash_points(hp, d.enc, d.enc.ord_heg), z1 = ec::sc_reduce(m + M5.z1.off, 8), z2 = ec::sc_reduce(m + M5.z2.off, 8);
     const ec::Jac l1 = ec::jac_add(ec::jac_mul_h2(z1), ec::jac_mul_gen(z2));
     const ec::Jac r1 = ec::jac_add_aff(ec::jac_mul(e, D), TT);
     const ec::Jac l2 = ec::jac_mul(z2, Rp);
@@ -587,13 +570,13 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r2a_group_kernel(Dim d, const i
   const int v = rvc & 1, pp = rvc >> 1, jj = pp % P1, pi = pp / P1, i = d.loc[pi % d.L], b = pi / d.L, ind = ind_of(i, jj);
   const uint32_t* m = in1 + (size_t)sub1_rv[rvc] * SUB1;
   const ec::U256 al = ec::sc_reduce(alpha_full + (size_t)rvc * 64, 64);
-  const ec::Aff Bpk = ec::aff_load(m + 128), BTpk = ec::aff_load(m + 168);
-  const ec::Aff R1 = ec::aff_load(m + 144), R2 = ec::aff_load(m + 184);
+  const ec::Aff Bpk = ec::aff_load(m + M1.b_pk.off), BTpk = ec::aff_load(m + M1.bt_pk.off);
+  const ec::Aff R1 = ec::aff_load(m + M1.b_R.off), R2 = ec::aff_load(m + M1.bt_R.off);
   ec::Jac res = ec::jac_inf(), fr = ec::jac_inf();
   if (live && sub < 3) {
     const ec::U256 sc = sub == 0 ? ec::u256_load(kq + (size_t)pi * 8) : (sub == 1 ? dlog_challenge(R1, Bpk, d.enc) : dlog_challenge(R2, BTpk, d.enc));
     res = ec::jac_mul(sc, sub == 2 ? BTpk : Bpk);
-    const ec::U256 fk = sub == 0 ? al : ec::sc_reduce(m + (sub == 1 ? 160 : 200), 8);
+    const ec::U256 fk = sub == 0 ? al : ec::sc_reduce(m + (sub == 1 ? M1.b_z.off : M1.bt_z.off), 8);
     fr = ec::jac_mul_gen(fk);
   }
   vs.v[threadIdx.x] = res;
@@ -619,13 +602,13 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r3_group_kernel(Dim d, int G, S
   ec::Jac res = ec::jac_inf(), fr = ec::jac_inf();
   if (live && sub < d.S) {
     const uint32_t* m = rec_of(in2, sub, b);
-    const ec::Aff C = ec::aff_load(m + 64), a1 = ec::aff_load(m + 32), a2 = ec::aff_load(m + 48);
+    const ec::Aff C = ec::aff_load(m + M2.com.off), a1 = ec::aff_load(m + M2.a1.off), a2 = ec::aff_load(m + M2.a2.off);
     const ec::Aff hp[5] = {Gp, H, C, a1, a2};
     res = ec::jac_mul(hash_points(hp, d.enc, d.enc.ord_pedersen), C);
   }
   if (live && sub < 2 * d.S) {
     const uint32_t* m = rec_of(in2, sub >> 1, b);
-    fr = ec::jac_mul_fixed(ec::sc_reduce(m + ((sub & 1) ? 88 : 80), 8), sub & 1);
+    fr = ec::jac_mul_fixed(ec::sc_reduce(m + ((sub & 1) ? M2.z2.off : M2.z1.off), 8), sub & 1);
   }
   vs.v[threadIdx.x] = res;
   fs.v[threadIdx.x] = fr;
@@ -635,9 +618,9 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r3_group_kernel(Dim d, int G, S
   bool com_ok = true, ped_ok = true;
   for (int j = 0; j < d.S; ++j) {
     const uint32_t* m = rec_of(in2, j, b);
-    sum = ec::sc_add(sum, ec::sc_reduce(m, 8));
-    com_ok = com_ok && words_eq(m + 8, m + 64, 16);
-    const ec::Aff a1 = ec::aff_load(m + 32), a2 = ec::aff_load(m + 48);
+    sum = ec::sc_add(sum, ec::sc_reduce(m + M2.delta.off, 8));
+    com_ok = com_ok && words_eq(m + M2.T.off, m + M2.com.off, M2.T.words);
+    const ec::Aff a1 = ec::aff_load(m + M2.a1.off), a2 = ec::aff_load(m + M2.a2.off);
     const ec::Jac lhs = ec::jac_add(fs.v[base + 2 * j], fs.v[base + 2 * j + 1]);
     const ec::Jac rhs = ec::jac_add_aff(ec::jac_add_aff(vs.v[base + j], a1), a2);
     ped_ok = ped_ok && ec::jac_eq(lhs, rhs);
@@ -657,15 +640,15 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r6_group_kernel(Dim d, int G, S
   if (live && sub < 3 * d.S) {
     const int j = sub / 3, kind = sub % 3;
     const uint32_t* m = rec_of(in5, j, b);
-    const ec::Aff E = ec::aff_load(m), TT = ec::aff_load(m + 16), A3 = ec::aff_load(m + 32),
+    const ec::Aff E = ec::aff_load(m + M5.S.off), TT = ec::aff_load(m + M5.T.off), A3 = ec::aff_load(m + M5.A3.off),
                   D = ec::aff_load(tvec + ((size_t)j * d.B + b) * 16);
     const ec::Aff hp[7] = {TT, A3, Rp, H, Gp, D, E};
     const ec::U256 e = hash_points(hp, d.enc, d.enc.ord_heg);
-    res = ec::jac_mul(kind == 1 ? ec::sc_reduce(m + 56, 8) : e, kind == 0 ? D : (kind == 1 ? Rp : E));
+    res = ec::jac_mul(kind == 1 ? ec::sc_reduce(m + M5.z2.off, 8) : e, kind == 0 ? D : (kind == 1 ? Rp : E));
   }
   if (live && sub < 2 * d.S) {
     const uint32_t* m = rec_of(in5, sub >> 1, b);
-    fr = ec::jac_mul_fixed(ec::sc_reduce(m + ((sub & 1) ? 56 : 48), 8), (sub & 1) ? 0 : 1);
+    fr = ec::jac_mul_fixed(ec::sc_reduce(m + ((sub & 1) ? M5.z2.off : M5.z1.off), 8), (sub & 1) ? 0 : 1);
   }
   vs.v[threadIdx.x] = res;
   fs.v[threadIdx.x] = fr;
@@ -675,7 +658,7 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r6_group_kernel(Dim d, int G, S
   ec::Jac acc = ec::jac_inf();
   for (int j = 0; j < d.S; ++j) {
     const uint32_t* m = rec_of(in5, j, b);
-    const ec::Aff E = ec::aff_load(m), TT = ec::aff_load(m + 16), A3 = ec::aff_load(m + 32);
+    const ec::Aff E = ec::aff_load(m + M5.S.off), TT = ec::aff_load(m + M5.T.off), A3 = ec::aff_load(m + M5.A3.off);
     const ec::Jac l1 = ec::jac_add(fs.v[base + 2 * j], fs.v[base + 2 * j + 1]);
     const ec::Jac r1 = ec::jac_add_aff(vs.v[base + 3 * j], TT);
     const ec::Jac r2 = ec::jac_add_aff(vs.v[base + 3 * j + 2], A3);
@@ -709,7 +692,7 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC complete_kernel(Dim d, Slab in6
   if (pi >= d.B * d.L) return;
   const int li = pi % d.L, i = d.loc[li], b = pi / d.L;
   ec::U256 s = ec::u256_load(s_i + (size_t)pi * 8);
-  for (int j = 0; j < d.S; ++j) if (j != i) s = ec::sc_add(s, ec::sc_reduce(rec_of(in6, j, b), 8));
+  for (int j = 0; j < d.S; ++j) if (j != i) s = ec::sc_add(s, ec::sc_reduce(rec_of(in6, j, b) + M7.s_i.off, 8));
   const ec::U256 m = ec::u256_load(mq + (size_t)pi * 8), r = ec::u256_load(rq + (size_t)pi * 8);
   const ec::U256 ry = ec::sc_reduce(R + (size_t)pi * 16 + 8, 8);
   int recid = (int)(ry.w[0] & 1u);
@@ -821,35 +804,7 @@ static void gg_trace(const mpe_ctx* ctx, hipStream_t st, const char* what, int r
     gg_trace(s->ctx, st, #kernel, rc);                                                                            \
   } while (0)
 
-struct Bump {
-  char* base; size_t off = 0;
-  explicit Bump(char* b) : base(b) {}
-  void* take(size_t bytes) { const size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return base ? base + o : nullptr; }
-  uint32_t* w(size_t words) { return (uint32_t*)take(words * 4); }
-  int32_t* i(size_t count) { return (int32_t*)take(count * 4); }
-  uint8_t* f(size_t count) { return (uint8_t*)take(count); }
-};
-struct Counts { size_t nPI, nAP, nVI, nMB, nPP, nPV, SB; };
-static Counts counts_of(const Dim& d) {
-  const size_t P1 = d.S - 1;
-  Counts c;
-  c.nPI = (size_t)d.B * d.L; c.nAP = c.nPI * d.n; c.nPP = c.nPI * P1; c.nMB = c.nPP * 2; c.nVI = c.nPP * d.V * d.n;
-  c.nPV = (size_t)d.B * d.PV * d.S * P1; c.SB = (size_t)d.S * d.B;
-  return c;
-}
-static size_t tmp_bytes_of(const Counts& c) {
-  const size_t r0 = c.nAP * 250 * 4 + 4096;
-  const size_t r1 = c.nVI * 5 + c.nMB * (8 + 8 + 128 + 16 + 16 + 8 + 16 + 16 + 8) * 4 + 8192;
-  const size_t r2 = c.nMB * (1 + 64 + 8) * 4 + c.nMB + c.nPI * 72 * 4 + 8192;
-  const size_t r4 = c.nPP * 450 * 4 + 4096;
-  const size_t r5 = c.nPV * 9 + c.nPI * 64 * 4 + 8192;
-  size_t m = r0;
-  if (r1 > m) m = r1;
-  if (r2 > m) m = r2;
-  if (r4 > m) m = r4;
-  if (r5 > m) m = r5;
-  return m + 64 * 256;                 // alignment slack of the bump allocator
-}
+static Counts counts_of(const Dim& d) { return counts_of(d.B, d.S, d.n, d.L, d.V, d.PV); }
 // assigns every state array (base == nullptr: only sizes)
 static size_t layout(mpe_gg20_session* s, char* base) {
   const Dim& d = s->d;
@@ -904,9 +859,10 @@ static int round_exit(mpe_gg20_session* s, int rc, const char* what) {
 }
 #define STAT(r) (s->status + (size_t)(r) * c.nPI)
 #define BADR(r) (s->bad + (size_t)(r) * c.nPI)
-#define PACK(nitems, per, nsub, sub0, subw, dst_off, src, words)                                                              \
-  GG_LAUNCH(pack_field_kernel, (size_t)(nitems) * (words), (int)(nitems), (int)(per), d.L, d.B, (int)(nsub), (int)(sub0), (int)(subw),  \
-            (int)(dst_off), (const uint32_t*)(src), (int)(words), s->status, s->next_round, d_out)
+// src [nitems][field.words] -> that field of sub-record sub0 + (item % per) of the outgoing records (nsub sub-records of subw words each)
+#define PACK(nitems, per, nsub, sub0, subw, field, src)                                                                                 \
+  GG_LAUNCH(pack_field_kernel, (size_t)(nitems) * (field).words, (int)(nitems), (int)(per), d.L, d.B, (int)(nsub), (int)(sub0), (int)(subw),   \
+            (field).off, (const uint32_t*)(src), (field).words, s->status, s->next_round, d_out)
 
 // does round 1 run the ladders of its verifications and of its MessageBs in ONE launch (round1_merged_ladders)?  Round 0 asks too:
 // only then is the inversion of the ciphertexts in front of a ladder that everything waits for
@@ -1007,7 +963,8 @@ static int round0(mpe_gg20_session* s, uint32_t* d_out, hipStream_t st) {
     gg_trace(s->ctx, sx, "round 1's inversion, ahead", rc);
   }
   Bump t(s->tmp);
-  mpe_alice_proof ap{t.w(c.nAP * 64), t.w(c.nAP * 8), t.w(c.nAP * 64), t.w(c.nAP * 25), t.w(c.nAP * 89)};
+  const Round0Tmp r0 = Round0Tmp::carve(t, c);
+  mpe_alice_proof ap{r0.z, r0.e, r0.s, r0.s1, r0.s2};
   mpe_alice_nonces an{Z.al_alpha, Z.al_beta, Z.al_gamma, Z.al_rho};
   if (rc == MPE_OK)
     rc = alice_generate(ctx, K->prv, K->stm, (int)c.nAP, s->ix.kown_ap, s->ix.st_ap, rows(s->kq, 8, s->ix.pi_ap),
@@ -1031,9 +988,9 @@ static int round0(mpe_gg20_session* s, uint32_t* d_out, hipStream_t st) {
   }
   if (held) ctx->ws_hold--;
   gg_trace(s->ctx, st, "alice_generate", rc);
-  PACK(c.nAP, n, n + 1, 0, SUB0, 0, ap.z, 64); PACK(c.nAP, n, n + 1, 0, SUB0, 64, ap.e, 8); PACK(c.nAP, n, n + 1, 0, SUB0, 72, ap.s, 64);
-  PACK(c.nAP, n, n + 1, 0, SUB0, 136, ap.s1, 25); PACK(c.nAP, n, n + 1, 0, SUB0, 161, ap.s2, 89);
-  PACK(c.nPI, 1, n + 1, n, SUB0, 0, s->c_a, 128); PACK(c.nPI, 1, n + 1, n, SUB0, 128, s->com, 8);
+  PACK(c.nAP, n, n + 1, 0, SUB0, M0A.z, ap.z); PACK(c.nAP, n, n + 1, 0, SUB0, M0A.e, ap.e); PACK(c.nAP, n, n + 1, 0, SUB0, M0A.s, ap.s);
+  PACK(c.nAP, n, n + 1, 0, SUB0, M0A.s1, ap.s1); PACK(c.nAP, n, n + 1, 0, SUB0, M0A.s2, ap.s2);
+  PACK(c.nPI, 1, n + 1, n, SUB0, M0L.c, s->c_a); PACK(c.nPI, 1, n + 1, n, SUB0, M0L.com, s->com);
   return round_exit(s, rc, "gg20 round0");
 }
 
@@ -1097,13 +1054,14 @@ static int round1(mpe_gg20_session* s, const uint32_t* d_in, const int64_t* h_of
   const Slab in0 = slab_of(s, d_in, h_off, 0);
   (void)hipMemsetAsync(d_out, 0, c.nPI * (size_t)msg_words(d.S, n, 1) * 4, st);
   // m_a_vec[..].c and bc_vec of every party (into_vec_including_me)
-  GG_LAUNCH(gather_field_kernel, c.SB * 128, in0, d.S, d.B, n * SUB0, 128, s->ca_all);
-  GG_LAUNCH(gather_field_kernel, c.SB * 8, in0, d.S, d.B, n * SUB0 + 128, 8, s->com_all);
+  GG_LAUNCH(gather_field_kernel, c.SB * M0L.c.words, in0, d.S, d.B, n * SUB0 + M0L.c.off, M0L.c.words, s->ca_all);
+  GG_LAUNCH(gather_field_kernel, c.SB * M0L.com.words, in0, d.S, d.B, n * SUB0 + M0L.com.off, M0L.com.words, s->com_all);
   Bump t(s->tmp);
   int32_t* sub0_vi = s->sub0_vi;
   uint8_t* ok_vi = s->ok_vi;
-  uint32_t *bsel = t.w(c.nMB * 8), *btq = t.w(c.nMB * 8), *c_b = t.w(c.nMB * 128);
-  uint32_t *Bpk = t.w(c.nMB * 16), *BR = t.w(c.nMB * 16), *Bz = t.w(c.nMB * 8), *BTpk = t.w(c.nMB * 16), *BTR = t.w(c.nMB * 16), *BTz = t.w(c.nMB * 8);
+  const Round1Tmp r1 = Round1Tmp::carve(t, c);
+  uint32_t *bsel = r1.bsel, *btq = r1.btq, *c_b = r1.c_b;
+  uint32_t *Bpk = r1.Bpk, *BR = r1.BR, *Bz = r1.Bz, *BTpk = r1.BTpk, *BTR = r1.BTR, *BTz = r1.BTz;
   GG_LAUNCH(idx1_kernel, c.nVI, d, in0, sub0_vi);
   // small batches: the verification of the peers' range proofs and the construction of my MessageBs are independent
   // (the reference runs them back to back inside MessageB::b) — two streams, one workspace reservation
@@ -1121,8 +1079,8 @@ static int round1(mpe_gg20_session* s, const uint32_t* d_in, const int64_t* h_of
   bool held = par && !merged && rc == MPE_OK;
   const uint32_t *m_vi = nullptr, *x_mb = nullptr;
   const uint8_t* inv_ok_vi = nullptr;
-  AliceProofRows pr{rows(d_in, SUB0, sub0_vi), rows(d_in + 64, SUB0, sub0_vi), rows(d_in + 72, SUB0, sub0_vi),
-                    rows(d_in + 136, SUB0, sub0_vi), rows(d_in + 161, SUB0, sub0_vi)};
+  AliceProofRows pr{rows(d_in + M0A.z.off, SUB0, sub0_vi), rows(d_in + M0A.e.off, SUB0, sub0_vi), rows(d_in + M0A.s.off, SUB0, sub0_vi),
+                    rows(d_in + M0A.s1.off, SUB0, sub0_vi), rows(d_in + M0A.s2.off, SUB0, sub0_vi)};
   if (merged && rc == MPE_OK) {
     rc = ws_reserve(ctx, ws_need_alice_verify((int)c.nVI) + ws_need_mul_add_enc((int)c.nMB) + ws_need_round1_merged(K->pub, c.nVI, c.nMB), st);
     if (rc == MPE_OK) { ctx->ws_hold++; held = true; }
@@ -1171,9 +1129,9 @@ static int round1(mpe_gg20_session* s, const uint32_t* d_in, const int64_t* h_of
   if (held) ctx->ws_hold--;
   GG_LAUNCH(status1_kernel, c.nPI, d, ok_vi, STAT(1), BADR(1));
   const int per = 2 * P1;
-  PACK(c.nMB, per, per, 0, SUB1, 0, c_b, 128); PACK(c.nMB, per, per, 0, SUB1, 128, Bpk, 16); PACK(c.nMB, per, per, 0, SUB1, 144, BR, 16);
-  PACK(c.nMB, per, per, 0, SUB1, 160, Bz, 8); PACK(c.nMB, per, per, 0, SUB1, 168, BTpk, 16); PACK(c.nMB, per, per, 0, SUB1, 184, BTR, 16);
-  PACK(c.nMB, per, per, 0, SUB1, 200, BTz, 8);
+  PACK(c.nMB, per, per, 0, SUB1, M1.c, c_b); PACK(c.nMB, per, per, 0, SUB1, M1.b_pk, Bpk); PACK(c.nMB, per, per, 0, SUB1, M1.b_R, BR);
+  PACK(c.nMB, per, per, 0, SUB1, M1.b_z, Bz); PACK(c.nMB, per, per, 0, SUB1, M1.bt_pk, BTpk); PACK(c.nMB, per, per, 0, SUB1, M1.bt_R, BTR);
+  PACK(c.nMB, per, per, 0, SUB1, M1.bt_z, BTz);
   return round_exit(s, rc, "gg20 round1");
 }
 
@@ -1186,10 +1144,11 @@ static int round2(mpe_gg20_session* s, const uint32_t* d_in, const int64_t* h_of
   (void)hipMemsetAsync(d_out, 0, c.nPI * (size_t)W2 * 4, st);
   GG_LAUNCH(validate_kernel, c.nPI, d, in1, 2, STAT(2), BADR(2));
   Bump t(s->tmp);
-  int32_t* sub1_rv = t.i(c.nMB);
-  uint32_t *alpha_full = t.w(c.nMB * 64), *alpha = t.w(c.nMB * 8);
-  uint8_t* code = t.f(c.nMB);
-  Ped ped{s->pedT, t.w(c.nPI * 8), t.w(c.nPI * 16), t.w(c.nPI * 16), t.w(c.nPI * 8), t.w(c.nPI * 8)};
+  const Round2Tmp r2 = Round2Tmp::carve(t, c);
+  int32_t* sub1_rv = r2.sub1_rv;
+  uint32_t *alpha_full = r2.alpha_full, *alpha = r2.alpha;
+  uint8_t* code = r2.code;
+  Ped ped{s->pedT, r2.e, r2.a1, r2.a2, r2.z1, r2.z2};
   GG_LAUNCH(idx2_kernel, c.nMB, d, in1, sub1_rv);
   const bool pdl_ahead = rc == MPE_OK && s->lockstep && s->pdl_bn && ctx->use_prio && !ctx->no_pdl_ahead && ctx->use_pair && ctx->use_crt &&
                          ctx->use_pown && ctx->allow_par && (int)c.nPP <= ctx->par_items && c.nPP > 0 && ensure_aux(ctx);
@@ -1198,7 +1157,7 @@ static int round2(mpe_gg20_session* s, const uint32_t* d_in, const int64_t* h_of
     (void)hipStreamWaitEvent(ctx->aux[1], ctx->ev_fork[0], 0);
   }
   if (rc == MPE_OK)      // Paillier::decrypt of the incoming c_b with my key (mta/mod.rs:165), in place
-    rc = paillier_decrypt(ctx, K->prv, (int)c.nMB, s->ix.kown_mb, rows(d_in, SUB1, sub1_rv), alpha_full, st);
+    rc = paillier_decrypt(ctx, K->prv, (int)c.nMB, s->ix.kown_mb, rows(d_in + M1.c.off, SUB1, sub1_rv), alpha_full, st);
   gg_trace(s->ctx, st, "decrypt", rc);
   // (round 6) lock-step signing of a small batch: the two dependent 1024-bit ladders behind beta^N mod N^2 of round 4's PDL proofs
   // (10 ms at 1 024 sessions, on that round's critical path) need nothing but the prover's nonce and key.  They start HERE on an auxiliary
@@ -1222,9 +1181,9 @@ static int round2(mpe_gg20_session* s, const uint32_t* d_in, const int64_t* h_of
   else GG_LAUNCH(r2a_kernel, c.nMB, d, sub1_rv, d_in, alpha_full, s->kq, K->gw, alpha, s->bpk_in, code);
   GG_LAUNCH(r2b_kernel, c.nPI, d, s->kq, s->gq, s->w, alpha, s->beta, code, Z.l, Z.ped_s1, Z.ped_s2, s->delta_i, s->sigma_i, s->lq, ped,
             STAT(2), BADR(2), alpha_full, s->miu, s->fault_step, s->fault_mask, s->ped_pre);
-  PACK(c.nPI, 1, 1, 0, W2, 0, s->delta_i, 8); PACK(c.nPI, 1, 1, 0, W2, 8, ped.T, 16); PACK(c.nPI, 1, 1, 0, W2, 24, ped.e, 8);
-  PACK(c.nPI, 1, 1, 0, W2, 32, ped.a1, 16); PACK(c.nPI, 1, 1, 0, W2, 48, ped.a2, 16); PACK(c.nPI, 1, 1, 0, W2, 64, ped.T, 16);
-  PACK(c.nPI, 1, 1, 0, W2, 80, ped.z1, 8); PACK(c.nPI, 1, 1, 0, W2, 88, ped.z2, 8);
+  PACK(c.nPI, 1, 1, 0, W2, M2.delta, s->delta_i); PACK(c.nPI, 1, 1, 0, W2, M2.T, ped.T); PACK(c.nPI, 1, 1, 0, W2, M2.e, ped.e);
+  PACK(c.nPI, 1, 1, 0, W2, M2.a1, ped.a1); PACK(c.nPI, 1, 1, 0, W2, M2.a2, ped.a2); PACK(c.nPI, 1, 1, 0, W2, M2.com, ped.T);
+  PACK(c.nPI, 1, 1, 0, W2, M2.z1, ped.z1); PACK(c.nPI, 1, 1, 0, W2, M2.z2, ped.z2);
   return round_exit(s, rc, "gg20 round2");
 }
 
@@ -1236,12 +1195,12 @@ static int round3(mpe_gg20_session* s, const uint32_t* d_in, const int64_t* h_of
   const Slab in2 = slab_of(s, d_in, h_off, 2);
   (void)hipMemsetAsync(d_out, 0, c.nPI * (size_t)W3 * 4, st);
   GG_LAUNCH(validate_kernel, c.nPI, d, in2, 3, STAT(3), BADR(3));
-  GG_LAUNCH(gather_field_kernel, c.SB * 16, in2, d.S, d.B, 8, 16, s->tvec);                  // t_vec
+  GG_LAUNCH(gather_field_kernel, c.SB * M2.T.words, in2, d.S, d.B, M2.T.off, M2.T.words, s->tvec);                 // t_vec
   const size_t lanes_fit = ctx->ec_lane_groups ? (size_t)ctx->cus * 4 * 64 * 2 / ctx->device_share : 0;
   const int g3 = 2 * d.S <= 4 ? 4 : (2 * d.S <= 8 ? 8 : 16);
   if (c.nPI * g3 <= lanes_fit) GG_LAUNCH(r3_group_kernel, c.nPI * g3, d, g3, in2, s->dinv, STAT(3), BADR(3));
   else GG_LAUNCH(r3_kernel, c.nPI, d, in2, s->dinv, STAT(3), BADR(3));
-  PACK(c.nPI, 1, 1, 0, W3, 0, s->Z.blind, 8); PACK(c.nPI, 1, 1, 0, W3, 8, s->g_gamma, 16);          // SignDecommitPhase1
+  PACK(c.nPI, 1, 1, 0, W3, M3.blind, s->Z.blind); PACK(c.nPI, 1, 1, 0, W3, M3.g_gamma, s->g_gamma);          // SignDecommitPhase1
   return round_exit(s, rc, "gg20 round3");
 }
 
@@ -1266,7 +1225,8 @@ static int round4(mpe_gg20_session* s, const uint32_t* d_in, const int64_t* h_of
     }
   }
   Bump t(s->tmp);
-  mpe_pdl_proof pp{t.w(c.nPP * 64), t.w(c.nPP * 16), t.w(c.nPP * 128), t.w(c.nPP * 64), t.w(c.nPP * 25), t.w(c.nPP * 64), t.w(c.nPP * 89)};
+  const Round4Tmp r4 = Round4Tmp::carve(t, c);
+  mpe_pdl_proof pp{r4.z, r4.u1, r4.u2, r4.u3, r4.s1, r4.s2, r4.s3};
   mpe_pdl_nonces pn{Z.pdl_alpha, Z.pdl_beta, Z.pdl_rho, Z.pdl_gamma};
   if (rc == MPE_OK)                                                                                            // phase5_proof_pdl
     rc = pdl_prove(ctx, K->prv, K->stm, (int)c.nPP, s->ix.kown_pp, s->ix.st_pp, rows(s->c_a, 128, s->ix.pi_pp), rows(s->Rbar, 16, s->ix.pi_pp),
@@ -1275,10 +1235,10 @@ static int round4(mpe_gg20_session* s, const uint32_t* d_in, const int64_t* h_of
   else g.join();
   if (rc == MPE_OK) s->pdl_ahead = false;                    // consumed (otherwise session_release waits for it)
   gg_trace(s->ctx, st, "pdl_prove", rc);
-  PACK(c.nPP, P1, S, 0, SUB4, 0, pp.z, 64); PACK(c.nPP, P1, S, 0, SUB4, 64, pp.u1, 16); PACK(c.nPP, P1, S, 0, SUB4, 80, pp.u2, 128);
-  PACK(c.nPP, P1, S, 0, SUB4, 208, pp.u3, 64); PACK(c.nPP, P1, S, 0, SUB4, 272, pp.s1, 25); PACK(c.nPP, P1, S, 0, SUB4, 297, pp.s2, 64);
-  PACK(c.nPP, P1, S, 0, SUB4, 361, pp.s3, 89);
-  PACK(c.nPI, 1, S, P1, SUB4, 0, s->Rbar, 16);
+  PACK(c.nPP, P1, S, 0, SUB4, M4P.z, pp.z); PACK(c.nPP, P1, S, 0, SUB4, M4P.u1, pp.u1); PACK(c.nPP, P1, S, 0, SUB4, M4P.u2, pp.u2);
+  PACK(c.nPP, P1, S, 0, SUB4, M4P.u3, pp.u3); PACK(c.nPP, P1, S, 0, SUB4, M4P.s1, pp.s1); PACK(c.nPP, P1, S, 0, SUB4, M4P.s2, pp.s2);
+  PACK(c.nPP, P1, S, 0, SUB4, M4P.s3, pp.s3);
+  PACK(c.nPI, 1, S, P1, SUB4, M4R.R_dash, s->Rbar);
   return round_exit(s, rc, "gg20 round4");
 }
 
@@ -1293,22 +1253,24 @@ static int round5(mpe_gg20_session* s, const uint32_t* d_in, const int64_t* h_of
   Bump t(s->tmp);
   int32_t *sub4_pv = s->sub4_pv, *rdash_pv = s->rdash_pv;
   uint8_t* ok_pv = s->ok_pv;
-  Heg heg{t.w(c.nPI * 16), t.w(c.nPI * 16), t.w(c.nPI * 16), t.w(c.nPI * 8), t.w(c.nPI * 8)};
+  const Round5Tmp r5 = Round5Tmp::carve(t, c);
+  Heg heg{r5.S, r5.T, r5.A3, r5.z1, r5.z2};
   GG_LAUNCH(idx5_kernel, c.nPV, d, in4, sub4_pv, rdash_pv);
   const bool par = ctx->allow_par && (int)c.nPV <= ctx->par_items;
-  PdlProofRows pr{rows(d_in, SUB4, sub4_pv), rows(d_in + 64, SUB4, sub4_pv), rows(d_in + 80, SUB4, sub4_pv), rows(d_in + 208, SUB4, sub4_pv),
-                  rows(d_in + 272, SUB4, sub4_pv), rows(d_in + 297, SUB4, sub4_pv), rows(d_in + 361, SUB4, sub4_pv)};
+  PdlProofRows pr{rows(d_in + M4P.z.off, SUB4, sub4_pv), rows(d_in + M4P.u1.off, SUB4, sub4_pv), rows(d_in + M4P.u2.off, SUB4, sub4_pv),
+                  rows(d_in + M4P.u3.off, SUB4, sub4_pv), rows(d_in + M4P.s1.off, SUB4, sub4_pv), rows(d_in + M4P.s2.off, SUB4, sub4_pv),
+                  rows(d_in + M4P.s3.off, SUB4, sub4_pv)};
   Fork g(ctx, st, 2, par, 2);
   if (rc == MPE_OK && c.nPI > 0)
     hipLaunchKernelGGL(r5_prove_kernel, dim3(blocks_for((int)c.nPI, 64)), dim3(64), 0, g.s(1), d, s->R, s->sigma_i, s->lq, s->pedT, Z.heg_s1, Z.heg_s2, heg);
   if (rc == MPE_OK)      // phase5_verify_pdl for every prover (mine included), G = the VERIFIER's R (rounds.rs:546-558)
-    rc = pdl_verify(ctx, K->pub, K->stm, (int)c.nPV, s->ix.kpub_pv, s->ix.st_pv, rows(s->ca_all, 128, s->ix.ca_pv), rows(d_in, SUB4, rdash_pv),
+    rc = pdl_verify(ctx, K->pub, K->stm, (int)c.nPV, s->ix.kpub_pv, s->ix.st_pv, rows(s->ca_all, 128, s->ix.ca_pv), rows(d_in + M4R.R_dash.off, SUB4, rdash_pv),
                     rows(s->R, 16, s->ix.pi_pv), pr, ok_pv, st);
   gg_trace(s->ctx, st, "pdl_verify", rc);
   g.join();
   GG_LAUNCH(r5_status_kernel, c.nPI, d, in4, ok_pv, STAT(5), BADR(5));
-  PACK(c.nPI, 1, 1, 0, W5, 0, heg.S, 16); PACK(c.nPI, 1, 1, 0, W5, 16, heg.T, 16); PACK(c.nPI, 1, 1, 0, W5, 32, heg.A3, 16);
-  PACK(c.nPI, 1, 1, 0, W5, 48, heg.z1, 8); PACK(c.nPI, 1, 1, 0, W5, 56, heg.z2, 8);
+  PACK(c.nPI, 1, 1, 0, W5, M5.S, heg.S); PACK(c.nPI, 1, 1, 0, W5, M5.T, heg.T); PACK(c.nPI, 1, 1, 0, W5, M5.A3, heg.A3);
+  PACK(c.nPI, 1, 1, 0, W5, M5.z1, heg.z1); PACK(c.nPI, 1, 1, 0, W5, M5.z2, heg.z2);
   return round_exit(s, rc, "gg20 round5");
 }
 
@@ -1332,7 +1294,7 @@ static int round7(mpe_gg20_session* s, const uint32_t* d_msg, uint32_t* d_out, h
   if (rc != MPE_OK) return rc;
   const Dim& d = s->d; const Counts c = counts_of(d);
   GG_LAUNCH(r7_kernel, c.nPI, d, d_msg, s->R, s->kq, s->sigma_i, s->mq, s->rq, s->s_i, s->fault_step, s->fault_mask);
-  PACK(c.nPI, 1, 1, 0, W6, 0, s->s_i, 8);
+  PACK(c.nPI, 1, 1, 0, W6, M7.s_i, s->s_i);
   return round_exit(s, rc, "gg20 round7");
 }
 // ---- SignManual::complete (sign.rs:625-646) ---------------------------------------------------------------------------------

@@ -157,29 +157,76 @@ def _put_pt(rec, off, pt):
     _put(rec, off + 8, 8, pt[1])
 
 
-ALICE = (("z", 0, 64), ("e", 64, 8), ("s", 72, 64), ("s1", 136, 25), ("s2", 161, 89))
-PDL = (("z", 0, 64), ("u2", 80, 128), ("u3", 208, 64), ("s1", 272, 25), ("s2", 297, 64), ("s3", 361, 89))
+# ---- the record layouts (include/mpecdsa_hip.h "GG20 round messages") ----------------------------------------------------
+# Every field of every record as (name, offset, words) under the names of csrc/mpe_gg20_msg.h, which states the same table
+# for the round engine (tests/test_gg20_layout_cpu.py compares the two).  M0A / M0L: the Alice and the last sub-record of
+# round 0; M1: one MessageB sub-record; M4P / M4R: a PDL and the R_dash sub-record of round 4.
+RECORDS = {
+    "M0A": (("z", 0, 64), ("e", 64, 8), ("s", 72, 64), ("s1", 136, 25), ("s2", 161, 89)),
+    "M0L": (("c", 0, 128), ("com", 128, 8)),
+    "M1": (("c", 0, 128), ("b_pk", 128, 16), ("b_R", 144, 16), ("b_z", 160, 8), ("bt_pk", 168, 16), ("bt_R", 184, 16), ("bt_z", 200, 8)),
+    "M2": (("delta", 0, 8), ("T", 8, 16), ("e", 24, 8), ("a1", 32, 16), ("a2", 48, 16), ("com", 64, 16), ("z1", 80, 8), ("z2", 88, 8)),
+    "M3": (("blind", 0, 8), ("g_gamma", 8, 16)),
+    "M4P": (("z", 0, 64), ("u1", 64, 16), ("u2", 80, 128), ("u3", 208, 64), ("s1", 272, 25), ("s2", 297, 64), ("s3", 361, 89)),
+    "M4R": (("R_dash", 0, 16),),
+    "M5": (("S", 0, 16), ("T", 16, 16), ("A3", 32, 16), ("z1", 48, 8), ("z2", 56, 8)),
+    "M7": (("s_i", 0, 8),),
+}
+WIDTHS = dict(SUB0=256, SUB1=208, W2=96, W3=24, SUB4=450, W5=64, W6=8)          # record and sub-record widths
+SUB0, SUB1, SUB4 = WIDTHS["SUB0"], WIDTHS["SUB1"], WIDTHS["SUB4"]
 
 
-def _dlog_to_json(w, off, style=DEFAULT_STYLE):
-    return {"pk": point_to_json(_pt(w[off:off + 16]), style), "pk_t_rand_commitment": point_to_json(_pt(w[off + 16:off + 32]), style),
-            "challenge_response": scalar_to_json(_int(w[off + 32:off + 40]), style)}
+def msg_words(S, n, rnd):
+    """words of one sender's record of round `rnd` (what mpe_gg20_msg_words returns for the rounds that emit a message)"""
+    return {0: SUB0 * (n + 1), 1: SUB1 * 2 * (S - 1), 2: WIDTHS["W2"], 3: WIDTHS["W3"], 4: SUB4 * S, 5: WIDTHS["W5"], 7: WIDTHS["W6"]}[rnd]
 
 
-def _dlog_from_json(rec, off, j):
-    _put_pt(rec, off, point_from_json(j["pk"]))
-    _put_pt(rec, off + 16, point_from_json(j["pk_t_rand_commitment"]))
-    _put(rec, off + 32, 8, scalar_from_json(j["challenge_response"]))
+def field(record, name, base=0):
+    """the slice a field takes in a record (or in a slab row whose record starts at `base`)"""
+    off, words = next((o, k) for f, o, k in RECORDS[record] if f == name)
+    return slice(base + off, base + off + words)
+
+
+def _get(w, record, name, base=0):
+    return _int(w[field(record, name, base)])
+
+
+def _get_pt(w, record, name, base=0):
+    return _pt(w[field(record, name, base)])
+
+
+def _set(rec, record, name, value, base=0):
+    sl = field(record, name, base)
+    _put(rec, sl.start, sl.stop - sl.start, value)
+
+
+def _set_pt(rec, record, name, pt, base=0):
+    _put_pt(rec, field(record, name, base).start, pt)
+
+
+ALICE = RECORDS["M0A"]
+PDL = tuple(f for f in RECORDS["M4P"] if f[0] != "u1")          # the big-integer fields; u1 is a point
+
+
+def _dlog_to_json(w, which, style=DEFAULT_STYLE):
+    return {"pk": point_to_json(_get_pt(w, "M1", which + "_pk"), style), "pk_t_rand_commitment": point_to_json(_get_pt(w, "M1", which + "_R"), style),
+            "challenge_response": scalar_to_json(_get(w, "M1", which + "_z"), style)}
+
+
+def _dlog_from_json(rec, base, which, j):
+    _set_pt(rec, "M1", which + "_pk", point_from_json(j["pk"]), base)
+    _set_pt(rec, "M1", which + "_R", point_from_json(j["pk_t_rand_commitment"]), base)
+    _set(rec, "M1", which + "_z", scalar_from_json(j["challenge_response"]), base)
 
 
 def _msgb_to_json(w, style=DEFAULT_STYLE):
-    return {"c": bigint_to_json(_int(w[0:128]), style), "b_proof": _dlog_to_json(w, 128, style), "beta_tag_proof": _dlog_to_json(w, 168, style)}
+    return {"c": bigint_to_json(_get(w, "M1", "c"), style), "b_proof": _dlog_to_json(w, "b", style), "beta_tag_proof": _dlog_to_json(w, "bt", style)}
 
 
-def _msgb_from_json(rec, off, j):
-    _put(rec, off, 128, bigint_from_json(j["c"]))
-    _dlog_from_json(rec, off + 128, j["b_proof"])
-    _dlog_from_json(rec, off + 168, j["beta_tag_proof"])
+def _msgb_from_json(rec, base, j):
+    _set(rec, "M1", "c", bigint_from_json(j["c"]), base)
+    _dlog_from_json(rec, base, "b", j["b_proof"])
+    _dlog_from_json(rec, base, "bt", j["beta_tag_proof"])
 
 
 def record_to_bodies(rnd, rec, S, n, sender, style=DEFAULT_STYLE):
@@ -187,37 +234,36 @@ def record_to_bodies(rnd, rec, S, n, sender, style=DEFAULT_STYLE):
     `OfflineProtocolMessage` (rounds 0..5) / `PartialSignature` (round 7).  sender, receiver: signer ordinals + 1 (the
     reference numbers parties from 1)."""
     w = np.ascontiguousarray(rec, dtype=np.uint32)
+    big = lambda record, name, base=0: bigint_to_json(_get(w, record, name, base), style)
+    sc = lambda record, name: scalar_to_json(_get(w, record, name), style)
+    pt = lambda record, name, base=0: point_to_json(_get_pt(w, record, name, base), style)
     if rnd == 0:
-        proofs = [{f: bigint_to_json(_int(w[st * 256 + o:st * 256 + o + k]), style) for f, o, k in ALICE} for st in range(n)]
-        c = w[n * 256:]
-        return [(None, {"M1": [{"c": bigint_to_json(_int(c[0:128]), style), "range_proofs": proofs}, {"com": bigint_to_json(_int(c[128:136]), style)}]})]
+        proofs = [{f: big("M0A", f, st * SUB0) for f, _, _ in ALICE} for st in range(n)]
+        return [(None, {"M1": [{"c": big("M0L", "c", n * SUB0), "range_proofs": proofs}, {"com": big("M0L", "com", n * SUB0)}]})]
     if rnd == 1:
         out = []
         for jj in range(S - 1):
             ind = jj if jj < sender - 1 else jj + 1
-            g, wi = w[(jj * 2) * 208:(jj * 2 + 1) * 208], w[(jj * 2 + 1) * 208:(jj * 2 + 2) * 208]
+            g, wi = w[(jj * 2) * SUB1:(jj * 2 + 1) * SUB1], w[(jj * 2 + 1) * SUB1:(jj * 2 + 2) * SUB1]
             out.append((ind + 1, {"M2": [_msgb_to_json(g, style), _msgb_to_json(wi, style)]}))
         return out
     if rnd == 2:
-        proof = {"e": scalar_to_json(_int(w[24:32]), style), "a1": point_to_json(_pt(w[32:48]), style), "a2": point_to_json(_pt(w[48:64]), style),
-                 "com": point_to_json(_pt(w[64:80]), style), "z1": scalar_to_json(_int(w[80:88]), style), "z2": scalar_to_json(_int(w[88:96]), style)}
-        return [(None, {"M3": [scalar_to_json(_int(w[0:8]), style), point_to_json(_pt(w[8:24]), style), proof]})]
+        proof = {"e": sc("M2", "e"), "a1": pt("M2", "a1"), "a2": pt("M2", "a2"), "com": pt("M2", "com"), "z1": sc("M2", "z1"), "z2": sc("M2", "z2")}
+        return [(None, {"M3": [sc("M2", "delta"), pt("M2", "T"), proof]})]
     if rnd == 3:
-        return [(None, {"M4": {"blind_factor": bigint_to_json(_int(w[0:8]), style), "g_gamma_i": point_to_json(_pt(w[8:24]), style)}})]
+        return [(None, {"M4": {"blind_factor": big("M3", "blind"), "g_gamma_i": pt("M3", "g_gamma")}})]
     if rnd == 4:
         proofs = []
         for jj in range(S - 1):
-            p = w[jj * 450:(jj + 1) * 450]
-            d = {f: bigint_to_json(_int(p[o:o + k]), style) for f, o, k in PDL}
-            d["u1"] = point_to_json(_pt(p[64:80]), style)
+            d = {f: big("M4P", f, jj * SUB4) for f, _, _ in PDL}
+            d["u1"] = pt("M4P", "u1", jj * SUB4)
             proofs.append({f: d[f] for f in ("z", "u1", "u2", "u3", "s1", "s2", "s3")})
-        return [(None, {"M5": [point_to_json(_pt(w[(S - 1) * 450:(S - 1) * 450 + 16]), style), proofs]})]
+        return [(None, {"M5": [pt("M4R", "R_dash", (S - 1) * SUB4), proofs]})]
     if rnd == 5:
-        proof = {"T": point_to_json(_pt(w[16:32]), style), "A3": point_to_json(_pt(w[32:48]), style), "z1": scalar_to_json(_int(w[48:56]), style),
-                 "z2": scalar_to_json(_int(w[56:64]), style)}
-        return [(None, {"M6": [point_to_json(_pt(w[0:16]), style), proof]})]
+        proof = {"T": pt("M5", "T"), "A3": pt("M5", "A3"), "z1": sc("M5", "z1"), "z2": sc("M5", "z2")}
+        return [(None, {"M6": [pt("M5", "S"), proof]})]
     if rnd == 7:
-        return [(None, scalar_to_json(_int(w[0:8]), style))]
+        return [(None, sc("M7", "s_i"))]
     raise ValueError(rnd)
 
 
@@ -228,43 +274,42 @@ def record_to_msgs(rnd, rec, S, n, sender, style=DEFAULT_STYLE):
 
 def bodies_to_record(rnd, bodies, S, n, sender):
     """inverse of record_to_bodies: the messages one sender emitted in round `rnd` -> its record (uint32 words)"""
-    W = {0: 256 * (n + 1), 1: 208 * 2 * (S - 1), 2: 96, 3: 24, 4: 450 * S, 5: 64, 7: 8}[rnd]
-    rec = np.zeros(W, dtype=np.uint32)
+    rec = np.zeros(msg_words(S, n, rnd), dtype=np.uint32)
     if rnd == 0:
         ma, bc = bodies[0][1]["M1"]
         for st, pr in enumerate(ma["range_proofs"]):
-            for f, o, k in ALICE:
-                _put(rec, st * 256 + o, k, bigint_from_json(pr[f]))
-        _put(rec, n * 256, 128, bigint_from_json(ma["c"]))
-        _put(rec, n * 256 + 128, 8, bigint_from_json(bc["com"]))
+            for f, _, _ in ALICE:
+                _set(rec, "M0A", f, bigint_from_json(pr[f]), st * SUB0)
+        _set(rec, "M0L", "c", bigint_from_json(ma["c"]), n * SUB0)
+        _set(rec, "M0L", "com", bigint_from_json(bc["com"]), n * SUB0)
     elif rnd == 1:
         for receiver, body in bodies:
             ind = receiver - 1
             jj = ind if ind < sender - 1 else ind - 1
             g, wi = body["M2"]
-            _msgb_from_json(rec, (jj * 2) * 208, g)
-            _msgb_from_json(rec, (jj * 2 + 1) * 208, wi)
+            _msgb_from_json(rec, (jj * 2) * SUB1, g)
+            _msgb_from_json(rec, (jj * 2 + 1) * SUB1, wi)
     elif rnd == 2:
         delta, T, pr = bodies[0][1]["M3"]
-        _put(rec, 0, 8, scalar_from_json(delta)); _put_pt(rec, 8, point_from_json(T))
-        _put(rec, 24, 8, scalar_from_json(pr["e"])); _put_pt(rec, 32, point_from_json(pr["a1"])); _put_pt(rec, 48, point_from_json(pr["a2"]))
-        _put_pt(rec, 64, point_from_json(pr["com"])); _put(rec, 80, 8, scalar_from_json(pr["z1"])); _put(rec, 88, 8, scalar_from_json(pr["z2"]))
+        _set(rec, "M2", "delta", scalar_from_json(delta)); _set_pt(rec, "M2", "T", point_from_json(T))
+        _set(rec, "M2", "e", scalar_from_json(pr["e"])); _set_pt(rec, "M2", "a1", point_from_json(pr["a1"])); _set_pt(rec, "M2", "a2", point_from_json(pr["a2"]))
+        _set_pt(rec, "M2", "com", point_from_json(pr["com"])); _set(rec, "M2", "z1", scalar_from_json(pr["z1"])); _set(rec, "M2", "z2", scalar_from_json(pr["z2"]))
     elif rnd == 3:
         d = bodies[0][1]["M4"]
-        _put(rec, 0, 8, bigint_from_json(d["blind_factor"])); _put_pt(rec, 8, point_from_json(d["g_gamma_i"]))
+        _set(rec, "M3", "blind", bigint_from_json(d["blind_factor"])); _set_pt(rec, "M3", "g_gamma", point_from_json(d["g_gamma_i"]))
     elif rnd == 4:
         rdash, proofs = bodies[0][1]["M5"]
         for jj, pr in enumerate(proofs):
-            for f, o, k in PDL:
-                _put(rec, jj * 450 + o, k, bigint_from_json(pr[f]))
-            _put_pt(rec, jj * 450 + 64, point_from_json(pr["u1"]))
-        _put_pt(rec, (S - 1) * 450, point_from_json(rdash))
+            for f, _, _ in PDL:
+                _set(rec, "M4P", f, bigint_from_json(pr[f]), jj * SUB4)
+            _set_pt(rec, "M4P", "u1", point_from_json(pr["u1"]), jj * SUB4)
+        _set_pt(rec, "M4R", "R_dash", point_from_json(rdash), (S - 1) * SUB4)
     elif rnd == 5:
         Si, pr = bodies[0][1]["M6"]
-        _put_pt(rec, 0, point_from_json(Si)); _put_pt(rec, 16, point_from_json(pr["T"])); _put_pt(rec, 32, point_from_json(pr["A3"]))
-        _put(rec, 48, 8, scalar_from_json(pr["z1"])); _put(rec, 56, 8, scalar_from_json(pr["z2"]))
+        _set_pt(rec, "M5", "S", point_from_json(Si)); _set_pt(rec, "M5", "T", point_from_json(pr["T"])); _set_pt(rec, "M5", "A3", point_from_json(pr["A3"]))
+        _set(rec, "M5", "z1", scalar_from_json(pr["z1"])); _set(rec, "M5", "z2", scalar_from_json(pr["z2"]))
     elif rnd == 7:
-        _put(rec, 0, 8, scalar_from_json(bodies[0][1]))
+        _set(rec, "M7", "s_i", scalar_from_json(bodies[0][1]))
     else:
         raise ValueError(rnd)
     return rec

@@ -2,6 +2,8 @@
 tests/golden/keys16.json, as the reference's keygen would leave it: keygen/rounds.rs:283-322) and per-session
 nonces drawn with the reference's ranges from a seeded stream.  Array layouts = oracle/mpe_oracle.h."""
 import ctypes as C
+import importlib.util
+import os
 
 import numpy as np
 
@@ -9,6 +11,11 @@ import fixtures as F
 import pyref
 
 Q = pyref.Q
+# the record layouts are the package's table; by path: the package import needs the HIP library, this module does not
+_spec = importlib.util.spec_from_file_location("mpe_wire", os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "multi_party_ecdsa_amd", "wire.py"))
+wire = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(wire)
+msg_words = wire.msg_words
 
 
 class KeysStruct(C.Structure):
@@ -102,10 +109,6 @@ def oracle_sign(lk, nonces, B, first=0, count=None):
 
 
 ROUNDS = [0, 1, 2, 3, 4, 5, 7]                     # rounds that emit a message (M0..M6)
-
-
-def msg_words(S, n, rnd):
-    return {0: 256 * (n + 1), 1: 208 * 2 * (S - 1), 2: 96, 3: 24, 4: 450 * S, 5: 64, 7: 8}[rnd]
 
 
 def oracle_sign_ex(lk, nonces, B, keyset=None):
@@ -264,11 +267,11 @@ def blame5_opened(lk, nonces, slabs, B):
                 src = ((b * S + ind) * P1 + jme) * 2 + 0                      # Bob ind's gamma MessageB to Alice i
                 dst = (b * S + i) * P1 + j
                 bt[dst], br[dst] = nonces["mb_beta_tag"][src], nonces["mb_r"][src]
-                cb[dst] = slabs[1][ind, b, (jme * 2 + 0) * 208:(jme * 2 + 0) * 208 + 128]
+                cb[dst] = slabs[1][ind, b, wire.field("M1", "c", (jme * 2 + 0) * wire.SUB1)]
     o.update(beta_tag=bt, beta_rand=br, c_b=cb)
-    o["delta"] = np.ascontiguousarray(np.transpose(slabs[2][:, :, 0:8], (1, 0, 2)).reshape(B * S, 8))
-    o["g_gamma"] = np.ascontiguousarray(np.transpose(slabs[3][:, :, 8:24], (1, 0, 2)).reshape(B * S, 16))
-    o["c_a"] = np.ascontiguousarray(np.transpose(slabs[0][:, :, n * 256:n * 256 + 128], (1, 0, 2)).reshape(B * S, 128))
+    o["delta"] = np.ascontiguousarray(np.transpose(slabs[2][:, :, wire.field("M2", "delta")], (1, 0, 2)).reshape(B * S, 8))
+    o["g_gamma"] = np.ascontiguousarray(np.transpose(slabs[3][:, :, wire.field("M3", "g_gamma")], (1, 0, 2)).reshape(B * S, 16))
+    o["c_a"] = np.ascontiguousarray(np.transpose(slabs[0][:, :, wire.field("M0L", "c", n * wire.SUB0)], (1, 0, 2)).reshape(B * S, 128))
     return o
 
 
@@ -282,7 +285,7 @@ def blame6_cb(lk, slabs, B):
             for j in range(P1):
                 ind = j if j < i else j + 1
                 jme = i if i < ind else i - 1
-                cb[(b * S + i) * P1 + j] = slabs[1][ind, b, (jme * 2 + 1) * 208:(jme * 2 + 1) * 208 + 128]
+                cb[(b * S + i) * P1 + j] = slabs[1][ind, b, wire.field("M1", "c", (jme * 2 + 1) * wire.SUB1)]
     return cb
 
 
