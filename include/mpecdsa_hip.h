@@ -772,6 +772,55 @@ int mpe_lindell_pdl_verify(mpe_ctx* ctx, const mpe_paillier* pk, int batch, cons
                            const uint32_t* d_stmt_N, const uint32_t* d_stmt_c, const uint32_t* d_stmt_Q, const uint32_t* d_c_key,
                            const uint32_t* d_q1, const mpe_pdl_proof* proof, uint8_t* d_ok, void* stream);
 
+/* ---- Lindell'17, key generation and the ephemeral exchange (lindell_2017/party_one.rs, party_two.rs) ------------------ */
+/* Sampled values (secrets, nonces, blind factors) are inputs; scalars [batch][8] are reduced mod q as read, points [batch][16],
+ * commitments and blind factors [batch][8].  Every d_ok is [batch], ok[i] = 1 accepts.  The four calls between the
+ * commitments run on the caller's stream without synchronising it.
+ * `HashCommitment::create_commitment_with_user_defined_randomness(m, blind)` for a 256-bit m [batch][8]: SHA-256 over
+ * BigInt::to_bytes(m) | BigInt::to_bytes(blind) — minimal big-endian bytes, leading zero bytes of m dropped, zero as the context's
+ * encoding says (mpe_encoding.zero_bytes); the rule mpe_hash_commit_point applies to its blind factor.  (party_two.rs:345-351) */
+int mpe_hash_commit_bigint(mpe_ctx* ctx, int batch, const uint32_t* d_m, const uint32_t* d_blind, uint32_t* d_com, void* stream);
+/* Party one, `KeyGenFirstMsg::create_commitments_with_fixed_secret_share(x1)` with its witness (party_one.rs:179-219):
+ * (d_Q1, d_R, d_z) = DLogProof::prove(x1) — the words mpe_dlog_prove gives for (x1, nonce) —, d_pk_com = Com(Q1; blind_pk),
+ * d_pok_com = Com(R; blind_pok), both over the compressed point as mpe_hash_commit_point computes. */
+int mpe_lindell_keygen_first_msg(mpe_ctx* ctx, int batch, const uint32_t* d_x1, const uint32_t* d_nonce, const uint32_t* d_blind_pk,
+                                 const uint32_t* d_blind_pok, uint32_t* d_Q1, uint32_t* d_R, uint32_t* d_z, uint32_t* d_pk_com,
+                                 uint32_t* d_pok_com, void* stream);
+/* Party two, `KeyGenSecondMsg::verify_commitments_and_dlog_proof` (party_two.rs:180-223): ok = pk_com == Com(Q1; blind_pk)  &&
+ * pok_com == Com(R; blind_pok)  &&  DLogProof::verify (as mpe_dlog_verify).  A Q1 or R that is no valid point (off the curve, not
+ * canonical, neutral) refuses the item: the reference cannot hold such a point. */
+int mpe_lindell_keygen_verify_first_msg(mpe_ctx* ctx, int batch, const uint32_t* d_pk_com, const uint32_t* d_pok_com,
+                                        const uint32_t* d_blind_pk, const uint32_t* d_blind_pok, const uint32_t* d_Q1, const uint32_t* d_R,
+                                        const uint32_t* d_z, uint8_t* d_ok, void* stream);
+/* Party two, `EphKeyGenFirstMsg::create_commitments` with its witness (party_two.rs:315-371): d_pub = k2 G, d_c = k2 H
+ * (H = base_point2), (d_a1, d_a2, d_z) = ECDDHProof::prove over (G, pub, H, c) — the words mpe_ecddh_prove gives for that statement
+ * and nonce —, d_pk_com = Com(pub; blind_pk), d_pok_com = Com(Sha256(chain_points([a1, a2])) as a BigInt; blind_pok), the digest NOT
+ * reduced mod q and hashed by the rule of mpe_hash_commit_bigint. */
+int mpe_lindell_eph_first_msg(mpe_ctx* ctx, int batch, const uint32_t* d_k2, const uint32_t* d_nonce, const uint32_t* d_blind_pk,
+                              const uint32_t* d_blind_pok, uint32_t* d_pub, uint32_t* d_c, uint32_t* d_a1, uint32_t* d_a2, uint32_t* d_z,
+                              uint32_t* d_pk_com, uint32_t* d_pok_com, void* stream);
+/* Party one, `EphKeyGenSecondMsg::verify_commitments_and_dlog_proof` (party_one.rs:437-483): ok = both commitments recomputed as above
+ * and equal  &&  ECDDHProof::verify over (G, pub, H, c) (as mpe_ecddh_verify).  An invalid pub, c, a1 or a2 refuses the item. */
+int mpe_lindell_eph_verify_first_msg(mpe_ctx* ctx, int batch, const uint32_t* d_pk_com, const uint32_t* d_pok_com, const uint32_t* d_blind_pk,
+                                     const uint32_t* d_blind_pok, const uint32_t* d_pub, const uint32_t* d_c, const uint32_t* d_a1,
+                                     const uint32_t* d_a2, const uint32_t* d_z, uint8_t* d_ok, void* stream);
+/* `party_one::verify(signature, pubkey, message)` (party_one.rs:567-592): d_pub [batch][16], d_msg, d_r, d_s [batch][8].
+ * ok = pub is a valid, finite point  &&  1 <= s  &&  s < q - s (so s >= q and high s are refused)  &&
+ *      P = (m mod q) s^-1 G + (r mod q) s^-1 pub is finite  &&  r == P.x AS INTEGERS (P.x is not reduced mod q; r is reduced only where
+ *      it enters the second scalar).  Where the reference would panic (s = 0, P at infinity) the item is refused. */
+int mpe_ecdsa_verify(mpe_ctx* ctx, int batch, const uint32_t* d_pub, const uint32_t* d_msg, const uint32_t* d_r, const uint32_t* d_s,
+                     uint8_t* d_ok, void* stream);
+/* d_out = a b mod q, rows [batch][8], both factors reduced mod q as read: what `Party1Private::refresh_private_key` (party_one.rs:260-261)
+ * and `Party2Private::update_private_key` (party_two.rs:241-246) do to a share, without the share leaving the device. */
+int mpe_scalar_mul(mpe_ctx* ctx, int batch, const uint32_t* d_a, const uint32_t* d_b, uint32_t* d_out, void* stream);
+/* `party_one::generate_h1_h2_n_tilde()` (party_one.rs:594-607) — NOT the rule of mpe_ntilde_generate: N~ = p~ q~,
+ * phi = (p~ - 1)(q~ - 1), h1 = sample_below(phi), xhi = sample_below(2^256), h2 = (h1^-1 mod N~)^xhi mod N~ (a 256-bit ladder).
+ * Field f draws stream `counter | f << 56` (counter < 2^56), item = row: f = 6 p~, 7 q~, 14 h1, 15 xhi.  d_Nt, d_h1, d_h2 [count][64],
+ * d_xhi [count][8].  An item whose prime search or draw gave up, or whose h1 is no unit modulo N~ (the reference would unwrap() a
+ * None), gets zero rows and adds 1 to *d_fail (may be NULL).  Synchronises the stream (the prime search does, once per pass). */
+int mpe_lindell_ntilde_generate(mpe_ctx* ctx, int count, const uint8_t* h_seed32, uint64_t counter, int max_attempts, uint32_t* d_Nt,
+                                uint32_t* d_h1, uint32_t* d_h2, uint32_t* d_xhi, int32_t* d_fail, void* stream);
+
 /* Kernel geometry chosen for the last launch (for bench.py's roofline accounting). */
 typedef struct {
   int waves;              /* workgroups (= waves) launched */

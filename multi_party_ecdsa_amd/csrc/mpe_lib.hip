@@ -272,6 +272,7 @@ static int launch_pair_modexp(mpe_ctx* ctx, const mpe_pairset* ps, int batch, Ro
 #include "mpe_keygen_deal.h"
 #include "mpe_primes.h"
 #include "mpe_lindell.h"
+#include "mpe_lindell_keygen.h"
 
 extern "C" {
 

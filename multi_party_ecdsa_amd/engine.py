@@ -369,12 +369,17 @@ def dlog_verify(ctx, d_pk, d_R, d_z):
 class Statements:
     """Table of `DLogStatement{N: N~, g: h1, ni: h2}` (party_i.rs:225-229) resident in HBM."""
 
-    def __init__(self, ctx, Nt, h1, h2):
+    def __init__(self, ctx, Nt, h1, h2, wb=None):
+        """wb: None = the context's window width of the fixed-base tables; 0 = one-off statements without tables (mpe_statements_create_wb)"""
         self.ctx = ctx
         self.d = [v if torch.is_tensor(v) else dev(ctx, v, 64) for v in (Nt, h1, h2)]      # ints, or device word tensors [count, 64]
         h = C.c_void_p()
-        N_.check(N_.lib.mpe_statements_create(ctx.h, len(Nt), _ptr(self.d[0]), _ptr(self.d[1]), _ptr(self.d[2]),
-                                              C.byref(h), ctx.stream()), "mpe_statements_create")
+        if wb is None:
+            N_.check(N_.lib.mpe_statements_create(ctx.h, len(Nt), _ptr(self.d[0]), _ptr(self.d[1]), _ptr(self.d[2]),
+                                                  C.byref(h), ctx.stream()), "mpe_statements_create")
+        else:
+            N_.check(N_.lib.mpe_statements_create_wb(ctx.h, len(Nt), _ptr(self.d[0]), _ptr(self.d[1]), _ptr(self.d[2]), int(wb),
+                                                     C.byref(h), ctx.stream()), "mpe_statements_create_wb")
         self.h, self.count = h, len(Nt)
 
     def close(self):
@@ -1240,3 +1245,223 @@ def lindell_sign(ctx, sk, d_c3, d_k1, d_R2, d_key_idx=None):
     N_.check(N_.lib.mpe_lindell_sign(ctx.h, sk.h, B, _ptr(d_key_idx), _ptr(d_c3), _ptr(d_k1), _ptr(d_R2), _ptr(r), _ptr(s),
                                      _ptr(recid), ctx.stream()), "mpe_lindell_sign")
     return r, s, recid
+
+
+# ---- Lindell'17, key generation and the ephemeral exchange (mpe_lindell_keygen.h; lindell_2017/party_one.rs, party_two.rs) ----
+def hash_commit_bigint(ctx, d_m, d_blind):
+    """HashCommitment over a 256-bit BigInt m [B,8] (minimal bytes, as the blind factor): com [B,8]"""
+    out = _new(ctx, d_m.shape[0], 8)
+    N_.check(N_.lib.mpe_hash_commit_bigint(ctx.h, d_m.shape[0], _ptr(d_m), _ptr(d_blind), _ptr(out), ctx.stream()), "mpe_hash_commit_bigint")
+    return out
+
+
+def lindell_keygen_first_msg(ctx, d_x1, d_nonce, d_blind_pk, d_blind_pok):
+    """party one's `KeyGenFirstMsg::create_commitments_with_fixed_secret_share` (party_one.rs:179-219): dict Q1, R, z, pk_com, pok_com"""
+    B = d_x1.shape[0]
+    o = dict(Q1=_new(ctx, B, 16), R=_new(ctx, B, 16), z=_new(ctx, B, 8), pk_com=_new(ctx, B, 8), pok_com=_new(ctx, B, 8))
+    N_.check(N_.lib.mpe_lindell_keygen_first_msg(ctx.h, B, _ptr(d_x1), _ptr(d_nonce), _ptr(d_blind_pk), _ptr(d_blind_pok), _ptr(o["Q1"]), _ptr(o["R"]),
+                                                 _ptr(o["z"]), _ptr(o["pk_com"]), _ptr(o["pok_com"]), ctx.stream()), "mpe_lindell_keygen_first_msg")
+    return o
+
+
+def lindell_keygen_verify_first_msg(ctx, d_pk_com, d_pok_com, d_blind_pk, d_blind_pok, d_Q1, d_R, d_z):
+    """party two's `KeyGenSecondMsg::verify_commitments_and_dlog_proof` (party_two.rs:180-223): ok [B]"""
+    ok = _flags(ctx, d_Q1.shape[0])
+    N_.check(N_.lib.mpe_lindell_keygen_verify_first_msg(ctx.h, d_Q1.shape[0], _ptr(d_pk_com), _ptr(d_pok_com), _ptr(d_blind_pk), _ptr(d_blind_pok),
+                                                        _ptr(d_Q1), _ptr(d_R), _ptr(d_z), _ptr(ok), ctx.stream()), "mpe_lindell_keygen_verify_first_msg")
+    return ok
+
+
+def lindell_eph_first_msg(ctx, d_k2, d_nonce, d_blind_pk, d_blind_pok):
+    """party two's `EphKeyGenFirstMsg::create_commitments` (party_two.rs:315-371): dict pub, c, a1, a2, z, pk_com, pok_com"""
+    B = d_k2.shape[0]
+    o = dict(pub=_new(ctx, B, 16), c=_new(ctx, B, 16), a1=_new(ctx, B, 16), a2=_new(ctx, B, 16), z=_new(ctx, B, 8), pk_com=_new(ctx, B, 8),
+             pok_com=_new(ctx, B, 8))
+    N_.check(N_.lib.mpe_lindell_eph_first_msg(ctx.h, B, _ptr(d_k2), _ptr(d_nonce), _ptr(d_blind_pk), _ptr(d_blind_pok), _ptr(o["pub"]), _ptr(o["c"]),
+                                              _ptr(o["a1"]), _ptr(o["a2"]), _ptr(o["z"]), _ptr(o["pk_com"]), _ptr(o["pok_com"]), ctx.stream()),
+             "mpe_lindell_eph_first_msg")
+    return o
+
+
+def lindell_eph_verify_first_msg(ctx, d_pk_com, d_pok_com, d_blind_pk, d_blind_pok, d_pub, d_c, d_a1, d_a2, d_z):
+    """party one's `EphKeyGenSecondMsg::verify_commitments_and_dlog_proof` (party_one.rs:437-483): ok [B]"""
+    ok = _flags(ctx, d_pub.shape[0])
+    N_.check(N_.lib.mpe_lindell_eph_verify_first_msg(ctx.h, d_pub.shape[0], _ptr(d_pk_com), _ptr(d_pok_com), _ptr(d_blind_pk), _ptr(d_blind_pok),
+                                                     _ptr(d_pub), _ptr(d_c), _ptr(d_a1), _ptr(d_a2), _ptr(d_z), _ptr(ok), ctx.stream()),
+             "mpe_lindell_eph_verify_first_msg")
+    return ok
+
+
+def ecdsa_verify(ctx, d_pub, d_msg, d_r, d_s):
+    """`party_one::verify` (party_one.rs:567-592) batched: ok [B]; high s and s >= q are refused, r is compared with P.x as integers"""
+    ok = _flags(ctx, d_pub.shape[0])
+    N_.check(N_.lib.mpe_ecdsa_verify(ctx.h, d_pub.shape[0], _ptr(d_pub), _ptr(d_msg), _ptr(d_r), _ptr(d_s), _ptr(ok), ctx.stream()), "mpe_ecdsa_verify")
+    return ok
+
+
+def scalar_mul(ctx, d_a, d_b):
+    """a b mod q per row [B,8]"""
+    out = _new(ctx, d_a.shape[0], 8)
+    N_.check(N_.lib.mpe_scalar_mul(ctx.h, d_a.shape[0], _ptr(d_a), _ptr(d_b), _ptr(out), ctx.stream()), "mpe_scalar_mul")
+    return out
+
+
+def lindell_ntilde_generate(ctx, count, seed, counter, max_attempts=0):
+    """`party_one::generate_h1_h2_n_tilde()` x count (party_one.rs:594-607): dict of device tensors Nt, h1, h2 [count, 64], xhi [count, 8], fail [1]"""
+    o = {f: _new(ctx, count, 64) for f in ("Nt", "h1", "h2")}
+    o["xhi"] = _new(ctx, count, 8)
+    fail = torch.zeros((1,), dtype=torch.int32, device=ctx.device)
+    N_.check(N_.lib.mpe_lindell_ntilde_generate(ctx.h, count, _seed(seed), int(counter), max_attempts, _ptr(o["Nt"]), _ptr(o["h1"]), _ptr(o["h2"]),
+                                                _ptr(o["xhi"]), _ptr(fail), ctx.stream()), "mpe_lindell_ntilde_generate")
+    o["fail"] = fail
+    return o
+
+
+# stream fields of the three chains below (field f of a call draws stream counter | f << 56; DESIGN.md §12)
+LINDELL_FIELDS = dict(x1=16, x2=17, blind_pk=18, blind_pok=19, nonce1=20, nonce2=21, enc_r=22, cdlog_r=23, pdl_alpha=24, pdl_beta=25, pdl_rho=26,
+                      pdl_gamma=27, k1=32, k2=33, eph_nonce1=34, eph_nonce2=35, eph_blind_pk=36, eph_blind_pok=37)
+LINDELL_MATERIAL_FIELDS = ("p", "q", "pt", "qt", "h1", "xhi")     # rows [B, 32] x 4, [B, 64], [B, 8]
+_Q = 0xFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFEBAAEDCE6AF48A03BBFD25E8CD0364141
+
+
+def _widen(t, words):
+    out = torch.zeros((t.shape[0], words), dtype=torch.int32, device=t.device)
+    out[:, :t.shape[1]] = t
+    return out
+
+
+def _lindell_paillier_half(ctx, B, seed, counter, d_x1, d_q1, material=None):
+    """What lindell_keygen and lindell_rotate share: `generate_keypair_and_encrypted_share`, `generate_ni_proof_correct_key`,
+    `verify_ni_proof_correct_key`, `pdl_proof`, `pdl_verify` (party_one.rs:319-401, party_two.rs:275-311) for the shares d_x1 [B,8]
+    (canonical scalars); d_q1 [B,16] is the Q1 party two holds.  One Paillier key and one (N~, h1, h2) per wallet."""
+    sid = lambda f: int(counter) | (LINDELL_FIELDS[f] << 56)
+    fails = []
+    if material is None:
+        p, q, N, f = paillier_keygen(ctx, B, seed, counter)
+        nt = lindell_ntilde_generate(ctx, B, seed, counter)
+        Nt, h1, h2, xhi = nt["Nt"], nt["h1"], nt["h2"], nt["xhi"]
+        fails += [f, nt["fail"]]
+    else:
+        m = {f: words_to_ints(np.ascontiguousarray(material[f])) for f in LINDELL_MATERIAL_FIELDS}
+        if any(len(v) != B for v in m.values()):
+            raise ValueError("material: B rows per field")
+        nts = [a * b for a, b in zip(m["pt"], m["qt"])]
+        p, q, N = dev(ctx, m["p"], 32), dev(ctx, m["q"], 32), dev(ctx, [a * b for a, b in zip(m["p"], m["q"])], 64)
+        Nt, h1, xhi = dev(ctx, nts, 64), dev(ctx, m["h1"], 64), dev(ctx, m["xhi"], 8)
+        h2 = dev(ctx, [pow(pow(h, -1, n), x, n) for h, x, n in zip(m["h1"], m["xhi"], nts)], 64)
+    ctx.sync()
+    Ni, Nti = host(N), host(Nt)                                  # public moduli: the sampler's bounds are formed from them on the host
+    sk = PaillierKeys(ctx, p=p, q=q)
+    pk = PaillierKeys(ctx, N=Ni)                                 # what party two holds
+    r, f = sample_below(ctx, B, seed, sid("enc_r"), N, 64)       # Randomness::sample(&ek)
+    fails.append(f)
+    c_key = sk.encrypt_device(_widen(d_x1, 64), r)
+    sigma = correct_key_prove(ctx, sk).reshape(B, 11 * 64)
+    ok_ck = correct_key_verify(ctx, N, sigma)
+    long_enough = ((N[:, 63].to(torch.int64) & 0xFFFFFFFF) >> 30) != 0     # ek.n.bit_length() >= PAILLIER_KEY_SIZE - 1 (party_two.rs:307)
+    # pdl_proof (party_one.rs:366-401)
+    cd_r = sample_bits(ctx, B, seed, sid("cdlog_r"), 512, 16)
+    cd_x, cd_y = composite_dlog_prove(ctx, Nt, h1, h2, _widen(xhi, 64), cd_r)
+    stm = Statements(ctx, Nt, h1, h2, wb=0)
+    nonces = {}
+    nonces["alpha"], f1 = sample_below(ctx, B, seed, sid("pdl_alpha"), dev(ctx, [_Q ** 3], 24), 24)
+    nonces["beta"], f2 = sample_below(ctx, B, seed, sid("pdl_beta"), dev(ctx, [max(n - 2, 0) for n in Ni], 64), 64, flags=SAMPLE_PLUS_ONE)
+    nonces["rho"], f3 = sample_below(ctx, B, seed, sid("pdl_rho"), dev(ctx, [_Q * n for n in Nti], 72), 72)
+    nonces["gamma"], f4 = sample_below(ctx, B, seed, sid("pdl_gamma"), dev(ctx, [_Q ** 3 * n for n in Nti], 88), 88)
+    fails += [f1, f2, f3, f4]
+    Q, proof = lindell_pdl_proof(ctx, sk, stm, c_key, d_x1, r, nonces)
+    ok_pdl = lindell_pdl_verify(ctx, pk, Nt, h1, h2, cd_x, cd_y, N, c_key, Q, c_key, d_q1, proof)
+    ok = ok_ck.bool() & long_enough & ok_pdl.bool()
+    ctx.sync()
+    stm.close(); sk.close(); pk.close()
+    return dict(ok=ok, fails=fails, p=p, q=q, N=N, c_key=c_key, r=r, Nt=Nt, h1=h1, h2=h2, xhi=xhi, sigma=sigma, cd_x=cd_x, cd_y=cd_y, Q=Q, pdl=proof)
+
+
+def _given_scalars(ctx, v):
+    """a share handed in: a device tensor [B,8] of canonical scalars, or Python ints (reduced mod q, as Scalar::from does)"""
+    return v if torch.is_tensor(v) else dev(ctx, [int(x) % _Q for x in v], 8)
+
+
+def lindell_keygen(ctx, B, seed, counter=0, x1=None, x2=None, material=None):
+    """`test_full_key_gen` (lindell_2017/test.rs) for B wallets with both parties local: a chain of C-ABI calls, no secret on the host.
+      x1 / x2:  None = drawn by the device sampler; given = the `_with_fixed_secret_share` forms.
+      material: None = mint the Paillier key and (N~, h1, h2, xhi) on the device (streams counter | 0, 1, 6, 7, 14, 15 << 56); or a dict
+                of uint32 arrays LINDELL_MATERIAL_FIELDS taken as `Paillier::keypair()` / `generate_h1_h2_n_tilde()` would have drawn them.
+      Every other draw: streams counter | LINDELL_FIELDS[..] << 56 of `seed`.
+    Returns a dict: ok [B] uint8 (both first-message verdicts, the correct-key and PDL verdicts, pubkeys agree), failures (sampler /
+    prime search give-ups), the wallet x1, x2 [B,8], Q1, Q2, pubkey [B,16], p, q [B,32], N [B,64], c_key [B,128], r [B,64], and `proofs`."""
+    if counter >> 56:
+        raise ValueError("counter < 2^56")
+    sid = lambda f: int(counter) | (LINDELL_FIELDS[f] << 56)
+    fails = []
+
+    def scalar(f):
+        v, fl = sample_scalar(ctx, B, seed, sid(f))
+        fails.append(fl)
+        return v
+    x1 = scalar("x1") if x1 is None else _given_scalars(ctx, x1)
+    x2 = scalar("x2") if x2 is None else _given_scalars(ctx, x2)
+    blind_pk, blind_pok = sample_bits(ctx, B, seed, sid("blind_pk"), 256, 8), sample_bits(ctx, B, seed, sid("blind_pok"), 256, 8)
+    m1 = lindell_keygen_first_msg(ctx, x1, scalar("nonce1"), blind_pk, blind_pok)                      # party one
+    Q2, R2, z2 = dlog_prove(ctx, x2, scalar("nonce2"))                                                   # party two: KeyGenFirstMsg::create
+    ok_p1 = dlog_verify(ctx, Q2, R2, z2)                                                                 # party one: verify_and_decommit
+    ok_p2 = lindell_keygen_verify_first_msg(ctx, m1["pk_com"], m1["pok_com"], blind_pk, blind_pok, m1["Q1"], m1["R"], m1["z"])
+    half = _lindell_paillier_half(ctx, B, seed, counter, x1, m1["Q1"], material)
+    pub1, pub2 = ec_mul(ctx, x1, Q2), ec_mul(ctx, x2, m1["Q1"])                                          # compute_pubkey on both sides
+    ok = ok_p1.bool() & ok_p2.bool() & half["ok"] & (pub1 == pub2).all(1)
+    ctx.sync()
+    return dict(ok=ok.to(torch.uint8), failures=int(sum(int(f.item()) for f in fails + half["fails"])), x1=x1, x2=x2, Q1=m1["Q1"], Q2=Q2,
+                pubkey=pub1, p=half["p"], q=half["q"], N=half["N"], c_key=half["c_key"], r=half["r"],
+                proofs=dict(first_msg=m1, blind_pk=blind_pk, blind_pok=blind_pok, half=half))
+
+
+def lindell_eph_exchange(ctx, B, seed, counter):
+    """the ephemeral exchange both ways: party one's `EphKeyGenFirstMsg::create` (two base multiplications + mpe_ecddh_prove) checked by
+    party two's `verify_and_decommit` (mpe_ecddh_verify), party two's `create_commitments` checked by party one's verdict.
+    Returns dict ok [B] uint8, k1, k2 [B,8], R1, R2 [B,16] (what lindell_partial_sig / lindell_sign take), failures."""
+    if counter >> 56:
+        raise ValueError("counter < 2^56")
+    sid = lambda f: int(counter) | (LINDELL_FIELDS[f] << 56)
+    fails = []
+
+    def scalar(f):
+        v, fl = sample_scalar(ctx, B, seed, sid(f))
+        fails.append(fl)
+        return v
+    k1, k2 = scalar("k1"), scalar("k2")
+    blind_pk, blind_pok = sample_bits(ctx, B, seed, sid("eph_blind_pk"), 256, 8), sample_bits(ctx, B, seed, sid("eph_blind_pok"), 256, 8)
+    Gp = dev(ctx, [0x79BE667EF9DCBBAC55A06295CE870B07029BFCDB2DCE28D959F2815B16F81798 |
+                   (0x483ADA7726A3C4655DA4FBFC0E1108A8FD17B448A68554199C47D08FFB10D4B8 << 256)], 16).expand(B, 16).contiguous()
+    Hp = dev(ctx, [0x08d13221e3a7326a34dd45214ba80116dd142e4b5ff3ce66a8dc7bfa0378b795 |
+                   (0x5d41ac1477614b5c0848d50dbd565ea2807bcba1df0df07a8217e9f7f7c2be88 << 256)], 16).expand(B, 16).contiguous()
+    R1 = ec_mul_base(ctx, k1)
+    st1 = dict(g1=Gp, h1=R1, g2=Hp, h2=ec_mul(ctx, k1, Hp))
+    pr1 = ecddh_prove(ctx, k1, scalar("eph_nonce1"), st1)
+    ok_a = ecddh_verify(ctx, st1, pr1)
+    m2 = lindell_eph_first_msg(ctx, k2, scalar("eph_nonce2"), blind_pk, blind_pok)
+    ok_b = lindell_eph_verify_first_msg(ctx, m2["pk_com"], m2["pok_com"], blind_pk, blind_pok, m2["pub"], m2["c"], m2["a1"], m2["a2"], m2["z"])
+    ok = ok_a.bool() & ok_b.bool()
+    ctx.sync()
+    return dict(ok=ok.to(torch.uint8), k1=k1, k2=k2, R1=R1, R2=m2["pub"], failures=int(sum(int(f.item()) for f in fails)),
+                proofs=dict(p1=dict(st1, **pr1), p2=m2, blind_pk=blind_pk, blind_pok=blind_pok))
+
+
+def lindell_rotate(ctx, wallet, d_factor, seed, counter, d_factor2=None, material=None):
+    """`Party1Private::refresh_private_key(factor)` (party_one.rs:246-296): a new Paillier key, x1 f, a new c_key, the correct-key proof
+    and the PDL triple, checked as party two checks them against f Q1 — the second half of lindell_keygen over another x1.
+    d_factor2 given: `Party2Private::update_private_key` (party_two.rs:241-246), x2 <- x2 factor2.  Returns the new wallet dict (same
+    fields as lindell_keygen's; pubkey is the OLD one, which still verifies when factor2 = factor^-1)."""
+    B = wallet["x1"].shape[0]
+    if counter >> 56:
+        raise ValueError("counter < 2^56")
+    x1 = scalar_mul(ctx, wallet["x1"], d_factor)
+    q1 = ec_mul(ctx, d_factor, wallet["Q1"])
+    half = _lindell_paillier_half(ctx, B, seed, counter, x1, q1, material)
+    out = dict(wallet)
+    out.update(ok=half["ok"].to(torch.uint8), failures=int(sum(int(f.item()) for f in half["fails"])), x1=x1, Q1=q1, p=half["p"], q=half["q"],
+               N=half["N"], c_key=half["c_key"], r=half["r"], proofs=dict(half=half))
+    if d_factor2 is not None:
+        out["x2"] = scalar_mul(ctx, wallet["x2"], d_factor2)
+        out["Q2"] = ec_mul(ctx, d_factor2, wallet["Q2"])
+    ctx.sync()
+    return out
