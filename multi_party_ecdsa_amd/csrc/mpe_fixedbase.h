@@ -106,7 +106,8 @@ __global__ void __launch_bounds__(64) fb_fill_kernel(int nrows, ModsetView ms, i
 // `split` = S (1, 2, 4, 8, 16): the S lane groups of a wave that follow each other share ONE item.  A fixed-base power has no
 // squarings — it is a product of nwin table rows — so the product can be cut into S runs of ~nwin / S rows, one per group, whose
 // partial products (Montgomery forms, like the rows) are multiplied together in a tree through LDS: a serial chain of
-// ceil(nwin / S) + log2(S) + 1 multiplications instead of nwin + 1 (217 windows at 13 bits: 218 -> 32 with S = 8).  A small launch
+// ceil(nwin / S) + log2(S) multiplications instead of nwin (217 windows at 13 bits: 217 -> 31 with S = 8; a run's first row is
+// loaded, not multiplied, and the last multiplication, by 1, leaves the Montgomery form).  A small launch
 // lasts as long as ONE chain however few items it has (1 024 sessions: 2.2 - 5.7 ms per launch, a dozen launches per batch), so the
 // host picks the largest S that still leaves one wave per SIMD (launch_fb_modexp); large launches keep S = 1, where every lane
 // multiplies useful rows all the time.  Same residue: the factors are the same rows, multiplied in another order.

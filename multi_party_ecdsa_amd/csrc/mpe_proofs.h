@@ -18,7 +18,7 @@ struct mpe_statements {
   uint32_t* h1 = nullptr;
   uint32_t* h2 = nullptr;
   mpe_modset* ms = nullptr;  // 2048-bit, modulus k = N~_k
-  int fb_wb = 8;               // window width of the fixed-base tables
+  int fb_wb = 8;               // window width of the fixed-base tables: set by mpe_statements_create_wb; 0 = no tables
   uint32_t* fb_tab = nullptr;  // [2*count][windows][2^fb_wb][72] fixed-base tables of h1 (even) / h2 (odd)
 };
 
@@ -586,7 +586,7 @@ int mpe_statements_create_wb(mpe_ctx* ctx, int count, const uint32_t* d_Nt, cons
   if (rc != MPE_OK) { (void)hipFree(s->blob); delete s; return rc; }
   s->fb_wb = 0;                                  // no tables unless they are built below
   if (ctx->use_fixed_base && wb != 0) {
-    // fixed-base window tables of h1, h2 (26 MB per base at 8-bit windows), built on the GPU once per statement set:
+    // fixed-base window tables of h1, h2 (0.5 GB per base at the default 13-bit windows, 26 MB at 8 bits), built on the GPU once per statement set:
     // the window bases one after the other (squarings), then every window's multiples in parallel
     using C = mpe::Cfg2048;
     s->fb_wb = wb;
