@@ -173,26 +173,11 @@ __device__ __forceinline__ void cios2(uint32_t (&res)[C::L], uint64_t (&c)[C::L]
   cios_finish<C>(res, c, ln);
 }
 
-// (r0, r1) = (a0, a1) * (y0, y1) R^-1 in Z/N^2.  The group's LDS region holds y0 in B0 and y1 in B1; for a squaring
-// (sq: y == a) B1 holds 2 y0 instead, so that pass B is the single stream a1 * (2 a0).
-// Column bound: a pass-B column absorbs per lane block 18 x (2^59.01 + 2^58.01) (squaring: the doubled stream) or
-// 18 x 3 x 2^58.01 (two streams) plus the 2^30 pre-load and the fold carries: < 2^63.8.
+// pass B's pre-loaded columns: c = K_c + (R - 1) - m, limb-wise (the digits m of pass A wait in M)
 template <class C>
-__device__ __forceinline__ void pairmul(uint32_t (&r0)[C::L], uint32_t (&r1)[C::L], const uint32_t (&a0)[C::L],
-                                        const uint32_t (&a1)[C::L], uint32_t* gl, const uint32_t (&n)[C::L],
-                                        uint32_t n0inv, bool sq, bool half, const Lane& ln) {
+__device__ __forceinline__ void pair_preload(uint64_t (&c)[C::L], const uint32_t* gl, const Lane& ln) {
   using PL = PairLds<C>;
   constexpr int L = C::L;
-  uint64_t c[L];
-#pragma unroll
-  for (int i = 0; i < L; ++i) c[i] = 0;
-  cios1<C, true>(r0, c, a0, gl + PL::B0, gl + PL::M, n, n0inv, ln);           // pass A: u, digits -> M
-  wave_lds_sync();
-  if (half) {                                      // arithmetic modulo N only: the x1 components stay 0
-#pragma unroll
-    for (int i = 0; i < L; ++i) r1[i] = 0;
-    return;
-  }
 #pragma unroll
   for (int i = 0; i < L; ++i) {
     uint32_t mi = gl[PL::M + ln.t * L + i];
@@ -203,18 +188,57 @@ __device__ __forceinline__ void pairmul(uint32_t (&r0)[C::L], uint32_t (&r1)[C::
     }
     c[i] = (uint64_t)(gl[PL::KC + ln.t * L + i] - mi);
   }
-  wave_lds_sync();
-  // u waits in the M region (its digits are consumed) so that pass B does not carry 18 more live registers
+}
+
+// (x0, x1) <- (x0, x1) * (y0, y1) R^-1 in Z/N^2, in place.  The group's LDS region holds y0 in B0 and y1 in B1.
+// Column bound: a pass-B column absorbs per lane block 18 x 3 x 2^58.01 (two streams; the squaring's doubled stream:
+// 18 x (2^59.01 + 2^58.01)) plus the 2^30 pre-load and the fold carries: < 2^63.8.
+template <class C>
+__device__ __forceinline__ void pairmul(uint32_t (&x0)[C::L], uint32_t (&x1)[C::L], uint32_t* gl, const uint32_t (&n)[C::L],
+                                        uint32_t n0inv, bool half, const Lane& ln) {
+  using PL = PairLds<C>;
+  constexpr int L = C::L;
+  uint64_t c[L];
+  uint32_t u[L];
 #pragma unroll
-  for (int i = 0; i < L; ++i) gl[PL::M + ln.t * L + i] = r0[i];
-  if (sq) {
-    cios1<C, false>(r1, c, a1, gl + PL::B1, gl + PL::M, n, n0inv, ln);        // pass B: a1 * (2 a0) - m
-  } else {
-    cios2<C>(r1, c, a0, a1, gl + PL::B0, gl + PL::B1, n, n0inv, ln);          // pass B: a0 * y1 + a1 * y0 - m
+  for (int i = 0; i < L; ++i) c[i] = 0;
+  cios1<C, true>(u, c, x0, gl + PL::B0, gl + PL::M, n, n0inv, ln);            // pass A: u, digits -> M
+  wave_lds_sync();
+  if (half) {                                      // arithmetic modulo N only: the x1 components stay 0
+#pragma unroll
+    for (int i = 0; i < L; ++i) { x0[i] = u[i]; x1[i] = 0; }
+    return;
   }
+  pair_preload<C>(c, gl, ln);
+  wave_lds_sync();
+  // pass B still reads x0, so u waits in the M region (its digits are consumed) and comes back into x0's registers
+#pragma unroll
+  for (int i = 0; i < L; ++i) gl[PL::M + ln.t * L + i] = u[i];
+  cios2<C>(x1, c, x0, x1, gl + PL::B0, gl + PL::B1, n, n0inv, ln);            // pass B: x0 * y1 + x1 * y0 - m
   wave_lds_sync();
 #pragma unroll
-  for (int i = 0; i < L; ++i) r0[i] = gl[PL::M + ln.t * L + i];
+  for (int i = 0; i < L; ++i) x0[i] = gl[PL::M + ln.t * L + i];
+}
+
+// (x0, x1) <- (x0, x1)^2 R^-1, in place.  B0 holds x0 (B1 is not read).  Pass B is the single stream (2 x1) * x0: x0 is dead once
+// pass A's loop ends, so u takes its registers (no trip through LDS), and x1 is doubled in its own registers — the products are
+// those of x1 * (2 x0), column by column.  half: the caller's x1 is 0 and stays 0.
+template <class C>
+__device__ __forceinline__ void pairsq(uint32_t (&x0)[C::L], uint32_t (&x1)[C::L], uint32_t* gl, const uint32_t (&n)[C::L],
+                                       uint32_t n0inv, bool half, const Lane& ln) {
+  using PL = PairLds<C>;
+  constexpr int L = C::L;
+  uint64_t c[L];
+#pragma unroll
+  for (int i = 0; i < L; ++i) c[i] = 0;
+  cios1<C, true>(x0, c, x0, gl + PL::B0, gl + PL::M, n, n0inv, ln);           // pass A: u -> x0, digits -> M
+  wave_lds_sync();
+  if (half) return;
+  pair_preload<C>(c, gl, ln);
+  wave_lds_sync();
+#pragma unroll
+  for (int i = 0; i < L; ++i) x1[i] <<= 1;                                    // limbs < 2^W + 2^12: no bit is lost
+  cios1<C, false>(x1, c, x1, gl + PL::B0, gl + PL::M, n, n0inv, ln);          // pass B: (2 x1) * x0 - m
 }
 
 // off1: where the second component starts in `src` (C::K in a window table, pair_kstore in the per-modulus constants)
@@ -525,7 +549,44 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     int k = 0, b = top_bit;
 #pragma unroll 1
     while (ph != PP_DONE) {
-      bool sq = false;
+      if (ph == PP_SQ || (SLIDE && ph == PP_TSQ)) {
+        // A run of squarings: down to the bit where the next multiplication (or the end) waits.  Nothing of the phase machine runs
+        // between them; the schedule is wave-uniform (scalar).
+        int run = 1;                                          // PP_TSQ: the one squaring x^2
+        if (ph == PP_SQ) {
+          int stop = sl ? (sw_lo < b ? sw_lo : 0) : ((b - 1) / wb) * wb;       // the low end of the window being crossed
+          if (dual) {                                         // the second exponent's 4-bit windows
+            int s2 = (b - 1) & ~3;
+            if ((s2 >> 2) >= nwin2) s2 = (nwin2 - 1) * 4;
+            if (s2 > stop) stop = s2;
+          }
+          if (stop < 0) stop = 0;
+          run = b - stop;
+          b = stop;
+        }
+        run = __builtin_amdgcn_readfirstlane(run);
+#pragma unroll 1
+        do {
+          put_limbs<C>(gl + PL::B0, cur0, ln);
+          wave_lds_sync();
+          pairsq<C>(cur0, cur1, gl, n, n0inv, half != 0, ln);
+          wave_lds_sync();
+        } while (--run > 0);
+        if (SLIDE && ph == PP_TSQ) {
+          // sliding windows need the ODD powers only: x^2 becomes the multiplier of the table phase, x comes back from the table
+          put_limbs<C>(gl + PL::B0, cur0, ln);
+          put_limbs<C>(gl + PL::B1, cur1, ln);
+          __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+          load_owner<C>(cur0, tab + K2, ln);
+          load_owner<C>(cur1, tab + K2 + C::K, ln);
+          ph = PP_TAB;
+        } else {
+          const bool m1 = sl ? b == sw_lo : (b % wb) == 0;
+          const bool m2 = dual && (b & 3) == 0 && (b >> 2) < nwin2;
+          ph = m1 ? PP_MUL1 : (m2 ? PP_MUL2 : PP_FINAL);      // (neither: the run ended at b == 0)
+        }
+        continue;
+      }
       // ---- multiplier pair -> LDS ----
       if (ph == PP_IN) {
         copy_pair_to_lds<C>(gl, ps.tp + (size_t)mi * 2 * KS, ln, KS);
@@ -534,11 +595,6 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
       } else if (ph == PP_TAB) {
         // fixed windows: the multiplier is x (written once); sliding: it is x^2, left in place by PP_TSQ
         if (k == 1 && !(sl && !which)) { put_limbs<C>(gl + PL::B0, cur0, ln); put_limbs<C>(gl + PL::B1, cur1, ln); }
-      } else if (ph == PP_SQ || (SLIDE && ph == PP_TSQ)) {
-        put_limbs<C>(gl + PL::B0, cur0, ln);
-#pragma unroll
-        for (int i = 0; i < C::L; ++i) gl[PL::B1 + ln.t * C::L + i] = cur0[i] << 1;
-        sq = true;
       } else if (ph == PP_MUL1) {
         const uint32_t w = sl ? sw_val : exp_window(ex, exp_words, b / wb, wb);
 #ifndef MPE_NARROW_COPY                                     // (A/B switch: the word-by-word copy of rounds 1-3)
@@ -562,11 +618,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
         }
       }
       wave_lds_sync();
-      uint32_t r0[C::L], r1[C::L];
-      pairmul<C>(r0, r1, cur0, cur1, gl, n, n0inv, sq, half != 0, ln);
+      pairmul<C>(cur0, cur1, gl, n, n0inv, half != 0, ln);
       wave_lds_sync();
-#pragma unroll
-      for (int i = 0; i < C::L; ++i) { cur0[i] = r0[i]; cur1[i] = r1[i]; }
 
       // ---- product -> its place; next phase ----
       bool tables_done = false;
@@ -587,14 +640,6 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
         store_owner<C>(T + K2 + C::K, cur1, ln);
         k = 1;
         ph = (sl && !which) ? PP_TSQ : PP_TAB;
-      } else if (SLIDE && ph == PP_TSQ) {
-        // sliding windows need the ODD powers only: x^2 becomes the multiplier of the table phase, x comes back from the table
-        put_limbs<C>(gl + PL::B0, cur0, ln);
-        put_limbs<C>(gl + PL::B1, cur1, ln);
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-        load_owner<C>(cur0, tab + K2, ln);
-        load_owner<C>(cur1, tab + K2 + C::K, ln);
-        ph = PP_TAB;
       } else if (ph == PP_TAB) {
         uint32_t* T = which ? tab2 : tab;
         const int step = (sl && !which) ? 2 : 1;              // x^3, x^5, ... x^(TE-1)  |  x^2, x^3, ...
@@ -617,18 +662,20 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
         }
       } else if (ph == PP_FINAL) {
         ph = PP_DONE;
-      } else {
-        if (ph == PP_SQ) --b;
+      } else {                                                // after a window multiplication
         if (ph == PP_MUL1 && sl) sw_lo = slide_window(exu, exp_words, b - 1, wb, sw_val);     // the next window below this one
-        const bool m1 = ph == PP_SQ && (sl ? b == sw_lo : (b % wb) == 0);
         const bool m2 = ph != PP_MUL2 && dual && (b & 3) == 0 && (b >> 2) < nwin2;
-        ph = m1 ? PP_MUL1 : (m2 ? PP_MUL2 : (b == 0 ? PP_FINAL : PP_SQ));
+        ph = m2 ? PP_MUL2 : (b == 0 ? PP_FINAL : PP_SQ);
       }
       if (tables_done) {
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
         const uint32_t w = sl ? sw_val : exp_window(ex, exp_words, nwin - 1, wb);
         load_owner<C>(cur0, tab + (size_t)w * K2, ln);
         load_owner<C>(cur1, tab + (size_t)w * K2 + C::K, ln);
+        if (half) {                                           // (the squarings of half mode leave x1 alone: it is 0 from here on)
+#pragma unroll
+          for (int i = 0; i < C::L; ++i) cur1[i] = 0;
+        }
         b = sl ? sw_lo : top_bit;
         if (sl) sw_lo = slide_window(exu, exp_words, b - 1, wb, sw_val);
         ph = b == 0 ? PP_FINAL : PP_SQ;
