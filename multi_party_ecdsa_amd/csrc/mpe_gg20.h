@@ -744,6 +744,21 @@ __global__ void sign_finish_kernel(int B, int L, int b0, const int32_t* __restri
   status[o] = st;
 }
 
+// ---- work started ahead of its round ------------------------------------------------------------------------------------
+// Lock-step signing of a small batch (mpe_gg20_sign: every signer local, the message slabs cannot change between two rounds) starts work before
+// the round that consumes it.  Round 0 inverts the ciphertexts round 1's verifiers need and computes Round 2's nonce-only points (every mode);
+// the two dependent ladders behind beta^N mod N^2 of round 4's PDL proofs (the prover's own nonce under its own key) run in the BACKGROUND on
+// aux[1], at wave priority 0 beside the ladders at 2 and the EC kernels at 1 (mpe_sched.h).  Its state; pdl_ahead_* and ahead_drain move it.
+enum class PdlStage { idle, first_queued, ready };     // ready: both ladders queued, ev_ahead recorded behind them
+struct Ahead {
+  bool lockstep = false;           // set by mpe_gg20_sign alone
+  uint32_t* cinv = nullptr;        // [vi][128] c^-1 mod N^2 of every (verifier, sender, statement) of round 1; small batches only
+  uint8_t* cinv_ok = nullptr; bool cinv_done = false;      // [vi] its verdicts; done: round 0 queued the inversion, round 1 takes it
+  uint32_t* ped = nullptr;         // [pi][48] l H | s1 G | s2 H of Round 2 (ped_ahead_kernel)
+  uint32_t *pdl_bn = nullptr, *pdl_scratch = nullptr;      // [pp][128], modexp_nn_scratch_words(pp); small batches only
+  PdlStage pdl = PdlStage::idle;   // back to idle only when round 4 consumed the value or ahead_drain waited for it
+};
+
 }  // namespace gg
 }  // namespace mpe
 
@@ -770,17 +785,7 @@ struct mpe_gg20_session {
   int32_t *status = nullptr, *sig_recid = nullptr;
   int32_t *sub0_vi = nullptr, *sub4_pv = nullptr, *rdash_pv = nullptr;
   uint8_t *ok_vi = nullptr, *ok_pv = nullptr;
-  // lock-step signing of a small batch (mpe_gg20_sign: every signer local, the rounds chained inside the library): round 0 already inverts
-  // the ciphertexts round 1's verifiers will need, beside the tail of the range proofs (round1_inversion_ahead)
-  bool lockstep = false, cinv_ahead = false;
-  uint32_t* cinv_pre = nullptr;    // [vi][128] c^-1 mod N^2 of every (verifier, sender, statement) of round 1; small batches only
-  uint8_t* cinv_ok_pre = nullptr;  // [vi]
-  // ... and round 2 starts the beta^N mod N^2 of round 4's PDL proofs (the prover's own nonce under its own key: no input of any round)
-  // as a BACKGROUND launch — wave priority 0 beside the decryption ladder at 2 and the EC kernels of rounds 2 and 3 at 1 (mpe_sched.h)
-  uint32_t* ped_pre = nullptr;     // [pi][48] l H | s1 G | s2 H of Round 2 (ped_ahead_kernel, Round 0)
-  bool pdl_ahead = false, pdl_phase1 = false;      // pdl_phase1: the first of its two ladders already ran between rounds 0 and 1
-  uint32_t* pdl_bn = nullptr;      // [pp][128]
-  uint32_t* pdl_scratch = nullptr; // modexp_nn_scratch_words(pp)
+  mpe::gg::Ahead ahead{};          // work started before the round that consumes it
   int fault_step = 0;              // fault injection of the reference's tests (gg_2020/test.rs:282-289,458-465,679-686): 5 / 6 / 7
   uint32_t fault_mask = 0;         // signer ordinals that double their delta_i / sigma_i / s_i
   char* tmp = nullptr;             // per-round scratch (dense outputs of the composites before they are packed)
@@ -805,6 +810,8 @@ static void gg_trace(const mpe_ctx* ctx, hipStream_t st, const char* what, int r
   } while (0)
 
 static Counts counts_of(const Dim& d) { return counts_of(d.B, d.S, d.n, d.L, d.V, d.PV); }
+static bool small_batch(const mpe_ctx* ctx, size_t items) { return ctx->allow_par && items <= (size_t)ctx->par_items; }      // its composites fork
+static size_t ec_lanes_fit(const mpe_ctx* ctx) { return ctx->ec_lane_groups ? (size_t)ctx->cus * 4 * 64 * 2 / ctx->device_share : 0; }      // two waves per SIMD
 // assigns every state array (base == nullptr: only sizes)
 static size_t layout(mpe_gg20_session* s, char* base) {
   const Dim& d = s->d;
@@ -827,10 +834,10 @@ static size_t layout(mpe_gg20_session* s, char* base) {
   s->status = m.i(c.nPI * NR); s->sig_recid = m.i(c.nPI);
   // index tables and verdicts of the two verification rounds
   s->sub0_vi = m.i(c.nVI); s->ok_vi = m.f(c.nVI); s->sub4_pv = m.i(c.nPV); s->rdash_pv = m.i(c.nPV); s->ok_pv = m.f(c.nPV);
-  const bool small = s->ctx->allow_par && c.nVI <= (size_t)s->ctx->par_items;       // the batches whose composites fork
-  s->cinv_pre = small ? m.w(c.nVI * 128) : nullptr; s->cinv_ok_pre = small ? m.f(c.nVI) : nullptr;
-  s->ped_pre = m.w(c.nPI * 48);
-  s->pdl_bn = small ? m.w(c.nPP * 128) : nullptr; s->pdl_scratch = small ? m.w(modexp_nn_scratch_words(c.nPP)) : nullptr;
+  Ahead& a = s->ahead; const bool small = small_batch(s->ctx, c.nVI);
+  a.cinv = small ? m.w(c.nVI * 128) : nullptr; a.cinv_ok = small ? m.f(c.nVI) : nullptr;
+  a.ped = m.w(c.nPI * 48);
+  a.pdl_bn = small ? m.w(c.nPP * 128) : nullptr; a.pdl_scratch = small ? m.w(modexp_nn_scratch_words(c.nPP)) : nullptr;
   s->tmp_bytes = tmp_bytes_of(c);
   s->tmp = (char*)m.take(s->tmp_bytes);
   return m.off;
@@ -867,7 +874,7 @@ static int round_exit(mpe_gg20_session* s, int rc, const char* what) {
 // does round 1 run the ladders of its verifications and of its MessageBs in ONE launch (round1_merged_ladders)?  Round 0 asks too:
 // only then is the inversion of the ciphertexts in front of a ladder that everything waits for
 static bool round1_merges(const mpe_ctx* ctx, const Counts& c) {
-  const bool par = ctx->allow_par && (int)c.nVI <= ctx->par_items;
+  const bool par = small_batch(ctx, c.nVI);
   const size_t resident_groups = (size_t)ctx->cus * ctx->modexp_waves_per_cu * 16 / ctx->device_share;
   return ctx->merge_r1 && ctx->use_pair && ctx->use_multiexp && c.nVI > 0 && c.nMB > 0 && c.nVI + c.nMB < ((size_t)1 << 30) &&
          (!par || 4 * (c.nVI + c.nMB) > (size_t)ctx->merge_r1_quarters * resident_groups);
@@ -884,27 +891,58 @@ __global__ void ca_all_from_local_kernel(int S, int B, const uint32_t* __restric
 }
 static size_t ws_need_inversion_ahead(const mpe_paillier* pk, size_t nVI) { return nVI * (128 + 128 + 1) * 4 + modinv_ws_words(pk->ms_nn, (int)nVI) * 4 + 16384; }
 
+// ---- beta^N of the PDL proofs ahead of round 4 (struct Ahead).  May the ladders start?  Round 0 adds "the ciphertexts' event exists", round 2 ensure_aux
+static bool pdl_ahead_eligible(const mpe_gg20_session* s, const Counts& c) {
+  const mpe_ctx* ctx = s->ctx; const Ahead& a = s->ahead;
+  return a.lockstep && a.pdl_bn && ctx->use_prio && !ctx->no_pdl_ahead && ctx->use_pair && ctx->use_crt && ctx->use_pown && c.nPP > 0 && small_batch(ctx, c.nPP);
+}
+// queues on aux[1] (which the caller has made wait for its inputs), at wave priority 0, the first ladder or, with `finish`, what is left of the two.
+// The only place that moves the stage forward: a launch that fails leaves it where it was, so that ahead_drain still waits for the first ladder
+static int pdl_ahead_queue(mpe_gg20_session* s, const Counts& c, bool finish) {
+  mpe_ctx* ctx = s->ctx; const mpe_paillier* prv = s->K->prv; Ahead& a = s->ahead; hipStream_t sa = ctx->aux[1];
+  const int phase = !finish ? 1 : (a.pdl == PdlStage::first_queued ? 2 : 0);
+  const int keep = ctx->ladder_prio;
+  ctx->ladder_prio = 0;
+  const int rc = modexp_nn(ctx, prv, (int)c.nPP, sel_of(s->ix.kown_pp, prv->nkeys), rows(s->Z.pdl_beta, 64, nullptr, 64),
+                           tab_rows(prv->N, 64, s->ix.kown_pp, prv->nkeys), 64, true, a.pdl_bn, sa, true, a.pdl_scratch, phase);
+  ctx->ladder_prio = keep;
+  if (rc == MPE_OK && !finish) a.pdl = PdlStage::first_queued;
+  else if (rc == MPE_OK) { (void)hipEventRecord(ctx->ev_ahead, sa); a.pdl = PdlStage::ready; }
+  gg_trace(ctx, sa, finish ? "PDL beta^N, ahead" : "PDL beta^N, first ladder, ahead", rc);
+  return rc;
+}
+// round 4: beta^N and the event after which it may be read, or nothing; pdl_ahead_consumed once the proofs that read it are queued
+static Handed pdl_ahead_take(const mpe_gg20_session* s) { return s->ahead.pdl == PdlStage::ready ? Handed{s->ahead.pdl_bn, s->ctx->ev_ahead} : Handed{}; }
+static void pdl_ahead_consumed(mpe_gg20_session* s) { if (s->ahead.pdl == PdlStage::ready) s->ahead.pdl = PdlStage::idle; }
+// `st` waits for ladders that were started and never consumed (a failed round) before the memory they write is wiped or reused
+static void ahead_drain(mpe_gg20_session* s, hipStream_t st) {
+  mpe_ctx* ctx = s->ctx; Ahead& a = s->ahead;
+  if (a.pdl == PdlStage::idle) return;
+  if (a.pdl == PdlStage::first_queued) (void)hipEventRecord(ctx->ev_ahead, ctx->aux[1]);      // no event behind the first ladder yet
+  (void)hipStreamWaitEvent(st, ctx->ev_ahead, 0);
+  a.pdl = PdlStage::idle;
+}
+
 // ---- Round0::proceed (rounds.rs:68-104) ------------------------------------------------------------------------------
 static int round0(mpe_gg20_session* s, uint32_t* d_out, hipStream_t st) {
   int rc = round_enter(s, 0, nullptr, d_out, false, true);
   if (rc != MPE_OK) return rc;
-  mpe_ctx* ctx = s->ctx; const mpe_gg20_keys* K = s->K; const Dim& d = s->d; const Counts c = counts_of(d); const mpe_gg20_nonces& Z = s->Z;
+  mpe_ctx* ctx = s->ctx; const mpe_gg20_keys* K = s->K; const Dim& d = s->d; const Counts c = counts_of(d); const mpe_gg20_nonces& Z = s->Z; Ahead& a = s->ahead;
   const int n = d.n;
   (void)hipMemsetAsync(d_out, 0, c.nPI * (size_t)msg_words(d.S, n, 0) * 4, st);
   // (r0_kernel — k_i, g^gamma_i, the commitments: 0.9 ms of EC — is launched BEHIND the fork below: the x^N ladders of a small batch need
   //  the nonces only and start at once; the encryption's tail waits for k_i through an event)
   // small batches: the encryption of k_i runs beside the first half of the range proofs (the proofs need c only for their
   // transcript hash); both composites draw from ONE workspace reservation
-  const bool par = ctx->allow_par && (int)c.nAP <= ctx->par_items;
+  const bool par = small_batch(ctx, c.nAP);
   const size_t nXN = c.nPI + c.nAP;
   // (round 6) lock-step signing: the inversion of the ciphertexts that round 1's verifiers need (6.7 ms of dependent short launches at
   // 1 024 sessions, in front of the ladder the whole round waits for) starts HERE, on the forked stream behind the encryption, beside the
-  // tail of the range proofs (transcript hash, r^e, the linear responses: 4 ms on the caller's stream).  Same inputs, same kernels, same
-  // verdicts — round 1 finds them done.  Only where the message slab cannot change between the two rounds: mpe_gg20_sign.
+  // tail of the range proofs (transcript hash, r^e, the linear responses: 4 ms on the caller's stream).  Same inputs, kernels and verdicts.
   bool all_local_in_order = d.L == d.S;           // local slot l IS signer ordinal l (ca_all_from_local_kernel)
   for (int l = 0; l < d.L && all_local_in_order; ++l) all_local_in_order = d.loc[l] == l;
-  const bool ahead = par && s->lockstep && s->cinv_pre && all_local_in_order && !ctx->no_r1_inversion_ahead && round1_merges(ctx, c);
-  s->cinv_ahead = false;
+  const bool ahead = par && a.lockstep && a.cinv && all_local_in_order && !ctx->no_r1_inversion_ahead && round1_merges(ctx, c);
+  a.cinv_done = false;
   if (par && rc == MPE_OK) {
     rc = ws_reserve(ctx, ws_need_encrypt((int)c.nPI) + ws_need_alice_generate((int)c.nAP) + nXN * (64 + 128 + 1 + CRT_WS_WORDS) * 4 + 65536 +
                          (ahead ? ws_need_inversion_ahead(K->pub, c.nVI) : 0), st);
@@ -921,7 +959,7 @@ static int round0(mpe_gg20_session* s, uint32_t* d_out, hipStream_t st) {
   Fork g(ctx, st, 2, held, 2);
   GG_LAUNCH(r0_kernel, c.nPI, d, K->x, Z.k, Z.gamma, Z.blind, s->kq, s->gq, s->w, s->k64, s->g_gamma, s->com, STAT(0), BADR(0));
   if (g.on) (void)hipEventRecord(ctx->ev_fork[0], st);                             // "k_i is there" (waited for in front of the encryption's tail)
-  GG_LAUNCH(ped_ahead_kernel, c.nPI, d, Z.l, Z.ped_s1, Z.ped_s2, s->ped_pre);      // Round 2's nonce-only points, beside this round's ladders
+  GG_LAUNCH(ped_ahead_kernel, c.nPI, d, Z.l, Z.ped_s1, Z.ped_s2, a.ped);           // Round 2's nonce-only points, beside this round's ladders
   hipEvent_t xn_ready = nullptr;
   if (held && ctx->merge_xn) {
     hipStream_t sx = g.s(1);
@@ -956,9 +994,9 @@ static int round0(mpe_gg20_session* s, uint32_t* d_out, hipStream_t st) {
     uint32_t* cinv = q.modinv(K->pub->ms_nn, ksel, rows(cred, 128), ok);
     rc = q.rc;
     if (rc == MPE_OK) {
-      (void)hipMemcpyAsync(s->cinv_pre, cinv, c.nVI * 128 * 4, hipMemcpyDeviceToDevice, sx);
-      (void)hipMemcpyAsync(s->cinv_ok_pre, ok, c.nVI, hipMemcpyDeviceToDevice, sx);
-      s->cinv_ahead = true;
+      (void)hipMemcpyAsync(a.cinv, cinv, c.nVI * 128 * 4, hipMemcpyDeviceToDevice, sx);
+      (void)hipMemcpyAsync(a.cinv_ok, ok, c.nVI, hipMemcpyDeviceToDevice, sx);
+      a.cinv_done = true;
     }
     gg_trace(s->ctx, sx, "round 1's inversion, ahead", rc);
   }
@@ -968,24 +1006,10 @@ static int round0(mpe_gg20_session* s, uint32_t* d_out, hipStream_t st) {
   mpe_alice_nonces an{Z.al_alpha, Z.al_beta, Z.al_gamma, Z.al_rho};
   if (rc == MPE_OK)
     rc = alice_generate(ctx, K->prv, K->stm, (int)c.nAP, s->ix.kown_ap, s->ix.st_ap, rows(s->kq, 8, s->ix.pi_ap),
-                        rows(s->c_a, 128, s->ix.pi_ap), rows(Z.r_a, 64, s->ix.pi_ap), &an, &ap, st, &g, bn_pre, c_ready ? c_ready : xn_ready, c_ready);
+                        rows(s->c_a, 128, s->ix.pi_ap), rows(Z.r_a, 64, s->ix.pi_ap), &an, &ap, st, &g, Handed{bn_pre, c_ready ? c_ready : xn_ready}, c_ready);
   g.join();                                       // (again: with c_ready the proofs waited for the event only)
-  // ... and the FIRST of the two ladders behind the PDL proofs' beta^N (round 2 starts the rest, round 4 needs it): at priority 0 on the
-  // stream of the range proofs' shortest branch, from the moment the ciphertexts are there — the 5 ms before round 1's ladder in which
-  // the chip runs an inversion and a hash
-  s->pdl_phase1 = false;
-  if (rc == MPE_OK && c_ready && s->pdl_bn && ctx->use_prio && !ctx->no_pdl_ahead && ctx->use_pair && ctx->use_crt && ctx->use_pown && c.nPP > 0 &&
-      (int)c.nPP <= ctx->par_items) {
-    hipStream_t sa = ctx->aux[1];
-    (void)hipStreamWaitEvent(sa, c_ready, 0);
-    const int keep = ctx->ladder_prio;
-    ctx->ladder_prio = 0;
-    const int rca = modexp_nn(ctx, K->prv, (int)c.nPP, sel_of(s->ix.kown_pp, K->prv->nkeys), rows(Z.pdl_beta, 64, nullptr, 64),
-                              tab_rows(K->prv->N, 64, s->ix.kown_pp, K->prv->nkeys), 64, true, s->pdl_bn, sa, true, s->pdl_scratch, 1);
-    ctx->ladder_prio = keep;
-    if (rca == MPE_OK) s->pdl_phase1 = true; else rc = rca;
-    gg_trace(s->ctx, sa, "PDL beta^N, first ladder, ahead", rc);
-  }
+  // ... and the FIRST ladder of the PDL proofs' beta^N, once the ciphertexts are there: the 5 ms before round 1's ladder hold an inversion and a hash
+  if (rc == MPE_OK && c_ready && pdl_ahead_eligible(s, c)) { (void)hipStreamWaitEvent(ctx->aux[1], c_ready, 0); rc = pdl_ahead_queue(s, c, false); }
   if (held) ctx->ws_hold--;
   gg_trace(s->ctx, st, "alice_generate", rc);
   PACK(c.nAP, n, n + 1, 0, SUB0, M0A.z, ap.z); PACK(c.nAP, n, n + 1, 0, SUB0, M0A.e, ap.e); PACK(c.nAP, n, n + 1, 0, SUB0, M0A.s, ap.s);
@@ -1013,12 +1037,13 @@ static size_t ws_need_round1_merged(const mpe_paillier* pk, size_t nVI, size_t n
 static int round1_merged_ladders(mpe_ctx* ctx, const mpe_paillier* pk, size_t nVI, const int32_t* kpub_vi, Rows cipher_vi, Rows s_vi, Rows e_vi,
                                  size_t nMB, const int32_t* kpub_mb, Rows ca_mb, const uint32_t* bsel, const uint32_t* mb_r,
                                  const uint32_t** m_vi, const uint8_t** inv_ok_vi, const uint32_t** x_mb, hipStream_t st,
-                                 const uint32_t* cinv_pre = nullptr, const uint8_t* cinv_ok_pre = nullptr) {
+                                 Handed cinv_pre = {}, const uint8_t* cinv_ok_pre = nullptr) {
   const size_t n = nVI + nMB;
   Seq q{ctx, st, (int)nVI};
   const Rows ksel = sel_of(kpub_vi, pk->nkeys);
   const uint8_t* inv_ok = cinv_ok_pre;
-  const uint32_t* cinv = cinv_pre;
+  const uint32_t* cinv = cinv_pre.p;
+  cinv_pre.wait(st);
   if (!cinv_pre) {                                                                                         // (round 0 did it: round1_inversion_ahead)
     uint8_t* ok = q.flags();
     uint32_t* cred = q.modmul(pk->ms_nn, ksel, cipher_vi, rows(pk->ms_nn->one_words, 0, nullptr, 1));      // c mod N^2
@@ -1065,7 +1090,7 @@ static int round1(mpe_gg20_session* s, const uint32_t* d_in, const int64_t* h_of
   GG_LAUNCH(idx1_kernel, c.nVI, d, in0, sub0_vi);
   // small batches: the verification of the peers' range proofs and the construction of my MessageBs are independent
   // (the reference runs them back to back inside MessageB::b) — two streams, one workspace reservation
-  const bool par = ctx->allow_par && (int)c.nVI <= ctx->par_items;
+  const bool par = small_batch(ctx, c.nVI);
   // the ladders of both halves of the round in ONE launch (round1_merged_ladders): always for large batches, and for a small batch (par)
   // when its two ladder launches on forked streams would overfill the chip (more than 3/4 of the resident groups between them) — then
   // the longer one sets the pace and the merged launch wins although the inversion of c moves in front of it (2 048 sessions:
@@ -1073,8 +1098,8 @@ static int round1(mpe_gg20_session* s, const uint32_t* d_in, const int64_t* h_of
   // inversion (1 536 sessions: -1.4 %; 1 024: no change; 512: -7.5 %) — profiles/r05/ab_merge_small_batches.jsonl.  What remains of the two halves (the N~ side of the
   // verification, MessageB's encryption tail and DLog proofs) runs on forked streams behind the merged launch.
   const bool merged = round1_merges(ctx, c);
-  const bool ahead = merged && s->cinv_ahead;                 // round 0 inverted the ciphertexts already (lock-step signing of a small batch)
-  s->cinv_ahead = false;
+  const bool ahead = merged && s->ahead.cinv_done;            // round 0 inverted the ciphertexts already (lock-step signing of a small batch)
+  s->ahead.cinv_done = false;
   if (par && !merged && rc == MPE_OK) { rc = ws_reserve(ctx, ws_need_alice_verify((int)c.nVI) + ws_need_mul_add_enc((int)c.nMB), st); if (rc == MPE_OK) ctx->ws_hold++; }
   bool held = par && !merged && rc == MPE_OK;
   const uint32_t *m_vi = nullptr, *x_mb = nullptr;
@@ -1112,7 +1137,7 @@ static int round1(mpe_gg20_session* s, const uint32_t* d_in, const int64_t* h_of
     if (merged && rc == MPE_OK) {
       rc = round1_merged_ladders(ctx, K->pub, c.nVI, s->ix.kpub_vi, rows(s->ca_all, 128, s->ix.ca_vi), with_words(pr.s, 64), pr.e, c.nMB, s->ix.kpub_mb,
                                  rows(s->ca_all, 128, s->ix.ca_mb), bsel, Z.mb_r, &m_vi, &inv_ok_vi, &x_mb, st2,
-                                 ahead ? s->cinv_pre : nullptr, ahead ? s->cinv_ok_pre : nullptr);
+                                 ahead ? Handed{s->ahead.cinv} : Handed{}, ahead ? s->ahead.cinv_ok : nullptr);      // (joined to `st` by round 0)
       if (rc == MPE_OK && g.on) { (void)hipEventRecord(ctx->ev_mid, st2); m_ready = ctx->ev_mid; }
       gg_trace(s->ctx, st2, "round 1 merged ladders", rc);
     }
@@ -1123,7 +1148,7 @@ static int round1(mpe_gg20_session* s, const uint32_t* d_in, const int64_t* h_of
     if (!dlog_first) dlog_proofs(st2);
   }
   if (rc == MPE_OK)        // every range proof of every peer, for both MessageB::b calls (mta/mod.rs:119-131), read in place
-    rc = alice_verify(ctx, K->pub, K->stm, (int)c.nVI, s->ix.kpub_vi, s->ix.st_vi, rows(s->ca_all, 128, s->ix.ca_vi), pr, ok_vi, st, m_vi, inv_ok_vi, m_ready);
+    rc = alice_verify(ctx, K->pub, K->stm, (int)c.nVI, s->ix.kpub_vi, s->ix.st_vi, rows(s->ca_all, 128, s->ix.ca_vi), pr, ok_vi, st, Handed{m_vi, m_ready}, inv_ok_vi);
   gg_trace(s->ctx, st, "alice_verify", rc);
   g.join();
   if (held) ctx->ws_hold--;
@@ -1150,37 +1175,18 @@ static int round2(mpe_gg20_session* s, const uint32_t* d_in, const int64_t* h_of
   uint8_t* code = r2.code;
   Ped ped{s->pedT, r2.e, r2.a1, r2.a2, r2.z1, r2.z2};
   GG_LAUNCH(idx2_kernel, c.nMB, d, in1, sub1_rv);
-  const bool pdl_ahead = rc == MPE_OK && s->lockstep && s->pdl_bn && ctx->use_prio && !ctx->no_pdl_ahead && ctx->use_pair && ctx->use_crt &&
-                         ctx->use_pown && ctx->allow_par && (int)c.nPP <= ctx->par_items && c.nPP > 0 && ensure_aux(ctx);
-  if (pdl_ahead) {                                              // the auxiliary stream goes on from HERE: behind round 1, beside the decryption
-    (void)hipEventRecord(ctx->ev_fork[0], st);
-    (void)hipStreamWaitEvent(ctx->aux[1], ctx->ev_fork[0], 0);
-  }
+  const bool pdl_ahead = rc == MPE_OK && pdl_ahead_eligible(s, c) && ensure_aux(ctx);
+  // the auxiliary stream goes on from HERE: behind round 1, beside the decryption
+  if (pdl_ahead) { (void)hipEventRecord(ctx->ev_fork[0], st); (void)hipStreamWaitEvent(ctx->aux[1], ctx->ev_fork[0], 0); }
   if (rc == MPE_OK)      // Paillier::decrypt of the incoming c_b with my key (mta/mod.rs:165), in place
     rc = paillier_decrypt(ctx, K->prv, (int)c.nMB, s->ix.kown_mb, rows(d_in + M1.c.off, SUB1, sub1_rv), alpha_full, st);
   gg_trace(s->ctx, st, "decrypt", rc);
-  // (round 6) lock-step signing of a small batch: the two dependent 1024-bit ladders behind beta^N mod N^2 of round 4's PDL proofs
-  // (10 ms at 1 024 sessions, on that round's critical path) need nothing but the prover's nonce and key.  They start HERE on an auxiliary
-  // stream, at wave priority 0: the decryption ladder (2) and the EC kernels of rounds 2 and 3 (1) keep their speed whichever SIMD they
-  // share with them, and the chip — half empty during these 13 ms — does the work.  Round 4 waits for the event, not for the ladders.
-  s->pdl_ahead = false;
-  if (pdl_ahead && rc == MPE_OK) {
-    hipStream_t sa = ctx->aux[1];
-    const Rows ksel = sel_of(s->ix.kown_pp, K->prv->nkeys);
-    const int keep = ctx->ladder_prio;
-    ctx->ladder_prio = 0;
-    const int rca = modexp_nn(ctx, K->prv, (int)c.nPP, ksel, rows(Z.pdl_beta, 64, nullptr, 64), tab_rows(K->prv->N, 64, s->ix.kown_pp, K->prv->nkeys), 64,
-                              true, s->pdl_bn, sa, true, s->pdl_scratch, s->pdl_phase1 ? 2 : 0);
-    ctx->ladder_prio = keep;
-    s->pdl_phase1 = false;
-    if (rca == MPE_OK) { (void)hipEventRecord(ctx->ev_ahead, sa); s->pdl_ahead = true; } else rc = rca;
-    gg_trace(s->ctx, sa, "PDL beta^N, ahead", rc);
-  }
-  const size_t lanes_fit = ctx->ec_lane_groups ? (size_t)ctx->cus * 4 * 64 * 2 / ctx->device_share : 0;      // two waves per SIMD
-  if (c.nMB * 4 <= lanes_fit) GG_LAUNCH(r2a_group_kernel, c.nMB * 4, d, sub1_rv, d_in, alpha_full, s->kq, K->gw, alpha, s->bpk_in, code);
+  // (round 6) the rest of round 4's beta^N (10 ms at 1 024 sessions, off that round's critical path) starts HERE: the chip is half empty for 13 ms
+  if (pdl_ahead && rc == MPE_OK) rc = pdl_ahead_queue(s, c, true);
+  if (c.nMB * 4 <= ec_lanes_fit(ctx)) GG_LAUNCH(r2a_group_kernel, c.nMB * 4, d, sub1_rv, d_in, alpha_full, s->kq, K->gw, alpha, s->bpk_in, code);
   else GG_LAUNCH(r2a_kernel, c.nMB, d, sub1_rv, d_in, alpha_full, s->kq, K->gw, alpha, s->bpk_in, code);
   GG_LAUNCH(r2b_kernel, c.nPI, d, s->kq, s->gq, s->w, alpha, s->beta, code, Z.l, Z.ped_s1, Z.ped_s2, s->delta_i, s->sigma_i, s->lq, ped,
-            STAT(2), BADR(2), alpha_full, s->miu, s->fault_step, s->fault_mask, s->ped_pre);
+            STAT(2), BADR(2), alpha_full, s->miu, s->fault_step, s->fault_mask, s->ahead.ped);
   PACK(c.nPI, 1, 1, 0, W2, M2.delta, s->delta_i); PACK(c.nPI, 1, 1, 0, W2, M2.T, ped.T); PACK(c.nPI, 1, 1, 0, W2, M2.e, ped.e);
   PACK(c.nPI, 1, 1, 0, W2, M2.a1, ped.a1); PACK(c.nPI, 1, 1, 0, W2, M2.a2, ped.a2); PACK(c.nPI, 1, 1, 0, W2, M2.com, ped.T);
   PACK(c.nPI, 1, 1, 0, W2, M2.z1, ped.z1); PACK(c.nPI, 1, 1, 0, W2, M2.z2, ped.z2);
@@ -1196,9 +1202,8 @@ static int round3(mpe_gg20_session* s, const uint32_t* d_in, const int64_t* h_of
   (void)hipMemsetAsync(d_out, 0, c.nPI * (size_t)W3 * 4, st);
   GG_LAUNCH(validate_kernel, c.nPI, d, in2, 3, STAT(3), BADR(3));
   GG_LAUNCH(gather_field_kernel, c.SB * M2.T.words, in2, d.S, d.B, M2.T.off, M2.T.words, s->tvec);                 // t_vec
-  const size_t lanes_fit = ctx->ec_lane_groups ? (size_t)ctx->cus * 4 * 64 * 2 / ctx->device_share : 0;
   const int g3 = 2 * d.S <= 4 ? 4 : (2 * d.S <= 8 ? 8 : 16);
-  if (c.nPI * g3 <= lanes_fit) GG_LAUNCH(r3_group_kernel, c.nPI * g3, d, g3, in2, s->dinv, STAT(3), BADR(3));
+  if (c.nPI * g3 <= ec_lanes_fit(ctx)) GG_LAUNCH(r3_group_kernel, c.nPI * g3, d, g3, in2, s->dinv, STAT(3), BADR(3));
   else GG_LAUNCH(r3_kernel, c.nPI, d, in2, s->dinv, STAT(3), BADR(3));
   PACK(c.nPI, 1, 1, 0, W3, M3.blind, s->Z.blind); PACK(c.nPI, 1, 1, 0, W3, M3.g_gamma, s->g_gamma);          // SignDecommitPhase1
   return round_exit(s, rc, "gg20 round3");
@@ -1214,7 +1219,7 @@ static int round4(mpe_gg20_session* s, const uint32_t* d_in, const int64_t* h_of
   (void)hipMemsetAsync(d_out, 0, c.nPI * (size_t)msg_words(S, d.n, 4) * 4, st);
   GG_LAUNCH(validate_kernel, c.nPI, d, in3, 4, STAT(4), BADR(4));
   // small batches: R and R_dash (two dependent scalar multiplications) beside the Paillier / N~ half of the PDL proofs
-  Fork g(ctx, st, 2, ctx->allow_par && (int)c.nPP <= ctx->par_items, 2);
+  Fork g(ctx, st, 2, small_batch(ctx, c.nPP), 2);
   hipEvent_t R_ready = nullptr;
   if (rc == MPE_OK && c.nPI > 0) {
     hipLaunchKernelGGL(r4_kernel, dim3(blocks_for((int)c.nPI, 64)), dim3(64), 0, g.s(1), d, in3, s->dinv, s->com_all, s->bpk_in, s->kq, s->R, s->Rbar,
@@ -1231,9 +1236,9 @@ static int round4(mpe_gg20_session* s, const uint32_t* d_in, const int64_t* h_of
   if (rc == MPE_OK)                                                                                            // phase5_proof_pdl
     rc = pdl_prove(ctx, K->prv, K->stm, (int)c.nPP, s->ix.kown_pp, s->ix.st_pp, rows(s->c_a, 128, s->ix.pi_pp), rows(s->Rbar, 16, s->ix.pi_pp),
                    rows(s->R, 16, s->ix.pi_pp), rows(s->kq, 8, s->ix.pi_pp), rows(Z.r_a, 64, s->ix.pi_pp), &pn, &pp, st, &g,
-                   s->pdl_ahead ? s->pdl_bn : nullptr, s->pdl_ahead ? ctx->ev_ahead : nullptr, R_ready);
+                   pdl_ahead_take(s), R_ready);
   else g.join();
-  if (rc == MPE_OK) s->pdl_ahead = false;                    // consumed (otherwise session_release waits for it)
+  if (rc == MPE_OK) pdl_ahead_consumed(s);                   // (otherwise session_release waits for it)
   gg_trace(s->ctx, st, "pdl_prove", rc);
   PACK(c.nPP, P1, S, 0, SUB4, M4P.z, pp.z); PACK(c.nPP, P1, S, 0, SUB4, M4P.u1, pp.u1); PACK(c.nPP, P1, S, 0, SUB4, M4P.u2, pp.u2);
   PACK(c.nPP, P1, S, 0, SUB4, M4P.u3, pp.u3); PACK(c.nPP, P1, S, 0, SUB4, M4P.s1, pp.s1); PACK(c.nPP, P1, S, 0, SUB4, M4P.s2, pp.s2);
@@ -1256,7 +1261,7 @@ static int round5(mpe_gg20_session* s, const uint32_t* d_in, const int64_t* h_of
   const Round5Tmp r5 = Round5Tmp::carve(t, c);
   Heg heg{r5.S, r5.T, r5.A3, r5.z1, r5.z2};
   GG_LAUNCH(idx5_kernel, c.nPV, d, in4, sub4_pv, rdash_pv);
-  const bool par = ctx->allow_par && (int)c.nPV <= ctx->par_items;
+  const bool par = small_batch(ctx, c.nPV);
   PdlProofRows pr{rows(d_in + M4P.z.off, SUB4, sub4_pv), rows(d_in + M4P.u1.off, SUB4, sub4_pv), rows(d_in + M4P.u2.off, SUB4, sub4_pv),
                   rows(d_in + M4P.u3.off, SUB4, sub4_pv), rows(d_in + M4P.s1.off, SUB4, sub4_pv), rows(d_in + M4P.s2.off, SUB4, sub4_pv),
                   rows(d_in + M4P.s3.off, SUB4, sub4_pv)};
@@ -1281,9 +1286,8 @@ static int round6(mpe_gg20_session* s, const uint32_t* d_in, const int64_t* h_of
   mpe_ctx* ctx = s->ctx; const Dim& d = s->d; const Counts c = counts_of(d);
   const Slab in5 = slab_of(s, d_in, h_off, 5);
   GG_LAUNCH(validate_kernel, c.nPI, d, in5, 6, STAT(6), BADR(6));
-  const size_t lanes_fit = ctx->ec_lane_groups ? (size_t)ctx->cus * 4 * 64 * 2 / ctx->device_share : 0;
   const int g6 = 3 * d.S <= 8 ? 8 : (3 * d.S <= 16 ? 16 : 32);
-  if (c.nPI * g6 <= lanes_fit) GG_LAUNCH(r6_group_kernel, c.nPI * g6, d, g6, in5, s->R, s->tvec, s->K->y, STAT(6), BADR(6));
+  if (c.nPI * g6 <= ec_lanes_fit(ctx)) GG_LAUNCH(r6_group_kernel, c.nPI * g6, d, g6, in5, s->R, s->tvec, s->K->y, STAT(6), BADR(6));
   else GG_LAUNCH(r6_kernel, c.nPI, d, in5, s->R, s->tvec, s->K->y, STAT(6), BADR(6));
   return round_exit(s, rc, "gg20 round6");
 }
@@ -1307,14 +1311,22 @@ static int complete(mpe_gg20_session* s, const uint32_t* d_in, const int64_t* h_
   return round_exit(s, rc, "gg20 complete");
 }
 
+// the index tables: one launch over the largest item count (again at every re-arm: the key indices follow the key-set choice)
+static void launch_idx(mpe_gg20_session* s, hipStream_t st) {
+  const Counts c = counts_of(s->d);
+  size_t total = 0;
+  for (const size_t v : {c.nVI, c.nMB, c.nAP, c.nPV, c.nPI}) if (v > total) total = v;
+  hipLaunchKernelGGL(idx_kernel, dim3(blocks_for((int)total, 64)), dim3(64), 0, st, s->d, s->ix, (int)total);
+}
+// the state region after the index tables, everything nonce-derived: secrets of a batch do not outlive it
+static hipError_t wipe_batch_state(mpe_gg20_session* s, hipStream_t st) {
+  ahead_drain(s, st);
+  return hipMemsetAsync(s->kq, 0, (size_t)((char*)s->mem + s->mem_bytes - (char*)s->kq), st);
+}
+
 static void session_release(mpe_gg20_session* s, hipStream_t st) {
   if (!s) return;
-  if (s->pdl_ahead && s->ctx->ev_ahead) { (void)hipStreamWaitEvent(st, s->ctx->ev_ahead, 0); s->pdl_ahead = false; }    // started, never consumed (a failed round)
-  if (s->pdl_phase1 && s->ctx->ev_ahead && s->ctx->aux_ready) {                                                            // its first ladder may still run
-    (void)hipEventRecord(s->ctx->ev_ahead, s->ctx->aux[1]);
-    (void)hipStreamWaitEvent(st, s->ctx->ev_ahead, 0);
-    s->pdl_phase1 = false;
-  }
+  ahead_drain(s, st);
   if (s->mem) {
     // secrets (k_i, gamma_i, w_i, sigma_i, nonce-derived intermediates) do not outlive the object (range_proofs.rs:26-36 zeroizes)
     (void)hipMemsetAsync(s->mem, 0, s->mem_bytes, st);
@@ -1434,12 +1446,7 @@ int mpe_gg20_session_create(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, 
   const mpe::gg::Counts c = mpe::gg::counts_of(d);
   (void)hipMemsetAsync(s->status, 0, c.nPI * mpe::gg::NR * 4, st);
   (void)hipMemsetAsync(s->bad, 0, c.nPI * mpe::gg::NR * 4, st);
-  size_t total = c.nVI;
-  if (c.nMB > total) total = c.nMB;
-  if (c.nAP > total) total = c.nAP;
-  if (c.nPV > total) total = c.nPV;
-  if (c.nPI > total) total = c.nPI;
-  hipLaunchKernelGGL(mpe::gg::idx_kernel, dim3(mpe::blocks_for((int)total, 64)), dim3(64), 0, st, d, s->ix, (int)total);
+  mpe::gg::launch_idx(s, st);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) { mpe_set_error("gg20 idx_kernel", e); mpe::gg::session_release(s, st); return MPE_E_HIP; }
   *out = s;
@@ -1462,17 +1469,10 @@ int mpe_gg20_session_rearm(mpe_gg20_session* s, const int32_t* d_keyset, const m
   // The caller passes FRESHLY SAMPLED values for every batch (re-using k, gamma or a Paillier randomness leaks the key share);
   // the library cannot tell fresh from stale device arrays — the arrays may legitimately be the same buffers refilled.
   hipStream_t st = (hipStream_t)stream;
-  const mpe::gg::Counts c = mpe::gg::counts_of(s->d);
-  // the state region after the index tables: secrets of the previous batch do not outlive it
-  const hipError_t em = hipMemsetAsync(s->kq, 0, (size_t)((char*)s->mem + s->mem_bytes - (char*)s->kq), st);
+  const hipError_t em = mpe::gg::wipe_batch_state(s, st);
   if (em != hipSuccess) { mpe_set_error("gg20 session rearm (wipe)", em); return MPE_E_HIP; }
   s->Z = *nonces; s->d.ks = d_keyset; s->next_round = 0; s->failed = false; s->fault_step = 0; s->fault_mask = 0;
-  size_t total = c.nVI;                 // the key indices follow the (possibly different) key-set choice
-  if (c.nMB > total) total = c.nMB;
-  if (c.nAP > total) total = c.nAP;
-  if (c.nPV > total) total = c.nPV;
-  if (c.nPI > total) total = c.nPI;
-  hipLaunchKernelGGL(mpe::gg::idx_kernel, dim3(mpe::blocks_for((int)total, 64)), dim3(64), 0, st, s->d, s->ix, (int)total);
+  mpe::gg::launch_idx(s, st);           // the key indices follow the (possibly different) key-set choice
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) { mpe_set_error("gg20 session rearm", e); return MPE_E_HIP; }
   return MPE_OK;
@@ -1482,7 +1482,7 @@ int mpe_gg20_session_abort(mpe_gg20_session* s, void* stream) {
   // the caller gives the running batch up (it stopped after the offline stage, a peer vanished, a round call failed): everything
   // nonce-derived is wiped now and the object waits for mpe_gg20_session_rearm; the round entry points refuse until then
   if (!s) return MPE_E_ARG;
-  const hipError_t em = hipMemsetAsync(s->kq, 0, (size_t)((char*)s->mem + s->mem_bytes - (char*)s->kq), (hipStream_t)stream);
+  const hipError_t em = mpe::gg::wipe_batch_state(s, (hipStream_t)stream);
   if (em != hipSuccess) { mpe_set_error("gg20 session abort (wipe)", em); return MPE_E_HIP; }
   s->failed = true;
   s->next_round = 9;
@@ -1545,24 +1545,22 @@ int mpe_gg20_sign(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, const int3
   const int S = keys->S, n = keys->n;
   for (int i = 0; i < S; ++i) if (keys->own_slot[keys->signers[i]] < 0) { mpe_set_error_msg("mpe_gg20_sign needs every signer's secrets"); return MPE_E_ARG; }
   hipStream_t st = (hipStream_t)stream;
+  int maxw = 0;                                     // the widest message record
+  for (int r = 0; r < 8; ++r) { const int w = mpe::gg::msg_words(S, n, r); if (w > maxw) maxw = w; }
   if (chunk <= 0) {
     // 65 536 sessions per pass (the EC kernels want >= 2 waves per SIMD), fewer when the shape is wide: state, message
     // slabs and composite workspace per session grow like S (S-1) n; keep a pass under ~64 GB
     const size_t P = (size_t)S * (S - 1), V = dedup_verify ? 1 : 2, PV = dedup_verify ? 1 : S;
     const size_t nVI = P * V * n, nPV = PV * P;
-    int mw = 0;
-    for (int r = 0; r < 8; ++r) { const int w = mpe::gg::msg_words(S, n, r); if (w > mw) mw = w; }
     const size_t words = (size_t)S * 1200 + (size_t)S * n * 260 + nVI * 8 + P * 2 * 300 + P * 470 + nPV * 8 +      // state + round scratch
                          (nVI > nPV ? nVI : nPV) * 2300 + (size_t)S * n * 2100 +                                     // composite workspace
-                         2 * (size_t)S * mw;                                                                         // two message slabs
+                         2 * (size_t)S * maxw;                                                                       // two message slabs
     size_t fit = ((size_t)64 << 30) / (words * 4);
     fit = fit >= 1024 ? (fit / 1024) * 1024 : (fit ? fit : 1);
     chunk = (int)(fit < 65536 ? fit : 65536);
   }
   int32_t local[8];
   for (int i = 0; i < S; ++i) local[i] = i;
-  int maxw = 0;
-  for (int r = 0; r < 8; ++r) { const int w = mpe::gg::msg_words(S, n, r); if (w > maxw) maxw = w; }
   const int Bc = batch < chunk ? batch : chunk;
   // two message slabs alternate: round q writes slab q & 1 and reads the other
   size_t slab_off[7];
@@ -1596,7 +1594,7 @@ int mpe_gg20_sign(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, const int3
     mpe_gg20_session* s = nullptr;
     int rc = mpe_gg20_session_create(ctx, keys, B, S, local, d_keyset ? d_keyset + b0 : nullptr, &Z, dedup_verify, &s, stream);
     if (rc != MPE_OK) return rc;
-    s->lockstep = true;                           // the message slabs never leave the library between two rounds
+    s->ahead.lockstep = true;                       // the message slabs never leave the library between two rounds
     rc = mpe::gg::round0(s, M[0], st);
     if (rc == MPE_OK) rc = mpe::gg::round1(s, M[0], nullptr, M[1], st);
     if (rc == MPE_OK) rc = mpe::gg::round2(s, M[1], nullptr, M[2], st);

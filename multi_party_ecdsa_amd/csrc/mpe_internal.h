@@ -50,17 +50,16 @@ struct mpe_ctx {
   int grid_mode = 2;              // persistent_grid(): 0 = equal trips (rounds 1-4), 1 = full trips + tail, 2 = tail only when it fits one wave per SIMD (option grid = equal|full|hybrid)
   // window-table scratch, grown on demand: one buffer per stream slot (0 = the caller's stream, 1..3 = the auxiliary streams
   // on which small batches run independent launches concurrently)
-  void* tables[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // slot 0: the caller's stream, 1..3: the auxiliary streams
-  size_t tables_bytes[6] = {0, 0, 0, 0, 0, 0};
+  void* tables[4] = {nullptr, nullptr, nullptr, nullptr};
+  size_t tables_bytes[4] = {0, 0, 0, 0};
   // Small batches are latency-bound (a launch lasts as long as ONE exponentiation): independent parts of a proof / a round
   // run on auxiliary streams, forked from and joined to the caller's stream with events (mpe::Fork).
   hipStream_t aux[3] = {nullptr, nullptr, nullptr};
   hipEvent_t ev_fork[2] = {nullptr, nullptr}, ev_join[3] = {nullptr, nullptr, nullptr};
-  hipEvent_t ev_ahead = nullptr;  // "the PDL proofs' beta^N, started in round 2, is done" (mpe_gg20.h round2 / round4)
-  hipEvent_t ev_mid = nullptr;    // "the merged ladder launch of round 1 is queued" (mpe_gg20.h round1)
-  // background streams of the lock-step composition (small batches): the pure verifications of rounds 1 and 5 run there,
-  // each with its own workspace, and are joined when the signature is completed
-  bool aux_ready = false;
+  hipEvent_t ev_ahead = nullptr;  // "the PDL proofs' beta^N, started ahead of round 4, is done": owned by mpe_gg20.h pdl_ahead_* / ahead_drain
+  hipEvent_t ev_mid = nullptr;    // a forked branch's value is there although the branch goes on, one use at a time (mpe_gg20.h): round 0's merged
+                                  // x^N, then its ciphertexts; round 1's merged ladders; round 4's R
+  bool aux_ready = false;         // ensure_aux made the streams and events above
   bool allow_par = true;          // MPE_NO_PAR=1 switches the concurrency off (A/B runs)
   int par_items = 32768;          // composites fork when they have at most this many items
   // bump-allocated workspace for the intermediates of composite operations (Paillier, proofs)

@@ -1,5 +1,6 @@
 // libmpecdsa_hip.so — C-ABI (include/mpecdsa_hip.h) over the gfx950 kernels.  Single translation unit.
 #include <string.h>
+#include <array>
 #include <initializer_list>
 #include <mutex>
 #include "mpe_internal.h"
@@ -430,13 +431,20 @@ int mpe_ctx_create(mpe_ctx** out, int device) {
   return MPE_OK;
 }
 
+// every device buffer the context owns: first what mpe_ctx_wipe zeroes (window tables, workspace), then the session arena and the message slabs
+struct CtxBuf { void* p; size_t bytes; }; constexpr int CTX_SCRATCH = 5, CTX_BUFS = 7;
+static std::array<CtxBuf, CTX_BUFS> ctx_bufs(const mpe_ctx* ctx) {
+  return {{{ctx->tables[0], ctx->tables_bytes[0]}, {ctx->tables[1], ctx->tables_bytes[1]}, {ctx->tables[2], ctx->tables_bytes[2]},
+           {ctx->tables[3], ctx->tables_bytes[3]}, {ctx->ws, ctx->ws_bytes}, {ctx->sess_buf, ctx->sess_bytes}, {ctx->slab_buf, ctx->slab_bytes}}};
+}
+
 // Zeroes every scratch buffer the context owns (window tables, composite workspace): they hold powers of secret bases and
 // nonce-derived intermediates of the last calls (the reference zeroizes its round-1 secrets, range_proofs.rs:26-36,197-212).
 int mpe_ctx_wipe(mpe_ctx* ctx, void* stream) {
   if (!ctx) return MPE_E_ARG;
   hipStream_t st = (hipStream_t)stream;
-  for (int i = 0; i < 6; ++i) if (ctx->tables[i]) (void)hipMemsetAsync(ctx->tables[i], 0, ctx->tables_bytes[i], st);
-  if (ctx->ws) (void)hipMemsetAsync(ctx->ws, 0, ctx->ws_bytes, st);
+  const auto b = ctx_bufs(ctx);
+  for (int i = 0; i < CTX_SCRATCH; ++i) if (b[i].p) (void)hipMemsetAsync(b[i].p, 0, b[i].bytes, st);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) { mpe_set_error("mpe_ctx_wipe", e); return MPE_E_HIP; }
   return MPE_OK;
@@ -458,15 +466,12 @@ int mpe_ctx_scratch_audit(mpe_ctx* ctx, uint64_t* nonzero_words, uint64_t* total
   hipError_t e = hipMalloc((void**)&d, 8);
   if (e != hipSuccess) { mpe_set_error("hipMalloc(audit)", e); return MPE_E_NOMEM; }
   (void)hipMemsetAsync(d, 0, 8, st);
-  const void* ptrs[11] = {ctx->tables[0], ctx->tables[1], ctx->tables[2], ctx->tables[3], ctx->tables[4], ctx->tables[5], ctx->ws,
-                          nullptr, nullptr, ctx->sess_buf, ctx->slab_buf};
-  const size_t bytes[11] = {ctx->tables_bytes[0], ctx->tables_bytes[1], ctx->tables_bytes[2], ctx->tables_bytes[3], ctx->tables_bytes[4],
-                            ctx->tables_bytes[5], ctx->ws_bytes, 0, 0, ctx->sess_bytes, ctx->slab_bytes};
+  const auto b = ctx_bufs(ctx);
   uint64_t tot = 0;
-  for (int i = 0; i < 11; ++i) {
-    if (!ptrs[i] || !bytes[i]) continue;
-    tot += bytes[i];
-    hipLaunchKernelGGL(count_nonzero_kernel, dim3(4096), dim3(256), 0, st, (const uint32_t*)ptrs[i], bytes[i] / 4, d);
+  for (int i = 0; i < CTX_BUFS; ++i) {
+    if (!b[i].p || !b[i].bytes) continue;
+    tot += b[i].bytes;
+    hipLaunchKernelGGL(count_nonzero_kernel, dim3(4096), dim3(256), 0, st, (const uint32_t*)b[i].p, b[i].bytes / 4, d);
   }
   unsigned long long h = 0;
   e = hipMemcpyAsync(&h, d, 8, hipMemcpyDeviceToHost, st);
@@ -481,13 +486,10 @@ int mpe_ctx_scratch_audit(mpe_ctx* ctx, uint64_t* nonzero_words, uint64_t* total
 int mpe_ctx_destroy(mpe_ctx* ctx) {
   if (!ctx) return MPE_E_ARG;
   (void)mpe_ctx_wipe(ctx, nullptr);
-  if (ctx->sess_buf) { (void)hipMemsetAsync(ctx->sess_buf, 0, ctx->sess_bytes, nullptr); }
-  if (ctx->slab_buf) { (void)hipMemsetAsync(ctx->slab_buf, 0, ctx->slab_bytes, nullptr); }
+  const auto b = ctx_bufs(ctx);
+  for (int i = CTX_SCRATCH; i < CTX_BUFS; ++i) if (b[i].p) (void)hipMemsetAsync(b[i].p, 0, b[i].bytes, nullptr);
   (void)hipDeviceSynchronize();
-  if (ctx->sess_buf) (void)hipFree(ctx->sess_buf);
-  if (ctx->slab_buf) (void)hipFree(ctx->slab_buf);
-  for (int i = 0; i < 6; ++i) if (ctx->tables[i]) (void)hipFree(ctx->tables[i]);
-  if (ctx->ws) (void)hipFree(ctx->ws);
+  for (int i = 0; i < CTX_BUFS; ++i) if (b[i].p) (void)hipFree(b[i].p);
   if (ctx->aux_ready) {
     for (int i = 0; i < 3; ++i) { (void)hipStreamDestroy(ctx->aux[i]); (void)hipEventDestroy(ctx->ev_join[i]); }
     for (int i = 0; i < 2; ++i) (void)hipEventDestroy(ctx->ev_fork[i]);

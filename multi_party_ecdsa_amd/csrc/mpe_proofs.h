@@ -307,6 +307,12 @@ static PdlProofRows dense(const mpe_pdl_proof* p) {
                       rows(p->s3, 89)};
 }
 static Rows with_words(Rows r, int words) { r.words = words; return r; }
+// A value the caller hands to a composite instead of letting it compute the value itself: the device pointer and the event after which
+// it may be read.  No event: the value is already ordered on the reader's stream.  No pointer: nothing is handed over.
+struct Handed {
+  const uint32_t* p = nullptr; hipEvent_t ready = nullptr; explicit operator bool() const { return p != nullptr; }
+  void wait(hipStream_t st) const { if (p && ready) (void)hipStreamWaitEvent(st, ready, 0); }
+};
 
 // ---------------------------------------------------------------------------------------------
 // AliceProof::generate   (range_proofs.rs:160-193; rounds :39-67 and :78-90)
@@ -320,12 +326,8 @@ static int merge_rc(const Seq& a, const Seq& b, const Seq& c) { return a.rc != M
 static int alice_generate(mpe_ctx* ctx, const mpe_paillier* pk, const mpe_statements* stm, int B, const int32_t* key_idx,
                           const int32_t* st_idx, Rows a, Rows cipher, Rows r,
                           const mpe_alice_nonces* nn, const mpe_alice_proof* out, hipStream_t st, Fork* outer = nullptr,
-                          const uint32_t* bn_pre = nullptr, hipEvent_t bn_pre_ready = nullptr,        // bn_pre: beta^N mod N^2 when the caller
-                          hipEvent_t cipher_ready = nullptr) {                                        // already has it (or has queued it
-                                                                                                      // elsewhere: bn_pre_ready);
-                                                                                                      // cipher_ready: the outer branch goes on
-                                                                                                      // with other work — wait for this event
-                                                                                                      // instead of joining it
+                          Handed bn_pre = {}, hipEvent_t cipher_ready = nullptr) {
+  // bn_pre: beta^N mod N^2 from the caller; cipher_ready: the outer branch goes on with other work — wait for this event instead of joining it
   MPE_TRY(ws_reserve(ctx, ws_need_alice_generate(B), st));
   Fork f(ctx, st, 3, B <= ctx->par_items);
   Seq q{ctx, f.s(0), B}, q1{ctx, f.s(1), B}, q2{ctx, f.s(2), B};
@@ -339,8 +341,8 @@ static int alice_generate(mpe_ctx* ctx, const mpe_paillier* pk, const mpe_statem
   // u = (alpha N + 1) beta^N mod N^2                                            :53-55
   uint32_t* gu = q.words(128);
   q.muladd(rows(nn->alpha, 24), 24, Nrow, 64, no_rows(), 0, gu, 128);
-  if (bn_pre && bn_pre_ready) (void)hipStreamWaitEvent(f.s(0), bn_pre_ready, 0);
-  const uint32_t* bn = bn_pre ? bn_pre : q.modexp_nn(pk, ksel, rows(nn->beta, 64, nullptr, 64), Nrow, 64, true, true);   // the prover owns the key
+  bn_pre.wait(f.s(0));
+  const uint32_t* bn = bn_pre ? bn_pre.p : q.modexp_nn(pk, ksel, rows(nn->beta, 64, nullptr, 64), Nrow, 64, true, true);   // the prover owns the key
   uint32_t* u = q.modmul(pk->ms_nn, ksel, rows(gu, 128), rows(bn, 128));
   // w = h1^alpha h2^gamma mod N~                                                :56-57
   uint32_t* w1 = q2.fb_modexp(stm, ssel, 0, h1,rows(nn->alpha, 24), 24);
@@ -367,12 +369,10 @@ static int alice_generate(mpe_ctx* ctx, const mpe_paillier* pk, const mpe_statem
 // ---------------------------------------------------------------------------------------------
 // AliceProof::verify   (range_proofs.rs:105-156).  Small batches: the N~ side and the N^2 side on separate streams.
 // ---------------------------------------------------------------------------------------------
-// m_pre / inv_ok_pre: the caller already holds m = s^N (c^-1)^e mod N^2 and the verdict of the inversion of c (Round 1 computes the
-// ladders of its verifications and of its MessageBs in ONE launch, mpe_gg20.h round1_merged_ladders)
+// m_pre / inv_ok_pre: the caller's m = s^N (c^-1)^e mod N^2 and verdict of the inversion of c (mpe_gg20.h round1_merged_ladders: ONE launch)
 static int alice_verify(mpe_ctx* ctx, const mpe_paillier* pk, const mpe_statements* stm, int B, const int32_t* key_idx,
                         const int32_t* st_idx, Rows cipher, const AliceProofRows& pr, uint8_t* ok, hipStream_t st,
-                        const uint32_t* m_pre = nullptr, const uint8_t* inv_ok_pre = nullptr, hipEvent_t m_pre_ready = nullptr) {
-  // m_pre: s^N (c^-1)^e already computed (or queued on another stream: then m_pre_ready says when) by the caller's merged ladder launch
+                        Handed m_pre = {}, const uint8_t* inv_ok_pre = nullptr) {
   MPE_TRY(ws_reserve(ctx, ws_need_alice_verify(B), st));
   Fork f(ctx, st, 3, B <= ctx->par_items);          // (with m_pre the N^2 side is one multiplication: the two N~ branches still fork)
   Seq q{ctx, f.s(0), B}, q1{ctx, f.s(1), B}, q2{ctx, f.s(2), B};
@@ -393,8 +393,8 @@ static int alice_verify(mpe_ctx* ctx, const mpe_paillier* pk, const mpe_statemen
   uint32_t *u = nullptr, *b12 = nullptr, *cie = nullptr;
   if (m_pre) {
     inv_ok2 = const_cast<uint8_t*>(inv_ok_pre);
-    if (m_pre_ready) (void)hipStreamWaitEvent(f.s(0), m_pre_ready, 0);
-    u = q.modmul(pk->ms_nn, ksel, rows(gs1, 128), rows(m_pre, 128));
+    m_pre.wait(f.s(0));
+    u = q.modmul(pk->ms_nn, ksel, rows(gs1, 128), rows(m_pre.p, 128));
   } else if (f.on) {
     // small batch (latency-bound): the 2048-bit ladder s^N starts at once; the inversion of c and the short ladder
     // (c^-1)^e run beside it on the stream of the fixed-base side, and one more multiplication joins them
@@ -437,10 +437,10 @@ static int alice_verify(mpe_ctx* ctx, const mpe_paillier* pk, const mpe_statemen
 // ---------------------------------------------------------------------------------------------
 static int pdl_prove(mpe_ctx* ctx, const mpe_paillier* pk, const mpe_statements* stm, int B, const int32_t* key_idx,
                      const int32_t* st_idx, Rows cipher, Rows Qp, Rows Gp, Rows x, Rows r, const mpe_pdl_nonces* nn,
-                     const mpe_pdl_proof* out, hipStream_t st, Fork* outer = nullptr, const uint32_t* bn_pre = nullptr,
-                     hipEvent_t bn_pre_ready = nullptr, hipEvent_t G_ready = nullptr) {      // G_ready: G is there although branch 1 goes on
+                     const mpe_pdl_proof* out, hipStream_t st, Fork* outer = nullptr, Handed bn_pre = {},
+                     hipEvent_t G_ready = nullptr) {                                         // G_ready: G is there although branch 1 goes on
   // outer: a fork of the CALLER whose branch 1 produces the statement points Q, G concurrently (Round 4: R, R_dash); only u1
-  // and the transcript hash need them.  bn_pre: beta^N mod N^2 when the caller has queued it elsewhere (done at bn_pre_ready)
+  // and the transcript hash need them.  bn_pre: beta^N mod N^2 when the caller has queued it elsewhere
   MPE_TRY(ws_reserve(ctx, (size_t)B * (1400 + CRT_WS_WORDS + MODEXP_N_HOLDER_WS_WORDS) * 4 + 65536, st));
   Fork f(ctx, st, 3, B <= ctx->par_items);
   Seq q{ctx, f.s(0), B}, q1{ctx, f.s(1), B}, q2{ctx, f.s(2), B};
@@ -458,8 +458,8 @@ static int pdl_prove(mpe_ctx* ctx, const mpe_paillier* pk, const mpe_statements*
   // u2 = (N+1)^alpha beta^N mod N^2; (N+1)^alpha = 1 + alpha N (mod N^2), alpha N + 1 < N^2      :87-93
   uint32_t* ga = q.words(128);
   q.muladd(rows(nn->alpha, 24), 24, Nrow, 64, no_rows(), 0, ga, 128);
-  if (bn_pre && bn_pre_ready) (void)hipStreamWaitEvent(f.s(0), bn_pre_ready, 0);
-  const uint32_t* bn = bn_pre ? bn_pre : q.modexp_nn(pk, ksel, rows(nn->beta, 64, nullptr, 64), Nrow, 64, true, true);   // the prover owns the key
+  bn_pre.wait(f.s(0));
+  const uint32_t* bn = bn_pre ? bn_pre.p : q.modexp_nn(pk, ksel, rows(nn->beta, 64, nullptr, 64), Nrow, 64, true, true);   // the prover owns the key
   q.modmul_to(pk->ms_nn, ksel, rows(ga, 128), rows(bn, 128), out->u2);
   // u3 = h1^alpha h2^gamma mod N~                                               :94-100
   uint32_t* w1 = q2.fb_modexp(stm, ssel, 0, h1,rows(nn->alpha, 24), 24);
