@@ -1,6 +1,9 @@
 """GPU parity tests of the Lindell'17 signing entry points (mpe_lindell_partial_sig / mpe_lindell_sign) against the
 GMP oracle: byte-identical c3 and (r, s, recid) on seeded inputs with edge messages, ECDSA verification of the result
-under the joint public key, and a ragged batch with per-item keys."""
+under the joint public key, and a ragged batch with per-item keys.
+Every R1 / R2 here is an honest point.  The invalid ones (neutral, off-curve, twist, coordinate >= p, x + p) and the fail-closed outputs
+they must produce — c3 = Enc(0; r), no signature — are in tests/test_hostile_gpu.py (test_lindell_partial_sig_fails_closed_on_invalid_R1,
+test_lindell_sign_fails_closed_on_invalid_R2), on the rows of tests/hostile_cases.py."""
 import numpy as np
 import pytest
 import torch
