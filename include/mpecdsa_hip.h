@@ -821,6 +821,92 @@ int mpe_scalar_mul(mpe_ctx* ctx, int batch, const uint32_t* d_a, const uint32_t*
 int mpe_lindell_ntilde_generate(mpe_ctx* ctx, int count, const uint8_t* h_seed32, uint64_t counter, int max_attempts, uint32_t* d_Nt,
                                 uint32_t* d_h1, uint32_t* d_h2, uint32_t* d_xhi, int32_t* d_fail, void* stream);
 
+/* ---- GG18 signing (src/protocols/multi_party_ecdsa/gg_2018/party_i.rs:384-737, examples/gg18_sign_client.rs) ------------------ */
+/* The calls of the reference's ten signing rounds that are not already one call of this header.  Those that are stay that call:
+ *   phase1_broadcast (:408-424)                  mpe_hash_commit_point(g_gamma_i, blind)
+ *   MessageA::a(k_i, ek, &[]) (client :111)      mpe_paillier_encrypt of k_i zero-extended to [64] words, under the sender's key
+ *   verify_proofs_get_alpha (client :226-232)    mpe_mta_verify_get_alpha
+ * Conventions.  S <= 8 signers: h_signers [S], HOST array of party indices, ascending; the parties this process plays: h_local
+ * [n_local], HOST array of signer ordinals (positions in h_signers), ascending.  Points are [16] words, scalars, commitments and blind
+ * factors [8], ciphertexts [128].  Sampled values are inputs; scalars are reduced mod q as read.
+ *   broadcast values   sender-major [S][batch][w], own value included
+ *   local values       [n_local][batch][w] — with every signer local an output array is the next phase's input array as it stands
+ *   per-peer values    [n_local][S-1][batch][w]; peer slot jj of signer ordinal i is ordinal jj (jj < i) or jj + 1
+ *   per-session        d_msg [batch][8], d_y [batch][16], d_pk_vec [batch][n][16]
+ * d_status [n_local][batch] int32 is written by mpe_gg18_sign_keys and carried through the other calls: the FIRST failure of a
+ * (session, party) wins, in the reference's evaluation order, and it sticks; no call stops the batch for one bad item.  A party whose
+ * status is not 0 when a call starts, or becomes so inside it, gets all-zero words as that call's outputs (a zero point is no valid
+ * point: its peers refuse it with the code of the phase in which they read it).  Every incoming point is checked (on the curve,
+ * canonical, not neutral) before a secret is multiplied into it; one that fails refuses the item with the code of its phase.
+ *    91  k_i / gamma_i is not a value Scalar::random() returns (zero or >= q)                       party_i.rs:396,402
+ *   201  verify_proofs_get_alpha -> InvalidKey                                                      gg_2018/test.rs:265,272
+ *   202  the peer's w-side b_proof.pk differs from THAT PEER's g_w entry: the check the comment at   gg_2018/test.rs:274-277
+ *        test.rs:274-277 describes (the assert at :278 compares with the receiver's own g_w_i, which is the sender's only with two
+ *        signers); gg18_sign_client.rs:235-241 compares as this call does
+ *   301  the sum of the deltas is zero (the reference panics: expect("sum of deltas is zero"))      party_i.rs:451
+ *   401  phase4 -> InvalidKey                                                                       party_i.rs:481
+ *   402  R is the point at infinity (the reference panics: R.x_coord().unwrap())                    party_i.rs:496-497
+ *   531  phase5c -> InvalidCom                                                                      party_i.rs:634
+ *   541  phase5d -> InvalidCom                                                                      party_i.rs:671
+ *   542  phase5d -> InvalidKey                                                                      party_i.rs:668
+ *   601  output_signature -> InvalidSig                                                             party_i.rs:709 */
+/* `SignKeys::create` (:385-406) with k_i, gamma_i handed in.  d_x_i, d_k_i, d_gamma_i [n_local][batch][8] ->
+ * d_w_i = lambda_i x_i (lambda_i = map_share_to_new_params(params, index, s)), d_g_w_i = w_i G, d_g_gamma_i = gamma_i G, and d_g_w
+ * [S][batch][16] = lambda_j pk_vec[s_j] of every signer (a pk_vec entry that is no valid point leaves a zero row).  Writes d_status:
+ * 0, or 91 with zero outputs. */
+int mpe_gg18_sign_keys(mpe_ctx* ctx, int t, int n, int S, const int32_t* h_signers, int n_local, const int32_t* h_local, int batch,
+                       const uint32_t* d_x_i, const uint32_t* d_pk_vec, const uint32_t* d_k_i, const uint32_t* d_gamma_i, uint32_t* d_w_i,
+                       uint32_t* d_g_w_i, uint32_t* d_g_gamma_i, uint32_t* d_g_w, int32_t* d_status, void* stream);
+/* `MessageB::b_with_predefined_randomness(b, ek, m_a, r, beta_tag, &[])` (mta/mod.rs:111-158) with an empty statement set: no range
+ * proof is read or checked; everything else is mpe_mta_message_b (flat items, d_key_idx selects Alice's key, same words out). */
+int mpe_gg18_message_b(mpe_ctx* ctx, const mpe_paillier* pk, int batch, const int32_t* d_key_idx, const uint32_t* d_b, const uint32_t* d_ca,
+                       const uint32_t* d_r, const uint32_t* d_beta_tag, const uint32_t* d_nonce_b, const uint32_t* d_nonce_bt, uint32_t* d_cb,
+                       uint32_t* d_beta, const mpe_dlog_proof* b_proof, const mpe_dlog_proof* beta_tag_proof, void* stream);
+/* The verdicts of the 2 (S-1) mpe_mta_verify_get_alpha calls in the order of gg18_sign_client.rs:221-244 (per peer: gamma side, w side
+ * -> 201; w-side pk == d_g_w of that peer -> 202), then `phase2_delta_i` and `phase2_sigma_i` (:426-444).  Per-peer inputs: d_alpha,
+ * d_beta (gamma side: the alphas received, the betas kept), d_miu, d_ni (w side) [..][8], d_ok_gamma, d_ok_w uint8, d_w_pk [..][16]. */
+int mpe_gg18_phase2(mpe_ctx* ctx, int S, const int32_t* h_signers, int n_local, const int32_t* h_local, int batch, const uint32_t* d_k_i,
+                    const uint32_t* d_gamma_i, const uint32_t* d_w_i, const uint32_t* d_alpha, const uint32_t* d_beta, const uint32_t* d_miu,
+                    const uint32_t* d_ni, const uint8_t* d_ok_gamma, const uint8_t* d_ok_w, const uint32_t* d_w_pk, const uint32_t* d_g_w,
+                    uint32_t* d_delta_i, uint32_t* d_sigma_i, int32_t* d_status, void* stream);
+/* `phase3_reconstruct_delta` and `phase4` (:446-483) as gg18_sign_client.rs:272-309 uses them.  d_delta, d_g_gamma, d_blind, d_com:
+ * broadcast; d_b_pk: per-peer, the gamma-side b_proof.pk received.  301 when the deltas sum to zero; 401 unless every PEER's
+ * b_proof.pk == g_gamma_i and Com(g_gamma_i; blind) == com (the own decommitment is only added); d_R = delta^-1 sum g_gamma_i, 402
+ * when that is the neutral point. */
+int mpe_gg18_phase4(mpe_ctx* ctx, int S, const int32_t* h_signers, int n_local, const int32_t* h_local, int batch, const uint32_t* d_delta,
+                    const uint32_t* d_b_pk, const uint32_t* d_g_gamma, const uint32_t* d_blind, const uint32_t* d_com, uint32_t* d_R,
+                    int32_t* d_status, void* stream);
+/* `phase5_local_sig` and `phase5a_broadcast_5b_zkproof` (:487-559) with l_i, rho_i, the blind factor, the HomoElGamal nonces s1, s2 and
+ * the DLog nonce handed in.  d_s_i = m k_i + r sigma_i stays with the caller; V_i = s_i R + l_i G, A_i = rho_i G, B_i = l_i rho_i G;
+ * d_com = Com(Sha256(chain_points([V, A, B])) as a BigInt; blind), the digest NOT reduced mod q and hashed by the rule of
+ * mpe_hash_commit_bigint; heg = HomoELGamalProof::prove(witness {r: l_i, x: s_i}, statement (G: A_i, H: R, Y: g, D: V_i, E: B_i)) as
+ * mpe_heg_prove; dlog = DLogProof::prove(rho_i) as mpe_dlog_prove.  d_status is only read. */
+int mpe_gg18_phase5a(mpe_ctx* ctx, int S, const int32_t* h_signers, int n_local, const int32_t* h_local, int batch, const uint32_t* d_k_i,
+                     const uint32_t* d_sigma_i, const uint32_t* d_msg, const uint32_t* d_R, const uint32_t* d_l_i, const uint32_t* d_rho_i,
+                     const uint32_t* d_blind, const uint32_t* d_s1, const uint32_t* d_s2, const uint32_t* d_nonce, uint32_t* d_s_i, uint32_t* d_V,
+                     uint32_t* d_A, uint32_t* d_B, uint32_t* d_com, const mpe_heg_proof* heg, const mpe_dlog_proof* dlog, const int32_t* d_status,
+                     void* stream);
+/* what every signer broadcast in 5A and 5B, each array [S][batch][..]: Phase5ADecom1 {V_i, A_i, B_i, blind_factor}, Phase5Com1 {com},
+ * the HomoELGamalProof (T, A3, z1, z2) and the DLogProof of rho_i */
+typedef struct { const uint32_t *V, *A, *B, *blind, *com, *T, *A3, *z1, *z2, *dlog_pk, *dlog_R, *dlog_z; } mpe_gg18_phase5b_msgs;
+/* `phase5c` (:561-636) per local party over its PEERS' entries of `in` (aligned as gg18_sign_client.rs:381-401): 531 unless every
+ * commitment opens, every HomoELGamalProof verifies over (A_j, R, g, V_j, B_j) and every DLogProof verifies.  d_u = rho_i (sum of
+ * every V - m G - r y), d_t = l_i (sum of the PEERS' A), d_com2 = Com(Sha256(chain_points([u_i, t_i])) as a BigInt; blind2). */
+int mpe_gg18_phase5c(mpe_ctx* ctx, int S, const int32_t* h_signers, int n_local, const int32_t* h_local, int batch, const uint32_t* d_msg,
+                     const uint32_t* d_y, const uint32_t* d_R, const uint32_t* d_l_i, const uint32_t* d_rho_i, const uint32_t* d_blind2,
+                     const mpe_gg18_phase5b_msgs* in, uint32_t* d_u, uint32_t* d_t, uint32_t* d_com2, int32_t* d_status, void* stream);
+/* `phase5d` (:638-673) over all S decommitments of 5D (d_u, d_t, d_blind2 against d_com2) and the B_i of 5A: 541 unless every
+ * commitment opens, then 542 unless g + sum t_i + sum B_i - sum u_i == g. */
+int mpe_gg18_phase5d(mpe_ctx* ctx, int S, const int32_t* h_signers, int n_local, const int32_t* h_local, int batch, const uint32_t* d_u,
+                     const uint32_t* d_t, const uint32_t* d_blind2, const uint32_t* d_com2, const uint32_t* d_B, int32_t* d_status, void* stream);
+/* `output_signature` with its `verify` (:674-737): s = d_s_own + the peers' rows of d_s_all (broadcast; the own row is not read),
+ * r = R.x mod q, recid = R.y & 1; s > q - s: s = q - s, recid ^= 1.  verify accepts iff s != 0 and ((m s^-1) G + (r s^-1) y).x mod q
+ * == r — no low-s rule (mpe_ecdsa_verify is Lindell's, another rule).  601 otherwise.  d_r, d_s [n_local][batch][8], d_recid
+ * [n_local][batch]: zero unless the status is 0. */
+int mpe_gg18_output_signature(mpe_ctx* ctx, int S, const int32_t* h_signers, int n_local, const int32_t* h_local, int batch,
+                              const uint32_t* d_s_own, const uint32_t* d_s_all, const uint32_t* d_R, const uint32_t* d_msg, const uint32_t* d_y,
+                              uint32_t* d_r, uint32_t* d_s, int32_t* d_recid, int32_t* d_status, void* stream);
+
 /* Kernel geometry chosen for the last launch (for bench.py's roofline accounting). */
 typedef struct {
   int waves;              /* workgroups (= waves) launched */

@@ -87,6 +87,7 @@ Blame6In = _ptr_struct("Blame6In", ["k", "k_rand", "miu", "miu_rand", "a1", "a2"
 Blame7In = _ptr_struct("Blame7In", ["s", "r", "R_dash", "m", "R", "S"])
 EcddhStatement = _ptr_struct("EcddhStatement", ["g1", "h1", "g2", "h2"])
 EcddhProof = _ptr_struct("EcddhProof", ["a1", "a2", "z"])
+Gg18Phase5bMsgs = _ptr_struct("Gg18Phase5bMsgs", ["V", "A", "B", "blind", "com", "T", "A3", "z1", "z2", "dlog_pk", "dlog_R", "dlog_z"])
 
 
 def _load():
@@ -96,6 +97,7 @@ def _load():
             "(hipcc --offload-arch=gfx950). There is no CPU fallback for the HIP path.")
     lib = C.CDLL(LIB_PATH)
     vp, ip, u32p, i32p = C.c_void_p, C.c_int, C.c_void_p, C.c_void_p
+    g18 = [ip, C.POINTER(C.c_int32), ip, C.POINTER(C.c_int32), ip]
     sig = {
         "mpe_version": (C.c_char_p, []),
         "mpe_last_error": (C.c_char_p, []),
@@ -251,6 +253,15 @@ def _load():
         "mpe_ecdsa_verify": (ip, [vp, ip, u32p, u32p, u32p, u32p, vp, vp]),
         "mpe_lindell_ntilde_generate": (ip, [vp, ip, C.c_char_p, C.c_uint64, ip, u32p, u32p, u32p, u32p, i32p, vp]),
         "mpe_gg20_sample_nonces": (ip, [vp, vp, ip, ip, C.POINTER(C.c_int32), i32p, C.c_char_p, C.c_uint64, C.POINTER(Gg20Nonces), i32p, vp]),
+        # GG18 signing: (ctx, S, h_signers, n_local, h_local, batch, ...) in front of every phase call
+        "mpe_gg18_sign_keys": (ip, [vp, ip, ip] + g18 + [u32p] * 8 + [i32p, vp]),
+        "mpe_gg18_message_b": (ip, [vp, vp, ip, i32p] + [u32p] * 8 + [C.POINTER(DlogProof), C.POINTER(DlogProof), vp]),
+        "mpe_gg18_phase2": (ip, [vp] + g18 + [u32p] * 7 + [vp, vp] + [u32p] * 4 + [i32p, vp]),
+        "mpe_gg18_phase4": (ip, [vp] + g18 + [u32p] * 6 + [i32p, vp]),
+        "mpe_gg18_phase5a": (ip, [vp] + g18 + [u32p] * 15 + [C.POINTER(HegProof), C.POINTER(DlogProof), i32p, vp]),
+        "mpe_gg18_phase5c": (ip, [vp] + g18 + [u32p] * 6 + [C.POINTER(Gg18Phase5bMsgs)] + [u32p] * 3 + [i32p, vp]),
+        "mpe_gg18_phase5d": (ip, [vp] + g18 + [u32p] * 5 + [i32p, vp]),
+        "mpe_gg18_output_signature": (ip, [vp] + g18 + [u32p] * 7 + [i32p, i32p, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -292,7 +303,9 @@ EXPORTED = ["mpe_version", "mpe_last_error", "mpe_ctx_create", "mpe_ctx_destroy"
             "mpe_is_probable_prime", "mpe_sample_prime", "mpe_paillier_keygen", "mpe_ntilde_generate",
             "mpe_vss_share", "mpe_keygen_construct_keypair", "mpe_keygen_verify_round3",
             "mpe_hash_commit_bigint", "mpe_lindell_keygen_first_msg", "mpe_lindell_keygen_verify_first_msg", "mpe_lindell_eph_first_msg",
-            "mpe_lindell_eph_verify_first_msg", "mpe_ecdsa_verify", "mpe_scalar_mul", "mpe_lindell_ntilde_generate"]
+            "mpe_lindell_eph_verify_first_msg", "mpe_ecdsa_verify", "mpe_scalar_mul", "mpe_lindell_ntilde_generate",
+            "mpe_gg18_sign_keys", "mpe_gg18_message_b", "mpe_gg18_phase2", "mpe_gg18_phase4", "mpe_gg18_phase5a", "mpe_gg18_phase5c",
+            "mpe_gg18_phase5d", "mpe_gg18_output_signature"]
 
 
 def check(rc, what):

@@ -274,6 +274,7 @@ static int launch_pair_modexp(mpe_ctx* ctx, const mpe_pairset* ps, int batch, Ro
 #include "mpe_primes.h"
 #include "mpe_lindell.h"
 #include "mpe_lindell_keygen.h"
+#include "mpe_gg18.h"
 
 extern "C" {
 

@@ -57,6 +57,21 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC mta_alpha_kernel(int B, ec::Enc
   ok[i] = good ? 1 : 0;
 }
 
+// MessageB::b_with_predefined_randomness behind its range-proof stage (:132-148), what mpe_mta_message_b and the bare form
+// mpe_gg18_message_b (`&[]`, mpe_gg18.h) share.  btq: [batch][8] scratch of the caller (beta_tag mod q, the witness of the second proof).
+static int mta_message_b_tail(mpe_ctx* ctx, const mpe_paillier* pk, int batch, const int32_t* d_key_idx, const uint32_t* d_b, const uint32_t* d_ca,
+                              const uint32_t* d_r, const uint32_t* d_beta_tag, const uint32_t* d_nonce_b, const uint32_t* d_nonce_bt, uint32_t* btq,
+                              uint32_t* d_cb, uint32_t* d_beta, const mpe_dlog_proof* b_proof, const mpe_dlog_proof* beta_tag_proof, hipStream_t st) {
+  // c_b = (b * c_a) + Enc(beta_tag; r)   (:133-145);  beta = -beta_tag mod q   (:146)
+  MPE_TRY(paillier_mul_add_enc(ctx, pk, batch, d_key_idx, rows(d_ca, 128), rows(d_b, 8), 8, d_beta_tag, d_r, d_cb,
+                               st));                                                           // Alice's key, Bob computes
+  MPE_LAUNCH_1D(mta_beta_kernel, batch, st, batch, d_beta_tag, btq, d_beta);
+  // DLogProof::prove(b), DLogProof::prove(beta_tag_fe)   (:147-148)
+  MPE_LAUNCH_1D(dlog_prove_kernel, batch, st, batch, ctx->enc, d_b, d_nonce_b, b_proof->pk, b_proof->R, b_proof->z);
+  MPE_LAUNCH_1D(dlog_prove_kernel, batch, st, batch, ctx->enc, btq, d_nonce_bt, beta_tag_proof->pk, beta_tag_proof->R, beta_tag_proof->z);
+  return MPE_OK;
+}
+
 }  // namespace mpe
 
 extern "C" {
@@ -112,14 +127,7 @@ int mpe_mta_message_b(mpe_ctx* ctx, const mpe_paillier* pk, const mpe_statements
   // verify Alice's range proofs against every statement   (:119-131); any failure -> Err(InvalidKey) -> ok = 0
   MPE_TRY(mpe::alice_verify(ctx, pk, stm, total, key_it, st_of, mpe::rows(d_ca, 128, b_of), mpe::dense(range_proofs), ok_items, st));
   MPE_LAUNCH_1D(mpe::mta_all_kernel, batch, st, batch, nst, ok_items, d_ok);
-  // c_b = (b * c_a) + Enc(beta_tag; r)   (:133-145);  beta = -beta_tag mod q   (:146)
-  MPE_TRY(mpe::paillier_mul_add_enc(ctx, pk, batch, d_key_idx, mpe::rows(d_ca, 128), mpe::rows(d_b, 8), 8, d_beta_tag, d_r, d_cb,
-                                    st));                                                      // Alice's key, Bob computes
-  MPE_LAUNCH_1D(mpe::mta_beta_kernel, batch, st, batch, d_beta_tag, btq, d_beta);
-  // DLogProof::prove(b), DLogProof::prove(beta_tag_fe)   (:147-148)
-  MPE_LAUNCH_1D(mpe::dlog_prove_kernel, batch, st, batch, ctx->enc, d_b, d_nonce_b, b_proof->pk, b_proof->R, b_proof->z);
-  MPE_LAUNCH_1D(mpe::dlog_prove_kernel, batch, st, batch, ctx->enc, btq, d_nonce_bt, beta_tag_proof->pk, beta_tag_proof->R, beta_tag_proof->z);
-  return MPE_OK;
+  return mpe::mta_message_b_tail(ctx, pk, batch, d_key_idx, d_b, d_ca, d_r, d_beta_tag, d_nonce_b, d_nonce_bt, btq, d_cb, d_beta, b_proof, beta_tag_proof, st);
 }
 
 int mpe_mta_verify_get_alpha(mpe_ctx* ctx, const mpe_paillier* sk, int batch, const int32_t* d_key_idx, const uint32_t* d_cb,

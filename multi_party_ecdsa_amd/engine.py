@@ -1465,3 +1465,284 @@ def lindell_rotate(ctx, wallet, d_factor, seed, counter, d_factor2=None, materia
         out["Q2"] = ec_mul(ctx, d_factor2, wallet["Q2"])
     ctx.sync()
     return out
+
+
+# ================================================================================================
+# GG18 threshold signing (mpe_gg18.h; gg_2018/party_i.rs:384-737, examples/gg18_sign_client.rs)
+# ================================================================================================
+def _g18_dims(signers, local):
+    sg = (C.c_int32 * len(signers))(*[int(s) for s in signers])
+    lc = (C.c_int32 * len(local))(*[int(x) for x in local])
+    return len(signers), sg, len(local), lc
+
+
+def gg18_sign_keys(ctx, t, n, signers, local, d_x_i, d_pk_vec, d_k_i, d_gamma_i):
+    """`SignKeys::create`: x_i, k_i, gamma_i [L,B,8], pk_vec [B,n,16] -> dict w_i [L,B,8], g_w_i, g_gamma_i [L,B,16], g_w [S,B,16], status [L,B]"""
+    L, B = d_k_i.shape[0], d_k_i.shape[1]
+    S = len(signers)
+    o = dict(w_i=_new(ctx, L * B, 8).reshape(L, B, 8), g_w_i=_new(ctx, L * B, 16).reshape(L, B, 16), g_gamma_i=_new(ctx, L * B, 16).reshape(L, B, 16),
+             g_w=_new(ctx, S * B, 16).reshape(S, B, 16), status=torch.zeros((L, B), dtype=torch.int32, device=ctx.device))
+    N_.check(N_.lib.mpe_gg18_sign_keys(ctx.h, t, n, *_g18_dims(signers, local), B, _ptr(d_x_i), _ptr(d_pk_vec), _ptr(d_k_i), _ptr(d_gamma_i), _ptr(o["w_i"]),
+                                       _ptr(o["g_w_i"]), _ptr(o["g_gamma_i"]), _ptr(o["g_w"]), _ptr(o["status"]), ctx.stream()), "mpe_gg18_sign_keys")
+    return o
+
+
+def gg18_message_b(ctx, pk, d_b, d_ca, d_r, d_beta_tag, d_nonce_b, d_nonce_bt, d_key_idx=None):
+    """`MessageB::b_with_predefined_randomness(.., &[])`, flat items: returns dict(c, beta, b_proof, beta_tag_proof)"""
+    B = d_b.shape[0]
+    out = dict(c=_new(ctx, B, 128), beta=_new(ctx, B, 8), b_proof=dict(pk=_new(ctx, B, 16), R=_new(ctx, B, 16), z=_new(ctx, B, 8)),
+               beta_tag_proof=dict(pk=_new(ctx, B, 16), R=_new(ctx, B, 16), z=_new(ctx, B, 8)))
+    p1, p2 = _struct(N_.DlogProof, out["b_proof"]), _struct(N_.DlogProof, out["beta_tag_proof"])
+    N_.check(N_.lib.mpe_gg18_message_b(ctx.h, pk.h, B, _ptr(d_key_idx), _ptr(d_b), _ptr(d_ca), _ptr(d_r), _ptr(d_beta_tag), _ptr(d_nonce_b), _ptr(d_nonce_bt),
+                                       _ptr(out["c"]), _ptr(out["beta"]), C.byref(p1), C.byref(p2), ctx.stream()), "mpe_gg18_message_b")
+    return out
+
+
+def gg18_phase2(ctx, signers, local, d_k_i, d_gamma_i, d_w_i, d_alpha, d_beta, d_miu, d_ni, d_ok_gamma, d_ok_w, d_w_pk, d_g_w, d_status):
+    """the alpha verdicts (201 / 202), `phase2_delta_i`, `phase2_sigma_i`: per-peer inputs [L,S-1,B,..] -> (delta_i, sigma_i) [L,B,8]"""
+    L, B = d_k_i.shape[0], d_k_i.shape[1]
+    delta, sigma = _new(ctx, L * B, 8).reshape(L, B, 8), _new(ctx, L * B, 8).reshape(L, B, 8)
+    N_.check(N_.lib.mpe_gg18_phase2(ctx.h, *_g18_dims(signers, local), B, _ptr(d_k_i), _ptr(d_gamma_i), _ptr(d_w_i), _ptr(d_alpha), _ptr(d_beta), _ptr(d_miu),
+                                    _ptr(d_ni), _ptr(d_ok_gamma), _ptr(d_ok_w), _ptr(d_w_pk), _ptr(d_g_w), _ptr(delta), _ptr(sigma), _ptr(d_status),
+                                    ctx.stream()), "mpe_gg18_phase2")
+    return delta, sigma
+
+
+def gg18_phase4(ctx, signers, local, d_delta, d_b_pk, d_g_gamma, d_blind, d_com, d_status):
+    """`phase3_reconstruct_delta` + `phase4` + the own g_gamma_i: broadcast [S,B,..], b_pk [L,S-1,B,16] -> R [L,B,16]"""
+    L, B = d_status.shape
+    R = _new(ctx, L * B, 16).reshape(L, B, 16)
+    N_.check(N_.lib.mpe_gg18_phase4(ctx.h, *_g18_dims(signers, local), B, _ptr(d_delta), _ptr(d_b_pk), _ptr(d_g_gamma), _ptr(d_blind), _ptr(d_com), _ptr(R),
+                                    _ptr(d_status), ctx.stream()), "mpe_gg18_phase4")
+    return R
+
+
+def gg18_phase5a(ctx, signers, local, d_k_i, d_sigma_i, d_msg, d_R, d_l_i, d_rho_i, d_blind, d_s1, d_s2, d_nonce, d_status):
+    """`phase5_local_sig` + `phase5a_broadcast_5b_zkproof`: dict s_i, V, A, B, com, heg{T, A3, z1, z2}, dlog{pk, R, z}, all [L,B,..]"""
+    L, B = d_status.shape
+    new = lambda w: _new(ctx, L * B, w).reshape(L, B, w)
+    o = dict(s_i=new(8), V=new(16), A=new(16), B=new(16), com=new(8), heg=dict(T=new(16), A3=new(16), z1=new(8), z2=new(8)),
+             dlog=dict(pk=new(16), R=new(16), z=new(8)))
+    hp, dp = _struct(N_.HegProof, o["heg"]), _struct(N_.DlogProof, o["dlog"])
+    N_.check(N_.lib.mpe_gg18_phase5a(ctx.h, *_g18_dims(signers, local), B, _ptr(d_k_i), _ptr(d_sigma_i), _ptr(d_msg), _ptr(d_R), _ptr(d_l_i), _ptr(d_rho_i),
+                                     _ptr(d_blind), _ptr(d_s1), _ptr(d_s2), _ptr(d_nonce), _ptr(o["s_i"]), _ptr(o["V"]), _ptr(o["A"]), _ptr(o["B"]),
+                                     _ptr(o["com"]), C.byref(hp), C.byref(dp), _ptr(d_status), ctx.stream()), "mpe_gg18_phase5a")
+    return o
+
+
+GG18_PHASE5B_FIELDS = ("V", "A", "B", "blind", "com", "T", "A3", "z1", "z2", "dlog_pk", "dlog_R", "dlog_z")
+
+
+def gg18_phase5c(ctx, signers, local, d_msg, d_y, d_R, d_l_i, d_rho_i, d_blind2, bc, d_status):
+    """`phase5c`: bc = dict GG18_PHASE5B_FIELDS of broadcast arrays [S,B,..] -> (u, t [L,B,16], com2 [L,B,8])"""
+    L, B = d_status.shape
+    u, t, com2 = _new(ctx, L * B, 16).reshape(L, B, 16), _new(ctx, L * B, 16).reshape(L, B, 16), _new(ctx, L * B, 8).reshape(L, B, 8)
+    st = _struct(N_.Gg18Phase5bMsgs, bc)
+    N_.check(N_.lib.mpe_gg18_phase5c(ctx.h, *_g18_dims(signers, local), B, _ptr(d_msg), _ptr(d_y), _ptr(d_R), _ptr(d_l_i), _ptr(d_rho_i), _ptr(d_blind2),
+                                     C.byref(st), _ptr(u), _ptr(t), _ptr(com2), _ptr(d_status), ctx.stream()), "mpe_gg18_phase5c")
+    return u, t, com2
+
+
+def gg18_phase5d(ctx, signers, local, d_u, d_t, d_blind2, d_com2, d_B, d_status):
+    """`phase5d` over the broadcast arrays [S,B,..]: writes 541 / 542 into d_status"""
+    B = d_status.shape[1]
+    N_.check(N_.lib.mpe_gg18_phase5d(ctx.h, *_g18_dims(signers, local), B, _ptr(d_u), _ptr(d_t), _ptr(d_blind2), _ptr(d_com2), _ptr(d_B), _ptr(d_status),
+                                     ctx.stream()), "mpe_gg18_phase5d")
+
+
+def gg18_output_signature(ctx, signers, local, d_s_own, d_s_all, d_R, d_msg, d_y, d_status):
+    """`output_signature`: s_own, R [L,B,..], s_all [S,B,8] -> (r, s [L,B,8], recid [L,B]); zero unless the status is 0"""
+    L, B = d_status.shape
+    r, s = _new(ctx, L * B, 8).reshape(L, B, 8), _new(ctx, L * B, 8).reshape(L, B, 8)
+    recid = torch.zeros((L, B), dtype=torch.int32, device=ctx.device)
+    N_.check(N_.lib.mpe_gg18_output_signature(ctx.h, *_g18_dims(signers, local), B, _ptr(d_s_own), _ptr(d_s_all), _ptr(d_R), _ptr(d_msg), _ptr(d_y), _ptr(r),
+                                              _ptr(s), _ptr(recid), _ptr(d_status), ctx.stream()), "mpe_gg18_output_signature")
+    return r, s, recid
+
+
+class Gg18Wallet:
+    """What GG18 signing reads of a `LocalKey`, resident in HBM, in the shape Gg20Keys takes it: arrays = dict of numpy uint32 arrays over
+    ALL n parties: x [n,8], p, q [n,32], X [n,16] (pk_vec), y [1,16], optionally N [n,64] (else p q).  own: the party indices whose
+    secrets (x, p, q) this object gets (default all); the other parties' rows of x, p, q never leave the host."""
+
+    def __init__(self, ctx, t, n, arrays, own=None):
+        self.ctx, self.t, self.n = ctx, t, n
+        self.own = list(range(n)) if own is None else sorted(int(a) for a in own)
+        a = {f: np.ascontiguousarray(arrays[f]) for f in ("x", "p", "q", "X", "y")}
+        if arrays.get("N") is not None:
+            Nw = np.ascontiguousarray(arrays["N"])
+        else:
+            Nw = ints_to_words([p_ * q_ for p_, q_ in zip(words_to_ints(a["p"]), words_to_ints(a["q"]))], 64)
+        up = lambda v: torch.from_numpy(np.ascontiguousarray(v).view(np.int32)).to(ctx.device)
+        self.x, self.X, self.y, self.N = up(a["x"][self.own]), up(a["X"][:n]), up(a["y"][:1]), up(Nw[:n])
+        self.pk = PaillierKeys(ctx, N=words_to_ints(Nw[:n]))                        # every party's public key
+        self.sk = PaillierKeys(ctx, p=up(a["p"][self.own]), q=up(a["q"][self.own]))  # the own ones, in the order of `own`
+
+    def close(self):
+        self.pk.close()
+        self.sk.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# stream fields of gg18_sign (field f draws stream counter | f << 56; 0..21 are mpe_gg20_sample_nonces', 0..15 the keygen chains',
+# 16..37 LINDELL_FIELDS; DESIGN.md §13)
+GG18_FIELDS = dict(k=40, gamma=41, blind=42, r_a=43, mb_beta_tag=44, mb_r=45, mb_nonce_b=46, mb_nonce_bt=47, l=48, rho=49, blind5a=50, heg_s1=51,
+                   heg_s2=52, dlog_nonce=53, blind5c=54)
+# messages of the nine broadcast / P2P rounds of gg18_sign_client.rs: field -> (round, words); every array is sender-major [S, B, w], the
+# MessageB fields [S, S-1, 2, B, w] (peer slot, then 0 = gamma side / 1 = w side)
+GG18_MSG_FIELDS = dict(com=(1, 8), c_a=(1, 128), mb_c=(2, 128), mb_b_pk=(2, 16), mb_b_R=(2, 16), mb_b_z=(2, 8), mb_bt_pk=(2, 16), mb_bt_R=(2, 16),
+                       mb_bt_z=(2, 8), delta=(3, 8), blind=(4, 8), g_gamma=(4, 16), com5a=(5, 8), V=(6, 16), A=(6, 16), B=(6, 16), blind5a=(6, 8),
+                       heg_T=(6, 16), heg_A3=(6, 16), heg_z1=(6, 8), heg_z2=(6, 8), dlog_pk=(6, 16), dlog_R=(6, 16), dlog_z=(6, 8), com5c=(7, 8),
+                       u=(8, 16), t=(8, 16), blind5c=(8, 8), s_i=(9, 8))
+
+
+def gg18_draw_shapes(S, L, B):
+    """shape of every field of `draws`: per local party [L, B, w]; the MessageB fields [2, L, S-1, B, w] (side, party, peer slot)"""
+    one = lambda w: (L, B, w)
+    mb = lambda w: (2, L, S - 1, B, w)
+    return dict(k=one(8), gamma=one(8), blind=one(8), r_a=one(64), mb_beta_tag=mb(64), mb_r=mb(64), mb_nonce_b=mb(8), mb_nonce_bt=mb(8), l=one(8),
+                rho=one(8), blind5a=one(8), heg_s1=one(8), heg_s2=one(8), dlog_nonce=one(8), blind5c=one(8))
+
+
+def gg18_sign(ctx, wallet, signers, d_msg, B, seed=None, counter=0, draws=None, local=None, _fault=None):
+    """The ten rounds of examples/gg18_sign_client.rs for B sessions in lock step, one call per phase over all of its items:
+    SignKeys | com + MessageA | MessageB x 2 per peer | alphas + delta_i / sigma_i | phase 4 | 5A | 5B | 5C | 5D | s_i + output.
+      wallet:  Gg18Wallet; signers: party indices, ascending; d_msg: device [B,8] (the hashed messages); local: signer ordinals played
+               here (default all).
+      draws:   None = every value the reference takes from OsRng is drawn by the device sampler from (seed, counter): stream
+               counter | GG18_FIELDS[f] << 56, rules sample_scalar, sample_bits(256) for the blind factors, sample_below(N_peer) for the
+               Paillier randomness and beta_tag (N_own for r_a); or a dict of arrays gg18_draw_shapes that replaces the sampler.
+      _fault:  a test aid, not part of the interface: _fault(round, msgs) is called when the messages of round 1..9 are in `msgs`
+               (GG18_MSG_FIELDS, sender-major device tensors; msgs["draws"] is the draws dict) and may edit them in place — a peer's
+               rows when `local` is a subset, a tampered value otherwise.
+    Every party reads every broadcast value, its own included, from `msgs`; a party that has failed sends zero words from then on.
+    Returns a dict: status [B, L] (include/mpecdsa_hip.h lists the codes), r, s [B,8], recid [B] of the first local party and
+    r_all, s_all [L,B,8], recid_all [L,B], R [L,B,16], draws, msgs, failures (sampler give-ups).  No secret is copied to the host."""
+    signers = [int(s) for s in signers]
+    S, n = len(signers), wallet.n
+    local = list(range(S)) if local is None else [int(x) for x in local]
+    L, P1, dev_ = len(local), S - 1, ctx.device
+    if counter >> 56:
+        raise ValueError("counter < 2^56")
+    own_pos = [wallet.own.index(signers[i]) for i in local]                    # rows of wallet.x / keys of wallet.sk
+    ind = [[jj if jj < i else jj + 1 for jj in range(P1)] for i in local]       # peer ordinal of (local party, slot)
+    jme = [[(i if i < ind[li][jj] else i - 1) for jj in range(P1)] for li, i in enumerate(local)]      # my slot at that peer
+    it = lambda v: torch.tensor(v, dtype=torch.int64, device=dev_)
+    i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=dev_)
+    t_loc, t_ind, t_jme = it(local), it(ind), it(jme)
+    key_own = i32(own_pos).reshape(L, 1).expand(L, B).contiguous()                                      # [L,B] key of wallet.sk
+    key_peer = i32([[signers[j] for j in row] for row in ind]).reshape(1, L, P1, 1).expand(2, L, P1, B).contiguous()   # key of wallet.pk
+    fails = []
+    if draws is None:
+        sid = lambda f: int(counter) | (GG18_FIELDS[f] << 56)
+        draws = {}
+
+        def scalar(f, shape):
+            v, fl = sample_scalar(ctx, int(np.prod(shape[:-1])), seed, sid(f))
+            fails.append(fl)
+            return v.reshape(shape)
+        for f, shape in gg18_draw_shapes(S, L, B).items():
+            rows = int(np.prod(shape[:-1]))
+            if f in ("blind", "blind5a", "blind5c"):
+                draws[f] = sample_bits(ctx, rows, seed, sid(f), 256, 8).reshape(shape)
+            elif f == "r_a":                                                   # Randomness of MessageA::a: below the own N   mta/mod.rs:57
+                own_N = i32([signers[i] for i in local]).reshape(L, 1).expand(L, B).contiguous()
+                v, fl = sample_below(ctx, rows, seed, sid(f), wallet.N, 64, own_N.reshape(-1))
+                fails.append(fl)
+                draws[f] = v.reshape(shape)
+            elif f in ("mb_beta_tag", "mb_r"):                                 # below the PEER's N                           mta/mod.rs:97-98
+                v, fl = sample_below(ctx, rows, seed, sid(f), wallet.N, 64, key_peer.reshape(-1))
+                fails.append(fl)
+                draws[f] = v.reshape(shape)
+            else:
+                draws[f] = scalar(f, shape)
+    else:
+        shapes = gg18_draw_shapes(S, L, B)
+        draws = {f: (v if torch.is_tensor(v) else _dev_u32(np.ascontiguousarray(v, dtype=np.uint32), dev_)).reshape(shapes[f]).contiguous()
+                 for f, v in draws.items()}
+    z = draws
+    msgs = {f: torch.zeros((S, B, w) if not f.startswith("mb_") else (S, P1, 2, B, w), dtype=torch.int32, device=dev_)
+            for f, (_, w) in GG18_MSG_FIELDS.items()}
+    msgs["draws"] = draws
+    hook = (lambda rnd: _fault(rnd, msgs)) if _fault is not None else (lambda rnd: None)
+
+    def put(name, val, status):
+        """the local parties' rows of a broadcast field; a failed party sends zero words"""
+        alive = (status == 0).reshape(status.shape + (1,) * (val.dim() - 2)).to(val.dtype)
+        msgs[name][t_loc] = val * alive
+
+    y = wallet.y.expand(B, 16).contiguous()
+    pk_vec = wallet.X.reshape(1, n, 16).expand(B, n, 16).contiguous()
+    x_i = wallet.x[it(own_pos)].reshape(L, 1, 8).expand(L, B, 8).contiguous()
+    # SignKeys::create (client :101-106)
+    sk_ = gg18_sign_keys(ctx, wallet.t, n, signers, local, x_i, pk_vec, z["k"], z["gamma"])
+    status, w_i, g_w = sk_["status"], sk_["w_i"], sk_["g_w"]
+    # round 1: phase1_broadcast + MessageA::a(k_i, ek, &[]) (client :110-119)
+    com = hash_commit_point(ctx, sk_["g_gamma_i"].reshape(L * B, 16), z["blind"].reshape(L * B, 8)).reshape(L, B, 8)
+    c_a = wallet.sk.encrypt_device(_widen(z["k"].reshape(L * B, 8), 64), z["r_a"].reshape(L * B, 64), key_own.reshape(-1)).reshape(L, B, 128)
+    put("com", com, status)
+    put("c_a", c_a, status)
+    hook(1)
+    # round 2: MessageB::b(gamma_i | w_i, ek_peer, m_a_peer, &[]) toward every peer, ONE launch (client :151-195); items [2, L, S-1, B]
+    nMB = 2 * L * P1 * B
+    b_sel = torch.stack([z["gamma"], w_i]).reshape(2, L, 1, B, 8).expand(2, L, P1, B, 8).contiguous()
+    ca_peer = msgs["c_a"][t_ind].reshape(1, L, P1, B, 128).expand(2, L, P1, B, 128).contiguous()
+    mb = gg18_message_b(ctx, wallet.pk, b_sel.reshape(nMB, 8), ca_peer.reshape(nMB, 128), z["mb_r"].reshape(nMB, 64), z["mb_beta_tag"].reshape(nMB, 64),
+                        z["mb_nonce_b"].reshape(nMB, 8), z["mb_nonce_bt"].reshape(nMB, 8), key_peer.reshape(-1))
+    beta = mb["beta"].reshape(2, L, P1, B, 8)
+    st_mb = status.reshape(L, 1, 1, B)
+    for name, val in (("mb_c", mb["c"]), ("mb_b_pk", mb["b_proof"]["pk"]), ("mb_b_R", mb["b_proof"]["R"]), ("mb_b_z", mb["b_proof"]["z"]),
+                      ("mb_bt_pk", mb["beta_tag_proof"]["pk"]), ("mb_bt_R", mb["beta_tag_proof"]["R"]), ("mb_bt_z", mb["beta_tag_proof"]["z"])):
+        v = val.reshape(2, L, P1, B, -1).permute(1, 2, 0, 3, 4)                # [L, S-1, 2, B, w]: sender-major
+        msgs[name][t_loc] = v * (st_mb == 0).reshape(L, 1, 1, B, 1).to(v.dtype)
+    hook(2)
+    # verify_proofs_get_alpha for both sides of every peer, ONE call (client :218-234), then delta_i / sigma_i (:246-247)
+    recv = lambda name: msgs[name][t_ind, t_jme].permute(2, 0, 1, 3, 4).contiguous()          # [2, L, S-1, B, w]: what each peer sent ME
+    rb = {f: recv("mb_b_" + f).reshape(nMB, -1) for f in ("pk", "R", "z")}
+    rbt = {f: recv("mb_bt_" + f).reshape(nMB, -1) for f in ("pk", "R", "z")}
+    a_it = z["k"].reshape(1, L, 1, B, 8).expand(2, L, P1, B, 8).contiguous().reshape(nMB, 8)
+    key_it = key_own.reshape(1, L, 1, B).expand(2, L, P1, B).contiguous().reshape(-1)
+    alpha, _share, ok = mta_verify_get_alpha(ctx, wallet.sk, recv("mb_c").reshape(nMB, 128), rb, rbt, a_it, key_it)
+    alpha, ok, rpk = alpha.reshape(2, L, P1, B, 8), ok.reshape(2, L, P1, B), rb["pk"].reshape(2, L, P1, B, 16)
+    delta_i, sigma_i = gg18_phase2(ctx, signers, local, z["k"], z["gamma"], w_i, alpha[0].contiguous(), beta[0].contiguous(), alpha[1].contiguous(),
+                                   beta[1].contiguous(), ok[0].contiguous(), ok[1].contiguous(), rpk[1].contiguous(), g_w, status)
+    del _share
+    put("delta", delta_i, status)
+    hook(3)
+    # round 4: the decommitment, then phase3_reconstruct_delta + phase4 (client :272-309)
+    put("blind", z["blind"], status)
+    put("g_gamma", sk_["g_gamma_i"], status)
+    hook(4)
+    R = gg18_phase4(ctx, signers, local, msgs["delta"], rpk[0].contiguous(), msgs["g_gamma"], msgs["blind"], msgs["com"], status)
+    # 5A, 5B (client :313-378)
+    a5 = gg18_phase5a(ctx, signers, local, z["k"], sigma_i, d_msg, R, z["l"], z["rho"], z["blind5a"], z["heg_s1"], z["heg_s2"], z["dlog_nonce"], status)
+    put("com5a", a5["com"], status)
+    hook(5)
+    for name, val in (("V", a5["V"]), ("A", a5["A"]), ("B", a5["B"]), ("blind5a", z["blind5a"]), ("heg_T", a5["heg"]["T"]), ("heg_A3", a5["heg"]["A3"]),
+                      ("heg_z1", a5["heg"]["z1"]), ("heg_z2", a5["heg"]["z2"]), ("dlog_pk", a5["dlog"]["pk"]), ("dlog_R", a5["dlog"]["R"]),
+                      ("dlog_z", a5["dlog"]["z"])):
+        put(name, val, status)
+    hook(6)
+    # 5C (client :379-427)
+    bc = dict(V=msgs["V"], A=msgs["A"], B=msgs["B"], blind=msgs["blind5a"], com=msgs["com5a"], T=msgs["heg_T"], A3=msgs["heg_A3"], z1=msgs["heg_z1"],
+              z2=msgs["heg_z2"], dlog_pk=msgs["dlog_pk"], dlog_R=msgs["dlog_R"], dlog_z=msgs["dlog_z"])
+    u, t_, com5c = gg18_phase5c(ctx, signers, local, d_msg, y, R, z["l"], z["rho"], z["blind5c"], bc, status)
+    put("com5c", com5c, status)
+    hook(7)
+    put("u", u, status)
+    put("t", t_, status)
+    put("blind5c", z["blind5c"], status)
+    hook(8)
+    # 5D, then the s_i and output_signature (client :455-488)
+    gg18_phase5d(ctx, signers, local, msgs["u"], msgs["t"], msgs["blind5c"], msgs["com5c"], msgs["B"], status)
+    put("s_i", a5["s_i"], status)
+    hook(9)
+    r, s, recid = gg18_output_signature(ctx, signers, local, a5["s_i"], msgs["s_i"], R, d_msg, y, status)
+    ctx.sync()
+    return dict(status=status.transpose(0, 1).contiguous(), r=r[0], s=s[0], recid=recid[0], r_all=r, s_all=s, recid_all=recid, R=R, draws=draws,
+                msgs={f: v for f, v in msgs.items() if f != "draws"}, failures=int(sum(int(f.item()) for f in fails)))
