@@ -94,13 +94,11 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC gni_kernel(Dim d, const uint32_
   ec::aff_store(gni + (size_t)pp * 16, ec::jac_to_aff(ec::jac_add(a, m)));
 }
 struct Ecddh { const uint32_t *a1, *a2, *z; };
-__device__ inline bool ecddh_verify(const ec::Aff& g1, const ec::Aff& h1, const ec::Aff& g2, const ec::Aff& h2, const ec::Aff& a1,
-                                    const ec::Aff& a2, const ec::U256& z, const ec::Enc& enc) {
+// all six points valid AND ECDDHProof::verify
+__device__ __forceinline__ bool ecddh_verify(const ec::Aff& g1, const ec::Aff& h1, const ec::Aff& g2, const ec::Aff& h2, const ec::Aff& a1,
+                                             const ec::Aff& a2, const ec::U256& z, const ec::Enc& enc) {
   if (!(ec::aff_valid(g1) && ec::aff_valid(h1) && ec::aff_valid(g2) && ec::aff_valid(h2) && ec::aff_valid(a1) && ec::aff_valid(a2))) return false;
-  const ec::Aff hp[6] = {g1, h1, g2, h2, a1, a2};
-  const ec::U256 e = gg::hash_points(hp, enc, enc.ord_ecddh);
-  return ec::jac_eq(ec::jac_mul(z, g1), ec::jac_add_aff(ec::jac_mul(e, h1), a1)) &&
-         ec::jac_eq(ec::jac_mul(z, g2), ec::jac_add_aff(ec::jac_mul(e, h2), a2));
+  return sig::ecddh_verify_body(g1, h1, g2, h2, a1, a2, z, enc);
 }
 // g_sigma_i and the ECDDH proof of signer i  (:380-414)
 __global__ void __launch_bounds__(64) MPE_EC_OCC gsigma_kernel(Dim d, const uint32_t* __restrict__ k, const uint32_t* __restrict__ miu, const uint32_t* __restrict__ gw,
@@ -163,12 +161,12 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC ecddh_prove_kernel(int B, ec::E
   const ec::U256 xx = ec::sc_reduce(x + (size_t)i * 8, 8), s = ec::sc_reduce(s_in + (size_t)i * 8, 8);
   const ec::Aff G1 = ec::aff_load(g1 + (size_t)i * 16), H1 = ec::aff_load(h1 + (size_t)i * 16), G2 = ec::aff_load(g2 + (size_t)i * 16),
                 H2 = ec::aff_load(h2 + (size_t)i * 16);
-  const ec::Aff A1 = gg::mul_aff(s, G1), A2 = gg::mul_aff(s, G2);
-  const ec::Aff hp[6] = {G1, H1, G2, H2, A1, A2};
-  const ec::U256 e = gg::hash_points(hp, enc, enc.ord_ecddh);
+  ec::Aff A1, A2;
+  ec::U256 zz;
+  sig::ecddh_prove_body(xx, s, G1, H1, G2, H2, enc, A1, A2, zz);
   ec::aff_store(a1 + (size_t)i * 16, A1);
   ec::aff_store(a2 + (size_t)i * 16, A2);
-  ec::u256_store(z + (size_t)i * 8, ec::sc_add(s, ec::sc_mul(e, xx)));
+  ec::u256_store(z + (size_t)i * 8, zz);
 }
 __global__ void __launch_bounds__(64) MPE_EC_OCC ecddh_verify_kernel(int B, ec::Enc enc, const uint32_t* __restrict__ g1, const uint32_t* __restrict__ h1, const uint32_t* __restrict__ g2,
                                                           const uint32_t* __restrict__ h2, Ecddh pr, uint8_t* __restrict__ ok) {
@@ -187,13 +185,13 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC session_ecddh_kernel(Dim d, con
   const size_t o = (size_t)(pi % d.L) * d.B + pi / d.L;
   const ec::U256 x = ec::u256_load(sigma_i + (size_t)pi * 8), s = ec::sc_reduce(nonce + (size_t)pi * 8, 8);
   const ec::Aff G1 = ec::aff_gen(), G2 = ec::aff_load(R + (size_t)pi * 16);
-  const ec::Aff H1 = ec::jac_to_aff(ec::jac_mul_gen(x)), H2 = gg::mul_aff(x, G2);
-  const ec::Aff A1 = ec::jac_to_aff(ec::jac_mul_gen(s)), A2 = gg::mul_aff(s, G2);
-  const ec::Aff hp[6] = {G1, H1, G2, H2, A1, A2};
-  const ec::U256 e = gg::hash_points(hp, d.enc, d.enc.ord_ecddh);
+  const ec::Aff H1 = ec::jac_to_aff(ec::jac_mul_gen(x)), H2 = ec::mul_aff(x, G2);
+  ec::Aff A1, A2;
+  ec::U256 zz;
+  sig::ecddh_prove_body<sig::GEN, sig::VAR>(x, s, G1, H1, G2, H2, d.enc, A1, A2, zz);
   ec::aff_store(a1 + o * 16, A1);
   ec::aff_store(a2 + o * 16, A2);
-  ec::u256_store(z + o * 8, ec::sc_add(s, ec::sc_mul(e, x)));
+  ec::u256_store(z + o * 8, zz);
 }
 // [pi][S-1][64] -> [L][B][S-1][64]
 __global__ void miu_out_kernel(Dim d, const uint32_t* __restrict__ miu, uint32_t* __restrict__ out) {

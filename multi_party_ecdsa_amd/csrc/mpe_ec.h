@@ -46,6 +46,7 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC ec_comb_build_kernel() {
 __device__ __forceinline__ Jac jac_mul_fixed(const U256& k, int g) { return jac_mul_comb(k, &COMB[g][0][0][0]); }
 __device__ __forceinline__ Jac jac_mul_gen(const U256& k) { return jac_mul_fixed(k, 0); }
 __device__ __forceinline__ Jac jac_mul_h2(const U256& k) { return jac_mul_fixed(k, 1); }
+__device__ __forceinline__ Aff mul_aff(const U256& k, const Aff& P) { return jac_to_aff(jac_mul(k, P)); }
 
 // interface layout: x[8] | y[8], all-zero = infinity
 __device__ __forceinline__ Aff aff_load(const uint32_t* p) {

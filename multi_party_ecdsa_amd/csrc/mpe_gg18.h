@@ -17,7 +17,7 @@
 // valid point, so its peers refuse it with the code of the phase in which they read it.
 // Included by mpe_lib.hip after mpe_lindell_keygen.h.
 #pragma once
-#include "mpe_lindell_keygen.h"
+#include "mpe_gg20.h"
 #include "mpe_mta.h"
 
 namespace mpe {
@@ -33,14 +33,6 @@ struct Dim {
 __device__ __forceinline__ void zero_words(uint32_t* p, int n) { for (int j = 0; j < n; ++j) p[j] = 0u; }
 // the first failure sticks
 __device__ __forceinline__ void fail(int32_t* status, int pi, int code) { if (status[pi] == 0) status[pi] = code; }
-// Sha256::new().chain_points([a1, a2, a3]).result_bigint(): the digest as an integer, not reduced mod q (party_i.rs:527-529)
-__device__ __forceinline__ ec::U256 points_digest3(const ec::Aff& a1, const ec::Aff& a2, const ec::Aff& a3, const ec::Enc& enc) {
-  ec::Sha256 s; ec::sha_init(s);
-  ec::sha_chain_point(s, a1, enc);
-  ec::sha_chain_point(s, a2, enc);
-  ec::sha_chain_point(s, a3, enc);
-  return ec::sha_final(s);
-}
 // a > b as 256-bit integers
 __device__ __forceinline__ bool u256_gt(const ec::U256& a, const ec::U256& b) {
   for (int j = 7; j >= 0; --j) if (a.w[j] != b.w[j]) return a.w[j] > b.w[j];
@@ -74,7 +66,7 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC g_w_kernel(Dim d, int n, const 
   const int j = g / d.B, b = g % d.B;
   const ec::Aff X = ec::aff_load(pk_vec + ((size_t)b * n + d.sg[j]) * 16);
   if (!ec::aff_valid(X)) { zero_words(g_w + (size_t)g * 16, 16); return; }
-  ec::aff_store(g_w + (size_t)g * 16, gg::mul_aff(gg::lagrange0(d.sg, d.S, j), X));
+  ec::aff_store(g_w + (size_t)g * 16, ec::mul_aff(gg::lagrange0(d.sg, d.S, j), X));
 }
 
 // the verdicts of the 2 (S-1) verify_proofs_get_alpha calls in the order of gg18_sign_client.rs:221-244, then phase2_delta_i and
@@ -130,13 +122,13 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC phase4_kernel(Dim d, const uint
     if (j != i) {
       const int jj = j < i ? j : j - 1;
       const ec::Aff Bp = ec::aff_load(b_pk + (((size_t)li * P1 + jj) * d.B + b) * 16);
-      good = good && ec::aff_eq(Bp, Gj) && ec::u256_eq(gg::commit_point(Gj, blind + row * 8, d.enc), ec::u256_load(com + row * 8));   // :463-469
+      good = good && ec::aff_eq(Bp, Gj) && ec::u256_eq(sig::commit_point(Gj, blind + row * 8, d.enc), ec::u256_load(com + row * 8));   // :463-469
     }
     acc = ec::jac_add_aff(acc, Gj);
   }
   if (!good) { fail(status, pi, 401); zero_words(Ro, 16); return; }
   const ec::Aff Rp = ec::jac_to_aff(acc);
-  const ec::Aff Rr = Rp.inf ? Rp : gg::mul_aff(ec::sc_inv(tot), Rp);                                    // :478, client :309
+  const ec::Aff Rr = Rp.inf ? Rp : ec::mul_aff(ec::sc_inv(tot), Rp);                                    // :478, client :309
   if (Rr.inf) { fail(status, pi, 402); zero_words(Ro, 16); return; }                                    // R.x_coord().unwrap() would panic (:496-497)
   ec::aff_store(Ro, Rr);
 }
@@ -164,15 +156,15 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC phase5a_kernel(Dim d, const uin
   const ec::Aff G = ec::aff_gen();
   const ec::Aff Ai = ec::jac_to_aff(ec::jac_mul_gen(rho)), Bi = ec::jac_to_aff(ec::jac_mul_gen(ec::sc_mul(l, rho)));           // :523-525
   const ec::Aff Vi = ec::jac_to_aff(ec::jac_add(ec::jac_mul(si, Rp), ec::jac_mul_gen(l)));                                     // :526
-  const ec::U256 dg = points_digest3(Vi, Ai, Bi, d.enc);                                                                       // :527-529
+  const ec::U256 dg = sig::points_digest(d.enc, Vi, Ai, Bi);                                                                       // :527-529
   ec::u256_store(s_i + (size_t)pi * 8, si);
   ec::aff_store(V + (size_t)pi * 16, Vi);
   ec::aff_store(A + (size_t)pi * 16, Ai);
   ec::aff_store(Bo + (size_t)pi * 16, Bi);
-  ec::u256_store(com + (size_t)pi * 8, lk::commit_bigint(dg.w, blind + (size_t)pi * 8, d.enc));                                // :530-533
+  ec::u256_store(com + (size_t)pi * 8, sig::commit_bigint(dg.w, blind + (size_t)pi * 8, d.enc));                                // :530-533
   ec::Aff T, A3;
   ec::U256 z1, z2;                                                                                       // witness {r: l_i, x: s_i}, statement (A_i, R, g, V_i, B_i)  :534-546
-  heg_prove_body(si, l, ec::sc_reduce(s1_in + (size_t)pi * 8, 8), ec::sc_reduce(s2_in + (size_t)pi * 8, 8), Ai, Rp, G, Vi, Bi, d.enc, T, A3, z1, z2);
+  sig::heg_prove_body(si, l, ec::sc_reduce(s1_in + (size_t)pi * 8, 8), ec::sc_reduce(s2_in + (size_t)pi * 8, 8), Ai, Rp, G, Vi, Bi, d.enc, T, A3, z1, z2);
   ec::aff_store(h.T + (size_t)pi * 16, T);
   ec::aff_store(h.A3 + (size_t)pi * 16, A3);
   ec::u256_store(h.z1 + (size_t)pi * 8, z1);
@@ -208,25 +200,22 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC phase5c_kernel(Dim d, const uin
     a = ec::jac_add_aff(a, Aj);                                                                         // :599  the peers' only
     const ec::Aff T = ec::aff_load(in.T + row * 16), A3 = ec::aff_load(in.A3 + row * 16), P = ec::aff_load(in.dpk + row * 16), Rd = ec::aff_load(in.dR + row * 16);
     if (!(ec::aff_valid(T) && ec::aff_valid(A3) && ec::aff_valid(P) && ec::aff_valid(Rd))) { good = false; break; }
-    const ec::U256 dg = points_digest3(Vj, Aj, Bj, d.enc);
-    good = ec::u256_eq(lk::commit_bigint(dg.w, in.blind + row * 8, d.enc), ec::u256_load(in.com + row * 8));                   // :582-589
-    good = good && heg_verify_body(Aj, Rp, G, Vj, Bj, T, A3, ec::sc_reduce(in.z1 + row * 8, 8), ec::sc_reduce(in.z2 + row * 8, 8), d.enc);   // :590
-    if (good) {                                                                                         // DLogProof::verify  :591
-      const ec::Jac lhs = ec::jac_add(ec::jac_mul_gen(ec::sc_reduce(in.dz + row * 8, 8)), ec::jac_mul(dlog_challenge(Rd, P, d.enc), P));
-      good = ec::jac_eq_aff(lhs, Rd);
-    }
+    const ec::U256 dg = sig::points_digest(d.enc, Vj, Aj, Bj);
+    good = ec::u256_eq(sig::commit_bigint(dg.w, in.blind + row * 8, d.enc), ec::u256_load(in.com + row * 8));                   // :582-589
+    good = good && sig::heg_verify_body(Aj, Rp, G, Vj, Bj, T, A3, ec::sc_reduce(in.z1 + row * 8, 8), ec::sc_reduce(in.z2 + row * 8, 8), d.enc);   // :590
+    good = good && sig::dlog_verify_body(P, Rd, ec::sc_reduce(in.dz + row * 8, 8), d.enc);              // DLogProof::verify  :591
   }
   if (!good) { fail(status, pi, 531); zero_words(uo, 16); zero_words(to, 16); zero_words(co, 8); return; }
   const ec::U256 m = ec::sc_reduce(msg + (size_t)b * 8, 8), r = ec::sc_reduce(Rp.x.w, 8);                                      // :601-610
   v = ec::jac_add(v, ec::jac_neg(ec::jac_mul_gen(m)));                                                  // :612
   v = ec::jac_add(v, ec::jac_neg(ec::jac_mul(r, Y)));
   const ec::Aff va = ec::jac_to_aff(v), aa = ec::jac_to_aff(a);
-  const ec::Aff ui = va.inf ? va : gg::mul_aff(ec::sc_reduce(rho_in + (size_t)pi * 8, 8), va);         // :613
-  const ec::Aff ti = aa.inf ? aa : gg::mul_aff(ec::sc_reduce(l_in + (size_t)pi * 8, 8), aa);           // :614
+  const ec::Aff ui = va.inf ? va : ec::mul_aff(ec::sc_reduce(rho_in + (size_t)pi * 8, 8), va);         // :613
+  const ec::Aff ti = aa.inf ? aa : ec::mul_aff(ec::sc_reduce(l_in + (size_t)pi * 8, 8), aa);           // :614
   ec::aff_store(uo, ui);
   ec::aff_store(to, ti);
-  const ec::U256 dg = lk::points_digest(ui, ti, d.enc);                                                 // :615
-  ec::u256_store(co, lk::commit_bigint(dg.w, blind2 + (size_t)pi * 8, d.enc));                          // :617-620
+  const ec::U256 dg = sig::points_digest(d.enc, ui, ti);                                                 // :615
+  ec::u256_store(co, sig::commit_bigint(dg.w, blind2 + (size_t)pi * 8, d.enc));                          // :617-620
 }
 
 // phase5d (:638-673) over all S decommitments of 5D and of 5A
@@ -242,8 +231,8 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC phase5d_kernel(Dim d, const uin
     const size_t row = (size_t)j * d.B + b;
     const ec::Aff uj = ec::aff_load(u + row * 16), tj = ec::aff_load(t + row * 16), Bj = ec::aff_load(Bv + row * 16);
     if (!(ec::aff_valid(uj) && ec::aff_valid(tj) && ec::aff_valid(Bj))) { test_com = false; break; }
-    const ec::U256 dg = lk::points_digest(uj, tj, d.enc);
-    test_com = test_com && ec::u256_eq(lk::commit_bigint(dg.w, blind2 + row * 8, d.enc), ec::u256_load(com2 + row * 8));       // :647-655
+    const ec::U256 dg = sig::points_digest(d.enc, uj, tj);
+    test_com = test_com && ec::u256_eq(sig::commit_bigint(dg.w, blind2 + row * 8, d.enc), ec::u256_load(com2 + row * 8));       // :647-655
     tb = ec::jac_add_aff(ec::jac_add_aff(tb, tj), Bj);                                                  // :662
     us = ec::jac_add_aff(us, uj);
   }

@@ -211,39 +211,12 @@ __device__ inline ec::U256 lagrange0(const int* sg, int S, int i) {
   }
   return ec::sc_mul(num, ec::sc_inv(den));
 }
-// HashCommitment(compressed point as BigInt, blind)  (party_i.rs:577-580)
-__device__ inline ec::U256 commit_point(const ec::Aff& P, const uint32_t* blind, const ec::Enc& enc) {
-  ec::Sha256 s; ec::sha_init(s);
-  ec::sha_point_compressed(s, P);
-  ec::sha_bigint(s, blind, 8, enc);
-  return ec::sha_final(s);
-}
-// (the points are passed as an array reference and the function is force-inlined: handing a pointer to a
-//  lane-private array to an out-of-line function hung the kernel on gfx950 / ROCm 7.2)
-// `pts` is the canonical list of the proof (include/mpecdsa_hip.h names it per proof); `ord[i]` = which of them is hashed
-// i-th.  The selection is a compare-and-select chain, never a dynamic index into the lane-private array.
-template <int N>
-__device__ __forceinline__ ec::U256 hash_points(const ec::Aff (&pts)[N], const ec::Enc& enc, const uint8_t* ord) {
-  ec::Sha256 s; ec::sha_init(s);
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    const int o = ord[i];
-    ec::Aff P = pts[0];
-#pragma unroll
-    for (int j = 1; j < N; ++j) if (o == j) P = pts[j];
-    ec::sha_chain_point(s, P, enc);
-  }
-  const ec::U256 d = ec::sha_final(s);
-  return ec::sc_reduce(d.w, 8);
-}
-__device__ __forceinline__ ec::Aff mul_aff(const ec::U256& k, const ec::Aff& P) { return ec::jac_to_aff(ec::jac_mul(k, P)); }
-
 // g_w_vec of a key set: lambda_j X_j for every signer (once per key object)
 __global__ void __launch_bounds__(64) MPE_EC_OCC gw_kernel(Dim d, const uint32_t* __restrict__ Xs, uint32_t* __restrict__ gw) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= d.K * d.S) return;
   const int kk = g / d.S, j = g % d.S;
-  ec::aff_store(gw + (size_t)g * 16, mul_aff(lagrange0(d.sg, d.S, j), ec::aff_load(Xs + ((size_t)kk * d.n + d.sg[j]) * 16)));
+  ec::aff_store(gw + (size_t)g * 16, ec::mul_aff(lagrange0(d.sg, d.S, j), ec::aff_load(Xs + ((size_t)kk * d.n + d.sg[j]) * 16)));
 }
 
 // ---- Round 0: SignKeys::create + phase1_broadcast (party_i.rs:546-589) ----------------------------
@@ -267,7 +240,7 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r0_kernel(Dim d, const uint32_t
   for (int j = 0; j < 64; ++j) k64[(size_t)pi * 64 + j] = j < 8 ? k.w[j] : 0u;
   const ec::Aff gg = ec::jac_to_aff(ec::jac_mul_gen(g));
   ec::aff_store(g_gamma + (size_t)pi * 16, gg);
-  ec::u256_store(com + (size_t)pi * 8, commit_point(gg, blind + (size_t)pi * 8, d.enc));
+  ec::u256_store(com + (size_t)pi * 8, sig::commit_point(gg, blind + (size_t)pi * 8, d.enc));
 }
 
 // ---- Round 1 -------------------------------------------------------------------------------------------------------
@@ -333,16 +306,9 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r2a_kernel(Dim d, const int32_t
   const ec::U256 al = ec::sc_reduce(alpha_full + (size_t)rv * 64, 64);
   ec::u256_store(alpha + (size_t)rv * 8, al);
   const ec::Aff Bpk = ec::aff_load(m + M1.b_pk.off), BTpk = ec::aff_load(m + M1.bt_pk.off);
-  const ec::Jac g_alpha = ec::jac_mul_gen(al);
-  const ec::Jac ba_btag = ec::jac_add_aff(ec::jac_mul(ec::u256_load(kq + (size_t)pi * 8), Bpk), BTpk);
-  bool good = ec::jac_eq(g_alpha, ba_btag);
-  {  // DLogProof::verify x2
-    const ec::Aff R1 = ec::aff_load(m + M1.b_R.off), R2 = ec::aff_load(m + M1.bt_R.off);
-    const ec::U256 c1 = dlog_challenge(R1, Bpk, d.enc), c2 = dlog_challenge(R2, BTpk, d.enc);
-    const ec::Jac l1 = ec::jac_add(ec::jac_mul_gen(ec::sc_reduce(m + M1.b_z.off, 8)), ec::jac_mul(c1, Bpk));
-    const ec::Jac l2 = ec::jac_add(ec::jac_mul_gen(ec::sc_reduce(m + M1.bt_z.off, 8)), ec::jac_mul(c2, BTpk));
-    good = good && ec::jac_eq_aff(l1, R1) && ec::jac_eq_aff(l2, R2);
-  }
+  const ec::Aff R1 = ec::aff_load(m + M1.b_R.off), R2 = ec::aff_load(m + M1.bt_R.off);
+  const bool good = sig::mta_alpha_holds(al, ec::u256_load(kq + (size_t)pi * 8), Bpk, R1, ec::sc_reduce(m + M1.b_z.off, 8), BTpk, R2,
+                                         ec::sc_reduce(m + M1.bt_z.off, 8), d.enc);
   r2a_finish(d, rv, v, pp, b, ind, Bpk, good, gw, bpk_in, code);
 }
 
@@ -390,20 +356,19 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r2b_kernel(Dim d, const uint32_
   ec::u256_store(sigma_i + (size_t)pi * 8, si);
   const ec::U256 l = ec::sc_reduce(l_in + (size_t)pi * 8, 8);
   ec::u256_store(lq + (size_t)pi * 8, l);
-  const ec::Aff G = ec::aff_gen(), H = ec::aff_h2();
   // l H, a1 = s1 G, a2 = s2 H depend on the party's own nonces only: Round 0 computed them beside its ladders (ped_ahead_kernel)
   const uint32_t* pre = ped_pre ? ped_pre + (size_t)pi * 48 : nullptr;
   const ec::Aff T = ec::jac_to_aff(ec::jac_add(ec::jac_mul_gen(si), pre ? ec::jac_from_aff(ec::aff_load(pre)) : ec::jac_mul_h2(l)));
   const ec::U256 s1 = ec::sc_reduce(s1_in + (size_t)pi * 8, 8), s2 = ec::sc_reduce(s2_in + (size_t)pi * 8, 8);
   const ec::Aff a1 = pre ? ec::aff_load(pre + 16) : ec::jac_to_aff(ec::jac_mul_gen(s1)), a2 = pre ? ec::aff_load(pre + 32) : ec::jac_to_aff(ec::jac_mul_h2(s2));
-  const ec::Aff hp[5] = {G, H, T, a1, a2};
-  const ec::U256 e = hash_points(hp, d.enc, d.enc.ord_pedersen);
+  ec::U256 e, z1, z2;
+  sig::pedersen_prove_body(si, l, s1, s2, T, a1, a2, d.enc, e, z1, z2);
   ec::aff_store(p.T + (size_t)pi * 16, T);
   ec::u256_store(p.e + (size_t)pi * 8, e);
   ec::aff_store(p.a1 + (size_t)pi * 16, a1);
   ec::aff_store(p.a2 + (size_t)pi * 16, a2);
-  ec::u256_store(p.z1 + (size_t)pi * 8, ec::sc_add(s1, ec::sc_mul(e, si)));
-  ec::u256_store(p.z2 + (size_t)pi * 8, ec::sc_add(s2, ec::sc_mul(e, l)));
+  ec::u256_store(p.z1 + (size_t)pi * 8, z1);
+  ec::u256_store(p.z2 + (size_t)pi * 8, z2);
 }
 
 // ---- Round 3: T_i == proof.com, delta^-1, every PedersenProof (rounds.rs:347-402) -----------------------------------
@@ -426,7 +391,6 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r3_kernel(Dim d, Slab in2, uint
   const int pi = blockIdx.x * blockDim.x + threadIdx.x;
   if (pi >= d.B * d.L) return;
   const int b = pi / d.L;
-  const ec::Aff G = ec::aff_gen(), H = ec::aff_h2();
   ec::U256 sum = ec::u256_zero();
   bool com_ok = true, ped_ok = true;
   for (int j = 0; j < d.S; ++j) {
@@ -434,11 +398,8 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r3_kernel(Dim d, Slab in2, uint
     sum = ec::sc_add(sum, ec::sc_reduce(m + M2.delta.off, 8));
     com_ok = com_ok && words_eq(m + M2.T.off, m + M2.com.off, M2.T.words);
     const ec::Aff C = ec::aff_load(m + M2.com.off), a1 = ec::aff_load(m + M2.a1.off), a2 = ec::aff_load(m + M2.a2.off);
-    const ec::Aff hp[5] = {G, H, C, a1, a2};
-    const ec::U256 e = hash_points(hp, d.enc, d.enc.ord_pedersen);
-    const ec::Jac lhs = ec::jac_add(ec::jac_mul_gen(ec::sc_reduce(m + M2.z1.off, 8)), ec::jac_mul_h2(ec::sc_reduce(m + M2.z2.off, 8)));
-    const ec::Jac rhs = ec::jac_add_aff(ec::jac_add_aff(ec::jac_mul(e, C), a1), a2);
-    ped_ok = ped_ok && ec::jac_eq(lhs, rhs);
+    const bool holds = sig::pedersen_verify_body(C, a1, a2, ec::sc_reduce(m + M2.z1.off, 8), ec::sc_reduce(m + M2.z2.off, 8), d.enc);
+    ped_ok = ped_ok && holds;
   }
   r3_finish(pi, com_ok, ped_ok, sum, dinv, status, bad);
 }
@@ -457,22 +418,22 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r4_kernel(Dim d, Slab in3, cons
     const uint32_t* m = rec_of(in3, ind, b);
     const ec::Aff gg = ec::aff_load(m + M3.g_gamma.off);
     bool good = ec::aff_eq(ec::aff_load(bpk_in + ((size_t)pi * P1 + jj) * 16), gg);
-    good = good && ec::u256_eq(commit_point(gg, m + M3.blind.off, d.enc), ec::u256_load(com_all + ((size_t)ind * d.B + b) * 8));
+    good = good && ec::u256_eq(sig::commit_point(gg, m + M3.blind.off, d.enc), ec::u256_load(com_all + ((size_t)ind * d.B + b) * 8));
     if (!good) mask |= 1u << ind;
   }
   if (mask) fail(status, bad, pi, 401, mask);
   ec::Jac acc = ec::jac_inf();
   for (int j = 0; j < d.S; ++j) acc = ec::jac_add(acc, ec::jac_from_aff(ec::aff_load(rec_of(in3, j, b) + M3.g_gamma.off)));
-  const ec::Aff Rp = mul_aff(ec::u256_load(dinv + (size_t)pi * 8), ec::jac_to_aff(acc));
+  const ec::Aff Rp = ec::mul_aff(ec::u256_load(dinv + (size_t)pi * 8), ec::jac_to_aff(acc));
   ec::aff_store(R + (size_t)pi * 16, Rp);
-  if (with_rbar) ec::aff_store(Rbar + (size_t)pi * 16, mul_aff(ec::u256_load(kq + (size_t)pi * 8), Rp));
+  if (with_rbar) ec::aff_store(Rbar + (size_t)pi * 16, ec::mul_aff(ec::u256_load(kq + (size_t)pi * 8), Rp));
 }
 // R_dash = k_i R in a launch of its own: a small batch runs it BESIDE u1 = alpha R of the PDL proofs (both need R only)
 __global__ void __launch_bounds__(64) MPE_EC_OCC r4_rbar_kernel(Dim d, const uint32_t* __restrict__ kq, const uint32_t* __restrict__ R, uint32_t* __restrict__ Rbar) {
   MPE_FOREGROUND();
   const int pi = blockIdx.x * blockDim.x + threadIdx.x;
   if (pi >= d.B * d.L) return;
-  ec::aff_store(Rbar + (size_t)pi * 16, mul_aff(ec::u256_load(kq + (size_t)pi * 8), ec::aff_load(R + (size_t)pi * 16)));
+  ec::aff_store(Rbar + (size_t)pi * 16, ec::mul_aff(ec::u256_load(kq + (size_t)pi * 8), ec::aff_load(R + (size_t)pi * 16)));
 }
 
 // ---- Round 5 -------------------------------------------------------------------------------------------------------
@@ -510,16 +471,16 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r5_prove_kernel(Dim d, const ui
   const ec::Aff G = ec::aff_gen(), H = ec::aff_h2();
   const ec::Aff Rp = ec::aff_load(R + (size_t)pi * 16), T = ec::aff_load(pedT + (size_t)pi * 16);
   const ec::U256 si = ec::u256_load(sigma_i + (size_t)pi * 8), l = ec::u256_load(lq + (size_t)pi * 8);
-  const ec::Aff Sp = mul_aff(si, Rp);
+  const ec::Aff Sp = ec::mul_aff(si, Rp);
   const ec::U256 s1 = ec::sc_reduce(s1_in + (size_t)pi * 8, 8), s2 = ec::sc_reduce(s2_in + (size_t)pi * 8, 8);
-  const ec::Aff A3 = mul_aff(s2, Rp), TT = ec::jac_to_aff(ec::jac_add(ec::jac_mul_h2(s1), ec::jac_mul_gen(s2)));
-  const ec::Aff hp[7] = {TT, A3, Rp, H, G, T, Sp};
-  const ec::U256 e = hash_points(hp, d.enc, d.enc.ord_heg);
+  ec::Aff TT, A3;
+  ec::U256 z1, z2;                                      // witness {x: l_i, r: sigma_i}, statement (R, h, g, T_i, S_i)
+  sig::heg_prove_body<sig::VAR, sig::H2, sig::GEN>(l, si, s1, s2, Rp, H, G, T, Sp, d.enc, TT, A3, z1, z2);
   ec::aff_store(h.S + (size_t)pi * 16, Sp);
   ec::aff_store(h.T + (size_t)pi * 16, TT);
   ec::aff_store(h.A3 + (size_t)pi * 16, A3);
-  ec::u256_store(h.z1 + (size_t)pi * 8, ec::u256_is_zero(l) ? s1 : ec::sc_add(s1, ec::sc_mul(l, e)));
-  ec::u256_store(h.z2 + (size_t)pi * 8, ec::sc_add(s2, ec::sc_mul(si, e)));
+  ec::u256_store(h.z1 + (size_t)pi * 8, z1);
+  ec::u256_store(h.z2 + (size_t)pi * 8, z2);
 }
 
 // ---- Round 6: every HomoELGamalProof; sum S_i == y (party_i.rs:801-848) --------------------------------------------
@@ -535,13 +496,8 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r6_kernel(Dim d, Slab in5, cons
     const uint32_t* m = rec_of(in5, j, b);
     const ec::Aff E = ec::aff_load(m + M5.S.off), TT = ec::aff_load(m + M5.T.off), A3 = ec::aff_load(m + M5.A3.off),
                   D = ec::aff_load(tvec + ((size_t)j * d.B + b) * 16);
-    const ec::Aff hp[7] = {TT, A3, Rp, H, G, D, E};
-    const ec::U256 e = hash_points(hp, d.enc, d.enc.ord_heg), z1 = ec::sc_reduce(m + M5.z1.off, 8), z2 = ec::sc_reduce(m + M5.z2.off, 8);
-    const ec::Jac l1 = ec::jac_add(ec::jac_mul_h2(z1), ec::jac_mul_gen(z2));
-    const ec::Jac r1 = ec::jac_add_aff(ec::jac_mul(e, D), TT);
-    const ec::Jac l2 = ec::jac_mul(z2, Rp);
-    const ec::Jac r2 = ec::jac_add_aff(ec::jac_mul(e, E), A3);
-    if (!(ec::jac_eq(l1, r1) && ec::jac_eq(l2, r2))) mask |= 1u << j;
+    if (!sig::heg_verify_body<sig::VAR, sig::H2, sig::GEN>(Rp, H, G, D, E, TT, A3, ec::sc_reduce(m + M5.z1.off, 8), ec::sc_reduce(m + M5.z2.off, 8), d.enc))
+      mask |= 1u << j;
     acc = ec::jac_add_aff(acc, E);
   }
   if (mask) fail(status, bad, pi, 601, mask);
@@ -574,7 +530,7 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r2a_group_kernel(Dim d, const i
   const ec::Aff R1 = ec::aff_load(m + M1.b_R.off), R2 = ec::aff_load(m + M1.bt_R.off);
   ec::Jac res = ec::jac_inf(), fr = ec::jac_inf();
   if (live && sub < 3) {
-    const ec::U256 sc = sub == 0 ? ec::u256_load(kq + (size_t)pi * 8) : (sub == 1 ? dlog_challenge(R1, Bpk, d.enc) : dlog_challenge(R2, BTpk, d.enc));
+    const ec::U256 sc = sub == 0 ? ec::u256_load(kq + (size_t)pi * 8) : (sub == 1 ? sig::dlog_challenge(R1, Bpk, d.enc) : sig::dlog_challenge(R2, BTpk, d.enc));
     res = ec::jac_mul(sc, sub == 2 ? BTpk : Bpk);
     const ec::U256 fk = sub == 0 ? al : ec::sc_reduce(m + (sub == 1 ? M1.b_z.off : M1.bt_z.off), 8);
     fr = ec::jac_mul_gen(fk);
@@ -584,9 +540,8 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r2a_group_kernel(Dim d, const i
   __syncthreads();
   if (!live || sub) return;
   ec::u256_store(alpha + (size_t)rv * 8, al);
-  bool good = ec::jac_eq(fs.v[base], ec::jac_add_aff(vs.v[base], BTpk));                     // g^alpha == k_i B + B'
-  good = good && ec::jac_eq_aff(ec::jac_add(fs.v[base + 1], vs.v[base + 1]), R1)             // DLogProof::verify x2
-              && ec::jac_eq_aff(ec::jac_add(fs.v[base + 2], vs.v[base + 2]), R2);
+  const bool good = sig::mta_relation_holds(fs.v[base], vs.v[base], BTpk)                    // g^alpha == k_i B + B'
+                    && sig::dlog_holds(fs.v[base + 1], vs.v[base + 1], R1) && sig::dlog_holds(fs.v[base + 2], vs.v[base + 2], R2);
   r2a_finish(d, rv, v, pp, b, ind, Bpk, good, gw, bpk_in, code);
 }
 
@@ -598,13 +553,11 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r3_group_kernel(Dim d, int G, S
   const int gid = blockIdx.x * 64 + threadIdx.x, pi = gid / G, sub = gid % G, base = (int)threadIdx.x - sub;
   const bool live = pi < d.B * d.L;
   const int b = live ? pi / d.L : 0;
-  const ec::Aff Gp = ec::aff_gen(), H = ec::aff_h2();
   ec::Jac res = ec::jac_inf(), fr = ec::jac_inf();
   if (live && sub < d.S) {
     const uint32_t* m = rec_of(in2, sub, b);
     const ec::Aff C = ec::aff_load(m + M2.com.off), a1 = ec::aff_load(m + M2.a1.off), a2 = ec::aff_load(m + M2.a2.off);
-    const ec::Aff hp[5] = {Gp, H, C, a1, a2};
-    res = ec::jac_mul(hash_points(hp, d.enc, d.enc.ord_pedersen), C);
+    res = ec::jac_mul(sig::pedersen_challenge(C, a1, a2, d.enc), C);
   }
   if (live && sub < 2 * d.S) {
     const uint32_t* m = rec_of(in2, sub >> 1, b);
@@ -621,9 +574,8 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r3_group_kernel(Dim d, int G, S
     sum = ec::sc_add(sum, ec::sc_reduce(m + M2.delta.off, 8));
     com_ok = com_ok && words_eq(m + M2.T.off, m + M2.com.off, M2.T.words);
     const ec::Aff a1 = ec::aff_load(m + M2.a1.off), a2 = ec::aff_load(m + M2.a2.off);
-    const ec::Jac lhs = ec::jac_add(fs.v[base + 2 * j], fs.v[base + 2 * j + 1]);
-    const ec::Jac rhs = ec::jac_add_aff(ec::jac_add_aff(vs.v[base + j], a1), a2);
-    ped_ok = ped_ok && ec::jac_eq(lhs, rhs);
+    const bool holds = sig::pedersen_holds(fs.v[base + 2 * j], fs.v[base + 2 * j + 1], vs.v[base + j], a1, a2);
+    ped_ok = ped_ok && holds;
   }
   r3_finish(pi, com_ok, ped_ok, sum, dinv, status, bad);
 }
@@ -642,8 +594,7 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r6_group_kernel(Dim d, int G, S
     const uint32_t* m = rec_of(in5, j, b);
     const ec::Aff E = ec::aff_load(m + M5.S.off), TT = ec::aff_load(m + M5.T.off), A3 = ec::aff_load(m + M5.A3.off),
                   D = ec::aff_load(tvec + ((size_t)j * d.B + b) * 16);
-    const ec::Aff hp[7] = {TT, A3, Rp, H, Gp, D, E};
-    const ec::U256 e = hash_points(hp, d.enc, d.enc.ord_heg);
+    const ec::U256 e = sig::heg_challenge(TT, A3, Rp, H, Gp, D, E, d.enc);
     res = ec::jac_mul(kind == 1 ? ec::sc_reduce(m + M5.z2.off, 8) : e, kind == 0 ? D : (kind == 1 ? Rp : E));
   }
   if (live && sub < 2 * d.S) {
@@ -659,10 +610,8 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r6_group_kernel(Dim d, int G, S
   for (int j = 0; j < d.S; ++j) {
     const uint32_t* m = rec_of(in5, j, b);
     const ec::Aff E = ec::aff_load(m + M5.S.off), TT = ec::aff_load(m + M5.T.off), A3 = ec::aff_load(m + M5.A3.off);
-    const ec::Jac l1 = ec::jac_add(fs.v[base + 2 * j], fs.v[base + 2 * j + 1]);
-    const ec::Jac r1 = ec::jac_add_aff(vs.v[base + 3 * j], TT);
-    const ec::Jac r2 = ec::jac_add_aff(vs.v[base + 3 * j + 2], A3);
-    if (!(ec::jac_eq(l1, r1) && ec::jac_eq(vs.v[base + 3 * j + 1], r2))) mask |= 1u << j;
+    if (!sig::heg_holds(fs.v[base + 2 * j], fs.v[base + 2 * j + 1], vs.v[base + 3 * j], TT, vs.v[base + 3 * j + 1], vs.v[base + 3 * j + 2], A3))
+      mask |= 1u << j;
     acc = ec::jac_add_aff(acc, E);
   }
   if (mask) fail(status, bad, pi, 601, mask);

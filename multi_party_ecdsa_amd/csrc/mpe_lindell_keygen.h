@@ -14,32 +14,16 @@
 #pragma once
 #include "mpe_lindell.h"
 #include "mpe_primes.h"
-#include "mpe_sigma.h"
+#include "mpe_sigma_dev.h"
 
 namespace mpe {
 namespace lk {
-
-// HashCommitment::create_commitment_with_user_defined_randomness(m, blind) for a 256-bit m: SHA-256 over BigInt::to_bytes of both
-// (minimal big-endian bytes; what zero gives is enc.zero_bytes) — the rule gg::commit_point applies to its blind factor
-__device__ __forceinline__ ec::U256 commit_bigint(const uint32_t* m, const uint32_t* blind, const ec::Enc& enc) {
-  ec::Sha256 s; ec::sha_init(s);
-  ec::sha_bigint(s, m, 8, enc);
-  ec::sha_bigint(s, blind, 8, enc);
-  return ec::sha_final(s);
-}
-// Sha256::new().chain_points([a1, a2]).result_bigint(): the digest as an integer, NOT reduced mod q (party_two.rs:347-349)
-__device__ __forceinline__ ec::U256 points_digest(const ec::Aff& a1, const ec::Aff& a2, const ec::Enc& enc) {
-  ec::Sha256 s; ec::sha_init(s);
-  ec::sha_chain_point(s, a1, enc);
-  ec::sha_chain_point(s, a2, enc);
-  return ec::sha_final(s);
-}
 
 __global__ void __launch_bounds__(64) MPE_EC_OCC hash_commit_bigint_kernel(int B, ec::Enc enc, const uint32_t* __restrict__ m, const uint32_t* __restrict__ blind,
                                                                 uint32_t* __restrict__ com) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B) return;
-  ec::u256_store(com + (size_t)i * 8, commit_bigint(m + (size_t)i * 8, blind + (size_t)i * 8, enc));
+  ec::u256_store(com + (size_t)i * 8, sig::commit_bigint(m + (size_t)i * 8, blind + (size_t)i * 8, enc));
 }
 
 // party two's verdict on party one's long-term first and second message (party_two.rs:180-223): both commitments recomputed and
@@ -52,11 +36,9 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC kg_verdict_kernel(int B, ec::En
   if (i >= B) return;
   const ec::Aff P = ec::aff_load(Q1 + (size_t)i * 16), Rp = ec::aff_load(R + (size_t)i * 16);
   if (!ec::aff_valid(P) || !ec::aff_valid(Rp)) { ok[i] = 0; return; }         // curv rejects such points when it deserialises them
-  const bool c1 = ec::u256_eq(gg::commit_point(P, blind_pk + (size_t)i * 8, enc), ec::u256_load(pk_com + (size_t)i * 8));       // :195-202
-  const bool c2 = ec::u256_eq(gg::commit_point(Rp, blind_pok + (size_t)i * 8, enc), ec::u256_load(pok_com + (size_t)i * 8));    // :203-215
-  const ec::U256 c = dlog_challenge(Rp, P, enc), zz = ec::sc_reduce(z + (size_t)i * 8, 8);
-  const ec::Jac l = ec::jac_add(ec::jac_mul_gen(zz), ec::jac_mul(c, P));                                                      // :221
-  const bool pr = ec::jac_eq_aff(l, Rp);
+  const bool c1 = ec::u256_eq(sig::commit_point(P, blind_pk + (size_t)i * 8, enc), ec::u256_load(pk_com + (size_t)i * 8));       // :195-202
+  const bool c2 = ec::u256_eq(sig::commit_point(Rp, blind_pok + (size_t)i * 8, enc), ec::u256_load(pok_com + (size_t)i * 8));    // :203-215
+  const bool pr = sig::dlog_verify_body(P, Rp, ec::sc_reduce(z + (size_t)i * 8, 8), enc);                                        // :221
   ok[i] = (c1 && c2 && pr) ? 1 : 0;
 }
 
@@ -72,17 +54,17 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC eph_first_kernel(int B, ec::Enc
   const ec::U256 x = ec::sc_reduce(k2 + (size_t)i * 8, 8), s = ec::sc_reduce(nonce + (size_t)i * 8, 8);
   const ec::Aff G = ec::aff_gen(), H = ec::aff_h2();
   const ec::Aff P = ec::jac_to_aff(ec::jac_mul_gen(x)), Cc = ec::jac_to_aff(ec::jac_mul_h2(x));                                // :320-324
-  const ec::Aff A1 = ec::jac_to_aff(ec::jac_mul_gen(s)), A2 = ec::jac_to_aff(ec::jac_mul_h2(s));                               // ECDDHProof::prove :334
-  const ec::Aff hp[6] = {G, P, H, Cc, A1, A2};
-  const ec::U256 e = gg::hash_points(hp, enc, enc.ord_ecddh);
+  ec::Aff A1, A2;
+  ec::U256 zz;
+  sig::ecddh_prove_body<sig::GEN, sig::H2>(x, s, G, P, H, Cc, enc, A1, A2, zz);                                                // ECDDHProof::prove :334
   ec::aff_store(pub + (size_t)i * 16, P);
   ec::aff_store(c + (size_t)i * 16, Cc);
   ec::aff_store(a1 + (size_t)i * 16, A1);
   ec::aff_store(a2 + (size_t)i * 16, A2);
-  ec::u256_store(z + (size_t)i * 8, ec::sc_add(s, ec::sc_mul(e, x)));
-  ec::u256_store(pk_com + (size_t)i * 8, gg::commit_point(P, blind_pk + (size_t)i * 8, enc));                                  // :338-342
-  const ec::U256 dg = points_digest(A1, A2, enc);
-  ec::u256_store(pok_com + (size_t)i * 8, commit_bigint(dg.w, blind_pok + (size_t)i * 8, enc));                                // :345-351
+  ec::u256_store(z + (size_t)i * 8, zz);
+  ec::u256_store(pk_com + (size_t)i * 8, sig::commit_point(P, blind_pk + (size_t)i * 8, enc));                                  // :338-342
+  const ec::U256 dg = sig::points_digest(enc, A1, A2);
+  ec::u256_store(pok_com + (size_t)i * 8, sig::commit_bigint(dg.w, blind_pok + (size_t)i * 8, enc));                                // :345-351
 }
 
 // party one's verdict on it (party_one.rs:437-483): both commitments, then ECDDHProof::verify over (G, public_share, H, c); the two
@@ -96,15 +78,12 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC eph_verdict_kernel(int B, ec::E
   const ec::Aff P = ec::aff_load(pub + (size_t)i * 16), Cc = ec::aff_load(c + (size_t)i * 16), A1 = ec::aff_load(a1 + (size_t)i * 16),
                 A2 = ec::aff_load(a2 + (size_t)i * 16);
   if (!(ec::aff_valid(P) && ec::aff_valid(Cc) && ec::aff_valid(A1) && ec::aff_valid(A2))) { ok[i] = 0; return; }
-  const bool c1 = ec::u256_eq(gg::commit_point(P, blind_pk + (size_t)i * 8, enc), ec::u256_load(pk_com + (size_t)i * 8));       // :451-458
-  const ec::U256 dg = points_digest(A1, A2, enc);
-  const bool c2 = ec::u256_eq(commit_bigint(dg.w, blind_pok + (size_t)i * 8, enc), ec::u256_load(pok_com + (size_t)i * 8));     // :459-468
+  const bool c1 = ec::u256_eq(sig::commit_point(P, blind_pk + (size_t)i * 8, enc), ec::u256_load(pk_com + (size_t)i * 8));       // :451-458
+  const ec::U256 dg = sig::points_digest(enc, A1, A2);
+  const bool c2 = ec::u256_eq(sig::commit_bigint(dg.w, blind_pok + (size_t)i * 8, enc), ec::u256_load(pok_com + (size_t)i * 8));     // :459-468
   const ec::Aff G = ec::aff_gen(), H = ec::aff_h2();
-  const ec::Aff hp[6] = {G, P, H, Cc, A1, A2};
-  const ec::U256 e = gg::hash_points(hp, enc, enc.ord_ecddh), zz = ec::sc_reduce(z + (size_t)i * 8, 8);
-  const bool p1 = ec::jac_eq(ec::jac_mul_gen(zz), ec::jac_add_aff(ec::jac_mul(e, P), A1));                                    // :480
-  const bool p2 = ec::jac_eq(ec::jac_mul_h2(zz), ec::jac_add_aff(ec::jac_mul(e, Cc), A2));
-  ok[i] = (c1 && c2 && p1 && p2) ? 1 : 0;
+  const bool pr = sig::ecddh_verify_body<sig::GEN, sig::H2>(G, P, H, Cc, A1, A2, ec::sc_reduce(z + (size_t)i * 8, 8), enc);      // :480
+  ok[i] = (c1 && c2 && pr) ? 1 : 0;
 }
 
 // party_one::verify (party_one.rs:567-592): accept iff pub is a valid point, 1 <= s and s < q - s (so s >= q and high s are refused),

@@ -47,14 +47,8 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC mta_alpha_kernel(int B, ec::Enc
   const ec::Aff Bpk = ec::aff_load(pk + (size_t)i * 16), BTpk = ec::aff_load(tpk + (size_t)i * 16);
   const ec::Aff R1 = ec::aff_load(R + (size_t)i * 16), R2 = ec::aff_load(tR + (size_t)i * 16);
   if (!ec::aff_valid(Bpk) || !ec::aff_valid(BTpk) || !ec::aff_valid(R1) || !ec::aff_valid(R2)) { ok[i] = 0; return; }   // the secret a is never multiplied into an unchecked point
-  const ec::Jac g_alpha = ec::jac_mul_gen(al);
-  const ec::Jac bb = ec::jac_add_aff(ec::jac_mul(ec::sc_reduce(a + (size_t)i * 8, 8), Bpk), BTpk);
-  bool good = ec::jac_eq(g_alpha, bb);
-  const ec::U256 c1 = dlog_challenge(R1, Bpk, enc), c2 = dlog_challenge(R2, BTpk, enc);
-  const ec::Jac l1 = ec::jac_add(ec::jac_mul_gen(ec::sc_reduce(z + (size_t)i * 8, 8)), ec::jac_mul(c1, Bpk));
-  const ec::Jac l2 = ec::jac_add(ec::jac_mul_gen(ec::sc_reduce(tz + (size_t)i * 8, 8)), ec::jac_mul(c2, BTpk));
-  good = good && ec::jac_eq_aff(l1, R1) && ec::jac_eq_aff(l2, R2);
-  ok[i] = good ? 1 : 0;
+  ok[i] = sig::mta_alpha_holds(al, ec::sc_reduce(a + (size_t)i * 8, 8), Bpk, R1, ec::sc_reduce(z + (size_t)i * 8, 8), BTpk, R2,
+                               ec::sc_reduce(tz + (size_t)i * 8, 8), enc) ? 1 : 0;
 }
 
 // MessageB::b_with_predefined_randomness behind its range-proof stage (:132-148), what mpe_mta_message_b and the bare form

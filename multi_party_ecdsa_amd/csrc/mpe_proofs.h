@@ -5,7 +5,7 @@
 // Included by mpe_lib.hip.  Heavy arithmetic = launch_modexp / launch_modmul; everything else is
 // one-item-per-lane glue (mpe_small.h, mpe_ec.h).
 #pragma once
-#include "mpe_ec.h"
+#include "mpe_sigma_dev.h"
 #include "mpe_internal.h"
 #include "mpe_modinv.h"
 #include "mpe_paillier.h"
@@ -82,30 +82,17 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC ec_add_kernel(int B, const uint
   ec::aff_store(out + (size_t)i * 16, ec::jac_to_aff(r));
 }
 
-// curv DLogProof: pk = sk G, R = rho G, c = H(R, G, pk) mod q, z = rho - c sk
-// (point form and order of the three points: ec::Enc — recalled conventions are run-time properties of the context)
-__device__ inline ec::U256 dlog_challenge(const ec::Aff& R, const ec::Aff& pk, const ec::Enc& enc) {
-  ec::Sha256 s;
-  ec::sha_init(s);
-  const ec::Aff G = ec::aff_gen();
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const int o = enc.ord_dlog[i];
-    ec::sha_chain_point(s, o == 0 ? R : (o == 1 ? G : pk), enc);
-  }
-  const ec::U256 d = ec::sha_final(s);
-  return ec::sc_reduce(d.w, 8);
-}
+// curv DLogProof: the transcript is sig::dlog_prove_body / sig::dlog_verify_body (mpe_sigma_dev.h)
 __global__ void __launch_bounds__(64) MPE_EC_OCC dlog_prove_kernel(int B, ec::Enc enc, const uint32_t* __restrict__ sk, const uint32_t* __restrict__ nonce,
                                   uint32_t* __restrict__ pk, uint32_t* __restrict__ R, uint32_t* __restrict__ z) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B) return;
-  const ec::U256 s = ec::sc_reduce(sk + (size_t)i * 8, 8), k = ec::sc_reduce(nonce + (size_t)i * 8, 8);
-  const ec::Aff Rp = ec::jac_to_aff(ec::jac_mul_gen(k)), P = ec::jac_to_aff(ec::jac_mul_gen(s));
-  const ec::U256 c = dlog_challenge(Rp, P, enc);
+  ec::Aff P, Rp;
+  ec::U256 zz;
+  sig::dlog_prove_body(ec::sc_reduce(sk + (size_t)i * 8, 8), ec::sc_reduce(nonce + (size_t)i * 8, 8), enc, P, Rp, zz);
   ec::aff_store(pk + (size_t)i * 16, P);
   ec::aff_store(R + (size_t)i * 16, Rp);
-  ec::u256_store(z + (size_t)i * 8, ec::sc_sub(k, ec::sc_mul(c, s)));
+  ec::u256_store(z + (size_t)i * 8, zz);
 }
 __global__ void __launch_bounds__(64) MPE_EC_OCC dlog_verify_kernel(int B, ec::Enc enc, const uint32_t* __restrict__ pk, const uint32_t* __restrict__ R,
                                    const uint32_t* __restrict__ z, uint8_t* __restrict__ ok) {
@@ -113,9 +100,7 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC dlog_verify_kernel(int B, ec::E
   if (i >= B) return;
   const ec::Aff P = ec::aff_load(pk + (size_t)i * 16), Rp = ec::aff_load(R + (size_t)i * 16);
   if (!ec::aff_valid(P) || !ec::aff_valid(Rp)) { ok[i] = 0; return; }         // curv rejects such points when it deserialises them
-  const ec::U256 c = dlog_challenge(Rp, P, enc), zz = ec::sc_reduce(z + (size_t)i * 8, 8);
-  const ec::Jac l = ec::jac_add(ec::jac_mul_gen(zz), ec::jac_mul(c, P));
-  ok[i] = ec::jac_eq_aff(l, Rp) ? 1 : 0;
+  ok[i] = sig::dlog_verify_body(P, Rp, ec::sc_reduce(z + (size_t)i * 8, 8), enc) ? 1 : 0;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1,11 +1,13 @@
 // curv sigma proofs and the hash commitment GG20 uses in phases 1, 3 and 6 (un-vendored curv-kzen 0.9),
-// as stand-alone batched entry points — the round pipeline (mpe_gg20.h) computes the same transcripts inline:
+// as stand-alone batched entry points.  The transcripts themselves are the device functions of mpe_sigma_dev.h, which the round
+// pipeline (mpe_gg20.h), GG18 and Lindell call too:
 //   PedersenProof::{prove, verify}        party_i.rs:620-634, rounds.rs:371-378
 //   HomoELGamalProof::{prove, verify}     party_i.rs:778-833
 //   HashCommitment::create_commitment_with_user_defined_randomness   party_i.rs:577-580,654-659
 // One item per lane.  Included by mpe_lib.hip.
 #pragma once
-#include "mpe_gg20.h"
+#include "mpe_internal.h"
+#include "mpe_sigma_dev.h"
 
 namespace mpe {
 
@@ -16,52 +18,23 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC pedersen_prove_kernel(int B, ec
   if (i >= B) return;
   const ec::U256 mm = ec::sc_reduce(m + (size_t)i * 8, 8), rr = ec::sc_reduce(r + (size_t)i * 8, 8);
   const ec::U256 s1 = ec::sc_reduce(s1_in + (size_t)i * 8, 8), s2 = ec::sc_reduce(s2_in + (size_t)i * 8, 8);
-  const ec::Aff G = ec::aff_gen(), H = ec::aff_h2();
   const ec::Aff C = ec::jac_to_aff(ec::jac_add(ec::jac_mul_gen(mm), ec::jac_mul_h2(rr)));
   const ec::Aff a1 = ec::jac_to_aff(ec::jac_mul_gen(s1)), a2 = ec::jac_to_aff(ec::jac_mul_h2(s2));
-  const ec::Aff hp[5] = {G, H, C, a1, a2};
-  const ec::U256 e = gg::hash_points(hp, enc, enc.ord_pedersen);
+  ec::U256 e, z1, z2;
+  sig::pedersen_prove_body(mm, rr, s1, s2, C, a1, a2, enc, e, z1, z2);
   ec::aff_store(p.com + (size_t)i * 16, C);
   ec::u256_store(p.e + (size_t)i * 8, e);
   ec::aff_store(p.a1 + (size_t)i * 16, a1);
   ec::aff_store(p.a2 + (size_t)i * 16, a2);
-  ec::u256_store(p.z1 + (size_t)i * 8, ec::sc_add(s1, ec::sc_mul(e, mm)));
-  ec::u256_store(p.z2 + (size_t)i * 8, ec::sc_add(s2, ec::sc_mul(e, rr)));
+  ec::u256_store(p.z1 + (size_t)i * 8, z1);
+  ec::u256_store(p.z2 + (size_t)i * 8, z2);
 }
 __global__ void __launch_bounds__(64) MPE_EC_OCC pedersen_verify_kernel(int B, ec::Enc enc, mpe_pedersen_proof p, uint8_t* __restrict__ ok) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B) return;
-  const ec::Aff G = ec::aff_gen(), H = ec::aff_h2();
   const ec::Aff C = ec::aff_load(p.com + (size_t)i * 16), a1 = ec::aff_load(p.a1 + (size_t)i * 16), a2 = ec::aff_load(p.a2 + (size_t)i * 16);
   if (!ec::aff_valid(C) || !ec::aff_valid(a1) || !ec::aff_valid(a2)) { ok[i] = 0; return; }
-  const ec::Aff hp[5] = {G, H, C, a1, a2};
-  const ec::U256 e = gg::hash_points(hp, enc, enc.ord_pedersen);
-  const ec::Jac lhs = ec::jac_add(ec::jac_mul_gen(ec::sc_reduce(p.z1 + (size_t)i * 8, 8)), ec::jac_mul_h2(ec::sc_reduce(p.z2 + (size_t)i * 8, 8)));
-  const ec::Jac rhs = ec::jac_add_aff(ec::jac_add_aff(ec::jac_mul(e, C), a1), a2);
-  ok[i] = ec::jac_eq(lhs, rhs) ? 1 : 0;
-}
-// HomoELGamalProof::prove / verify over the statement (G, H, Y, D, E) with the points already loaded: the bodies heg_prove_kernel /
-// heg_verify_kernel and the GG18 phase-5 kernels (mpe_gg18.h) share.  Force-inlined: the points stay in the caller's registers.
-__device__ __forceinline__ void heg_prove_body(const ec::U256& xx, const ec::U256& rr, const ec::U256& s1, const ec::U256& s2, const ec::Aff& G,
-                                               const ec::Aff& H, const ec::Aff& Y, const ec::Aff& D, const ec::Aff& E, const ec::Enc& enc,
-                                               ec::Aff& T, ec::Aff& A3, ec::U256& z1, ec::U256& z2) {
-  A3 = gg::mul_aff(s2, G);
-  T = ec::jac_to_aff(ec::jac_add(ec::jac_mul(s1, H), ec::jac_mul(s2, Y)));
-  const ec::Aff hp[7] = {T, A3, G, H, Y, D, E};
-  const ec::U256 e = gg::hash_points(hp, enc, enc.ord_heg);
-  z1 = ec::u256_is_zero(xx) ? s1 : ec::sc_add(s1, ec::sc_mul(e, xx));
-  z2 = ec::sc_add(s2, ec::sc_mul(e, rr));
-}
-// all seven points must have passed ec::aff_valid
-__device__ __forceinline__ bool heg_verify_body(const ec::Aff& G, const ec::Aff& H, const ec::Aff& Y, const ec::Aff& D, const ec::Aff& E, const ec::Aff& T,
-                                                const ec::Aff& A3, const ec::U256& z1, const ec::U256& z2, const ec::Enc& enc) {
-  const ec::Aff hp[7] = {T, A3, G, H, Y, D, E};
-  const ec::U256 e = gg::hash_points(hp, enc, enc.ord_heg);
-  const ec::Jac l1 = ec::jac_add(ec::jac_mul(z1, H), ec::jac_mul(z2, Y));
-  const ec::Jac r1 = ec::jac_add_aff(ec::jac_mul(e, D), T);
-  const ec::Jac l2 = ec::jac_mul(z2, G);
-  const ec::Jac r2 = ec::jac_add_aff(ec::jac_mul(e, E), A3);
-  return ec::jac_eq(l1, r1) && ec::jac_eq(l2, r2);
+  ok[i] = sig::pedersen_verify_body(C, a1, a2, ec::sc_reduce(p.z1 + (size_t)i * 8, 8), ec::sc_reduce(p.z2 + (size_t)i * 8, 8), enc) ? 1 : 0;
 }
 __global__ void __launch_bounds__(64) MPE_EC_OCC heg_prove_kernel(int B, ec::Enc enc, const uint32_t* __restrict__ x, const uint32_t* __restrict__ r,
                                                        const uint32_t* __restrict__ s1_in, const uint32_t* __restrict__ s2_in,
@@ -74,7 +47,7 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC heg_prove_kernel(int B, ec::Enc
                 D = ec::aff_load(s.D + (size_t)i * 16), E = ec::aff_load(s.E + (size_t)i * 16);
   ec::Aff T, A3;
   ec::U256 z1, z2;
-  heg_prove_body(xx, rr, s1, s2, G, H, Y, D, E, enc, T, A3, z1, z2);
+  sig::heg_prove_body(xx, rr, s1, s2, G, H, Y, D, E, enc, T, A3, z1, z2);
   ec::aff_store(p.T + (size_t)i * 16, T);
   ec::aff_store(p.A3 + (size_t)i * 16, A3);
   ec::u256_store(p.z1 + (size_t)i * 8, z1);
@@ -87,13 +60,13 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC heg_verify_kernel(int B, ec::En
                 D = ec::aff_load(s.D + (size_t)i * 16), E = ec::aff_load(s.E + (size_t)i * 16);
   const ec::Aff T = ec::aff_load(p.T + (size_t)i * 16), A3 = ec::aff_load(p.A3 + (size_t)i * 16);
   if (!(ec::aff_valid(G) && ec::aff_valid(H) && ec::aff_valid(Y) && ec::aff_valid(D) && ec::aff_valid(E) && ec::aff_valid(T) && ec::aff_valid(A3))) { ok[i] = 0; return; }
-  ok[i] = heg_verify_body(G, H, Y, D, E, T, A3, ec::sc_reduce(p.z1 + (size_t)i * 8, 8), ec::sc_reduce(p.z2 + (size_t)i * 8, 8), enc) ? 1 : 0;
+  ok[i] = sig::heg_verify_body(G, H, Y, D, E, T, A3, ec::sc_reduce(p.z1 + (size_t)i * 8, 8), ec::sc_reduce(p.z2 + (size_t)i * 8, 8), enc) ? 1 : 0;
 }
 __global__ void __launch_bounds__(64) MPE_EC_OCC hash_commit_kernel(int B, ec::Enc enc, const uint32_t* __restrict__ P, const uint32_t* __restrict__ blind,
                                                          uint32_t* __restrict__ com) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B) return;
-  ec::u256_store(com + (size_t)i * 8, gg::commit_point(ec::aff_load(P + (size_t)i * 16), blind + (size_t)i * 8, enc));
+  ec::u256_store(com + (size_t)i * 8, sig::commit_point(ec::aff_load(P + (size_t)i * 16), blind + (size_t)i * 8, enc));
 }
 
 }  // namespace mpe

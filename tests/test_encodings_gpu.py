@@ -74,14 +74,18 @@ def test_each_switch_reaches_its_kernels(enc_ctx, keys):
         enc_ctx.set_encoding(ENCS.DEFAULT.as_dict())
 
 
-@pytest.mark.parametrize("name,t,n,signers,B", [("all-alt", 1, 3, [0, 2], 2), ("reordered", 2, 5, [0, 2, 4], 1), ("compressed", 1, 3, [0, 1, 2], 1)])
+@pytest.mark.parametrize("name,t,n,signers,B", [("all-alt", 1, 3, [0, 2], 2), ("reordered", 2, 5, [0, 2, 4], 1), ("compressed", 1, 3, [0, 1, 2], 1),
+                                                ("reordered/serial", 1, 3, [0, 2], 2)])
 def test_whole_signing_sessions_under_an_alternative_profile(keys, name, t, n, signers, B):
     """every round message of every party byte-identical to the per-party oracle under the same profile (all parties in one
-    object, then one object per party exchanging slabs), the signature equal to the default one"""
+    object, then one object per party exchanging slabs), the signature equal to the default one.  "/serial": on a context with
+    conftest.gpu_ctx_serial's options, so that the sessions go through the lane-per-item round kernels (r2a_kernel, r3_kernel,
+    r6_kernel), which small batches do not take by default"""
     from multi_party_ecdsa_amd import engine as E
     from test_gg20_gpu import GpuParty
+    name, _, serial = name.partition("/")
     prof = ENCS.PROFILES[name]
-    ctx = E.Context(0, encoding=prof.as_dict())
+    ctx = E.Context(0, encoding=prof.as_dict(), options={"no_par": 1, "no_adaptive_lanes": 1} if serial else None)
     lk = G.make_local_keys(keys, t, n, signers)
     nonces = G.make_nonces(lk, B, seed=f"enc-gpu-{name}")
     base = G.oracle_sign_ex(lk, nonces, B)
@@ -119,12 +123,14 @@ def test_whole_signing_sessions_under_an_alternative_profile(keys, name, t, n, s
     assert not status.cpu().numpy().any() and np.array_equal(_u32(r_), want["r"]) and np.array_equal(_u32(s_), want["s"])
 
 
-def test_parties_on_different_profiles_reject_each_other_with_the_oracles_status(gpu_ctx, keys):
+@pytest.mark.parametrize("ctx_fixture", ["gpu_ctx", "gpu_ctx_serial"])
+def test_parties_on_different_profiles_reject_each_other_with_the_oracles_status(request, ctx_fixture, keys):
     """party 1's round-1 message is replaced by the one it would have sent under "compressed" (same ciphertexts, other Schnorr
     challenges): the default-profile receiver fails MessageB::verify_proofs_get_alpha with 201 — same status and bad-actor
     arrays from the engine and from the oracle, nobody signs that session"""
     from multi_party_ecdsa_amd import engine as E
     from test_gg20_gpu import GpuParty
+    gpu_ctx = request.getfixturevalue(ctx_fixture)
     t, n, signers, B = 1, 3, [0, 1], 2
     lk = G.make_local_keys(keys, t, n, signers)
     nonces = G.make_nonces(lk, B, seed="enc-gpu-mixed")
