@@ -466,8 +466,9 @@ int mpe_gg20_session_destroy(mpe_gg20_session* sess, void* stream);
  * half-way through the protocol and healthy (finish it with mpe_gg20_complete, or give it up with mpe_gg20_session_abort);
  * MPE_E_HIP when the wipe fails. */
 int mpe_gg20_session_rearm(mpe_gg20_session* sess, const int32_t* d_keyset, const mpe_gg20_nonces* nonces, void* stream);
-/* Gives the running batch up (the caller stops after the offline stage, a peer vanished, a round call returned an error): the
- * nonce-derived state is wiped at once, every round entry point refuses, and mpe_gg20_session_rearm starts the next batch.  A
+/* Gives the running batch up (a peer vanished, a round call returned an error): the
+ * nonce-derived state is wiped at once, every round entry point refuses, and mpe_gg20_session_rearm starts the next batch.  (A caller
+ * that stops after the offline stage to sign later does not abort: mpe_gg20_presig_deposit moves the presignatures into a pool.)  A
  * session whose round call FAILED (MPE_E_NOMEM, MPE_E_HIP) may also be re-armed directly: a long-lived party process is never
  * left with an object it can only destroy. */
 int mpe_gg20_session_abort(mpe_gg20_session* sess, void* stream);
@@ -486,6 +487,81 @@ int mpe_gg20_session_result(const mpe_gg20_session* sess, int32_t* d_status, uin
 /* Fault injection of the reference's own tests (gg_2020/test.rs:282-289,458-465,679-686): the local parties whose signer
  * ordinal is in party_mask double their delta_i (step 5), sigma_i (step 6) or s_i (step 7).  step 0 switches it off. */
 int mpe_gg20_session_fault_inject(mpe_gg20_session* sess, int step, uint32_t party_mask);
+
+/* ---- the presignature pool: offline stages kept, signed online later ----------------------------------------------------
+ * GG20's rounds 0-6 need no message.  `CompletedOfflineStage` (state_machine/sign/rounds.rs:647-661) is a value in the reference: it
+ * leaves `OfflineStage::pick_output` and enters `SignManual::new` when the message arrives.  A pool keeps that value on the device, in
+ * single-use SLOTS, for the n_local parties h_local[] (signer ordinals, as for mpe_gg20_session_create) of `keys`; one slot = one
+ * session: per party k_i [8], sigma_i [8], R [16], per slot the key-set index and a state word.  The pool's memory is its own
+ * allocation; _destroy zeroes it first (and waits for the device: calls on any stream may still use the slots).
+ *
+ *   EMPTY --deposit / import--> READY --sign--> SIGNED --complete--> EMPTY        READY --export--> EMPTY       any --discard--> EMPTY
+ *
+ * Every transition is ONE device-scope compare-and-swap on the slot's state word, taken before any secret of the slot is read; a row
+ * that loses it touches nothing and reports a status.  However calls, streams and duplicate slot indices interleave, at most one
+ * partial signature is ever computed from one k_i.  (A slot is BUSY only while the winning row of a running call works on it.)
+ * Which slots are free is the caller's policy: every call takes the slot indices d_slot [count] it is to use.  Row statuses (0 = done):
+ *   801 deposit: slot out of range | 802 deposit: slot not EMPTY | 803 deposit: the session had failed in that row (a local party's
+ *       status is non-zero; it stays readable through mpe_gg20_session_result)
+ *   811 sign: slot out of range | 812 sign: slot not READY (empty, already signed, or claimed by another row or another call)
+ *   821 complete: slot out of range | 822 complete: slot not SIGNED | 701 output_signature: verify failed (party_i.rs:873-936, as
+ *       mpe_gg20_complete reports it)
+ *   831 export / import: slot out of range | 832 import: record refused | 833 export: slot not READY | 834 import: slot not EMPTY
+ * Every d_status may be NULL.
+ *
+ * mpe_gg20_presig_deposit   sess must be behind round 6 (the next call would be mpe_gg20_round7) with the pool's keys and local
+ *     parties, else MPE_E_ARG and nothing is touched.  Row b of the session goes to slot d_slot[b] ([batch]) when every local party's
+ *     status in it is 0 and the slot is EMPTY.  In EVERY case the session's nonce-derived state is then wiped as
+ *     mpe_gg20_session_abort wipes it and the rounds refuse until mpe_gg20_session_rearm: the only live copy of k_i is the pool's.
+ * mpe_gg20_presig_sign      `Round7::new` / phase7_local_sig (party_i.rs:850-871) for READY slots: d_msg [count][8] as
+ *     mpe_gg20_round7 takes it, d_s_i [n_local][count][8] = m k_i + r sigma_i (zero rows unless status 0).  The slot keeps m, r and its
+ *     own s_i for the completion; k_i and sigma_i are zeroed by the same kernel.  Among duplicate indices exactly one row wins.
+ * mpe_gg20_presig_complete  `SignManual::complete` (sign.rs:625-646; output_signature + verify) for SIGNED slots: d_in = the partial
+ *     signatures of all S senders including the own, sender j's [count][8] block at record h_in_off[j] (HOST array; NULL = j * count);
+ *     d_r, d_s [n_local][count][8], d_recid, d_status [n_local][count]: low-s normalised with the recid flip, zero unless status 0.
+ *     The slot returns to EMPTY whatever the verdict.
+ * mpe_gg20_presig_export    moves READY slots out (READY -> EMPTY, secrets zeroed in the pool): the record is then the only copy.
+ * mpe_gg20_presig_import    EMPTY -> READY.  Refused (832): a version, signer-set mask, number of local parties or ordinals that are
+ *     not the pool's; a key-set index out of range or a y that is not that key set's; an R that is no valid curve point; a k_i outside
+ *     (0, q) or a sigma_i outside [0, q).
+ *     The RECORD, mpe_gg20_presig_record_words(pool) = 28 + 32 n_local little-endian 32-bit words:
+ *       [0] MPE_GG20_PRESIG_RECORD_VERSION | [1] signer-set mask (bit = party index) | [2] n_local | [3..10] local ordinals (unused: 0)
+ *       | [11] key-set index | [12..27] y (x[8] | y[8]) | then per local party k_i [8] | sigma_i [8] | R [16]
+ *     This layout is this library's own: the reference derives no `Serialize` for `CompletedOfflineStage`, there is no byte parity to
+ *     claim.  A record holds k_i in the clear: importing one record twice, or into two pools, is the nonce reuse the slots prevent.
+ * mpe_gg20_presig_discard   READY, SIGNED or EMPTY -> EMPTY with the wipe (a slot that a running call on another stream holds BUSY is
+ *     left to that call).
+ * mpe_gg20_presig_pool_audit  h_out[0..3] = slots that are EMPTY, READY, SIGNED, BUSY; h_out[4] = non-zero words of k_i, sigma_i in
+ *     slots that are not READY (must be 0).  Synchronises the stream. */
+#define MPE_GG20_PRESIG_RECORD_VERSION 1
+#define MPE_GG20_PRESIG_DEPOSIT_RANGE 801
+#define MPE_GG20_PRESIG_DEPOSIT_NOT_EMPTY 802
+#define MPE_GG20_PRESIG_SESSION_FAILED 803
+#define MPE_GG20_PRESIG_SIGN_RANGE 811
+#define MPE_GG20_PRESIG_SIGN_NOT_READY 812
+#define MPE_GG20_PRESIG_COMPLETE_RANGE 821
+#define MPE_GG20_PRESIG_COMPLETE_NOT_SIGNED 822
+#define MPE_GG20_PRESIG_VERIFY_FAILED 701
+#define MPE_GG20_PRESIG_RECORD_RANGE 831
+#define MPE_GG20_PRESIG_IMPORT_REFUSED 832
+#define MPE_GG20_PRESIG_EXPORT_NOT_READY 833
+#define MPE_GG20_PRESIG_IMPORT_NOT_EMPTY 834
+typedef struct mpe_gg20_presig_pool mpe_gg20_presig_pool;
+int mpe_gg20_presig_pool_create(mpe_ctx* ctx, const mpe_gg20_keys* keys, int n_local, const int32_t* h_local, int capacity,
+                                mpe_gg20_presig_pool** out);
+int mpe_gg20_presig_pool_destroy(mpe_gg20_presig_pool* pool);
+int mpe_gg20_presig_pool_capacity(const mpe_gg20_presig_pool* pool);
+int mpe_gg20_presig_record_words(const mpe_gg20_presig_pool* pool);
+int mpe_gg20_presig_deposit(mpe_gg20_presig_pool* pool, mpe_gg20_session* sess, const int32_t* d_slot, int32_t* d_status, void* stream);
+int mpe_gg20_presig_sign(mpe_gg20_presig_pool* pool, int count, const int32_t* d_slot, const uint32_t* d_msg, uint32_t* d_s_i,
+                         int32_t* d_status, void* stream);
+int mpe_gg20_presig_complete(mpe_gg20_presig_pool* pool, int count, const int32_t* d_slot, const uint32_t* d_in, const int64_t* h_in_off,
+                             uint32_t* d_r, uint32_t* d_s, int32_t* d_recid, int32_t* d_status, void* stream);
+int mpe_gg20_presig_export(mpe_gg20_presig_pool* pool, int count, const int32_t* d_slot, uint32_t* d_rec, int32_t* d_status, void* stream);
+int mpe_gg20_presig_import(mpe_gg20_presig_pool* pool, int count, const int32_t* d_slot, const uint32_t* d_rec, int32_t* d_status,
+                           void* stream);
+int mpe_gg20_presig_discard(mpe_gg20_presig_pool* pool, int count, const int32_t* d_slot, void* stream);
+int mpe_gg20_presig_pool_audit(mpe_gg20_presig_pool* pool, int64_t* h_out, void* stream);
 
 /* ---- identifiable abort: src/protocols/multi_party_ecdsa/gg_2020/blame.rs ---------------------------------------- */
 /* Every signer has opened the values the failing phase used; the functions re-derive the public ciphertexts from the

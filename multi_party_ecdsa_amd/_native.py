@@ -12,6 +12,12 @@ LIB_PATH = os.environ.get("MPE_LIB_PATH") or os.path.join(_HERE, "libmpecdsa_hip
 
 MPE_OK, MPE_E_ARG, MPE_E_HIP, MPE_E_NOMEM = 0, -1, -2, -3
 GG20_STATUS_BAD_NONCE = 91                    # include/mpecdsa_hip.h MPE_GG20_STATUS_BAD_NONCE
+# the presignature pool's row statuses and record version (include/mpecdsa_hip.h MPE_GG20_PRESIG_*)
+PRESIG_RECORD_VERSION = 1
+PRESIG_DEPOSIT_RANGE, PRESIG_DEPOSIT_NOT_EMPTY, PRESIG_SESSION_FAILED = 801, 802, 803
+PRESIG_SIGN_RANGE, PRESIG_SIGN_NOT_READY = 811, 812
+PRESIG_COMPLETE_RANGE, PRESIG_COMPLETE_NOT_SIGNED, PRESIG_VERIFY_FAILED = 821, 822, 701
+PRESIG_RECORD_RANGE, PRESIG_IMPORT_REFUSED, PRESIG_EXPORT_NOT_READY, PRESIG_IMPORT_NOT_EMPTY = 831, 832, 833, 834
 
 
 def gg20_status_pass_failed(rc):              # MPE_GG20_STATUS_PASS_FAILED(rc)
@@ -181,6 +187,17 @@ def _load():
         "mpe_gg20_session_fault_inject": (ip, [vp, ip, C.c_uint32]),
         "mpe_gg20_session_rearm": (ip, [vp, i32p, C.POINTER(Gg20Nonces), vp]),
         "mpe_gg20_session_abort": (ip, [vp, vp]),
+        "mpe_gg20_presig_pool_create": (ip, [vp, vp, ip, C.POINTER(C.c_int32), ip, C.POINTER(vp)]),
+        "mpe_gg20_presig_pool_destroy": (ip, [vp]),
+        "mpe_gg20_presig_pool_capacity": (ip, [vp]),
+        "mpe_gg20_presig_record_words": (ip, [vp]),
+        "mpe_gg20_presig_deposit": (ip, [vp, vp, i32p, i32p, vp]),
+        "mpe_gg20_presig_sign": (ip, [vp, ip, i32p, u32p, u32p, i32p, vp]),
+        "mpe_gg20_presig_complete": (ip, [vp, ip, i32p, u32p, C.POINTER(C.c_int64), u32p, u32p, i32p, i32p, vp]),
+        "mpe_gg20_presig_export": (ip, [vp, ip, i32p, u32p, i32p, vp]),
+        "mpe_gg20_presig_import": (ip, [vp, ip, i32p, u32p, i32p, vp]),
+        "mpe_gg20_presig_discard": (ip, [vp, ip, i32p, vp]),
+        "mpe_gg20_presig_pool_audit": (ip, [vp, C.POINTER(C.c_int64), vp]),
         "mpe_gg20_blame5": (ip, [vp, vp, ip, i32p, C.POINTER(Blame5In), u32p, vp]),
         "mpe_gg20_blame6": (ip, [vp, vp, ip, i32p, C.POINTER(Blame6In), u32p, vp]),
         "mpe_gg20_blame7": (ip, [vp, ip, ip, C.POINTER(Blame7In), u32p, vp]),
@@ -305,7 +322,10 @@ EXPORTED = ["mpe_version", "mpe_last_error", "mpe_ctx_create", "mpe_ctx_destroy"
             "mpe_hash_commit_bigint", "mpe_lindell_keygen_first_msg", "mpe_lindell_keygen_verify_first_msg", "mpe_lindell_eph_first_msg",
             "mpe_lindell_eph_verify_first_msg", "mpe_ecdsa_verify", "mpe_scalar_mul", "mpe_lindell_ntilde_generate",
             "mpe_gg18_sign_keys", "mpe_gg18_message_b", "mpe_gg18_phase2", "mpe_gg18_phase4", "mpe_gg18_phase5a", "mpe_gg18_phase5c",
-            "mpe_gg18_phase5d", "mpe_gg18_output_signature"]
+            "mpe_gg18_phase5d", "mpe_gg18_output_signature",
+            "mpe_gg20_presig_pool_create", "mpe_gg20_presig_pool_destroy", "mpe_gg20_presig_pool_capacity", "mpe_gg20_presig_record_words",
+            "mpe_gg20_presig_deposit", "mpe_gg20_presig_sign", "mpe_gg20_presig_complete", "mpe_gg20_presig_export", "mpe_gg20_presig_import",
+            "mpe_gg20_presig_discard", "mpe_gg20_presig_pool_audit"]
 
 
 def check(rc, what):

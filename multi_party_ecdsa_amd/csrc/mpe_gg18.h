@@ -33,11 +33,6 @@ struct Dim {
 __device__ __forceinline__ void zero_words(uint32_t* p, int n) { for (int j = 0; j < n; ++j) p[j] = 0u; }
 // the first failure sticks
 __device__ __forceinline__ void fail(int32_t* status, int pi, int code) { if (status[pi] == 0) status[pi] = code; }
-// a > b as 256-bit integers
-__device__ __forceinline__ bool u256_gt(const ec::U256& a, const ec::U256& b) {
-  for (int j = 7; j >= 0; --j) if (a.w[j] != b.w[j]) return a.w[j] > b.w[j];
-  return false;
-}
 
 // SignKeys::create (:385-406) with k_i, gamma_i handed in: w_i = lambda_i x_i, g_w_i, g_gamma_i; status 0 or 91
 __global__ void __launch_bounds__(64) MPE_EC_OCC sign_keys_kernel(Dim d, const uint32_t* __restrict__ x_i, const uint32_t* __restrict__ k_in,
@@ -254,16 +249,9 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC output_kernel(Dim d, const uint
   ec::U256 s = ec::sc_reduce(s_own + (size_t)pi * 8, 8);
   for (int j = 0; j < d.S; ++j) if (j != i) s = ec::sc_add(s, ec::sc_reduce(s_all + ((size_t)j * d.B + b) * 8, 8));            // :675
   const ec::U256 r = ec::sc_reduce(Rp.x.w, 8), ry = ec::sc_reduce(Rp.y.w, 8);
-  int recid = (int)(ry.w[0] & 1u);                                                                      // :697-698
-  const ec::U256 neg = ec::sc_neg(s);
-  if (u256_gt(s, neg)) { s = neg; recid ^= 1; }                                                         // :699-703
-  bool okv = !ec::u256_is_zero(s);                                                                      // invert().ok_or(InvalidSig)  :715
-  if (okv) {
-    const ec::U256 bi = ec::sc_inv(s), u1 = ec::sc_mul(ec::sc_reduce(msg + (size_t)b * 8, 8), bi), u2 = ec::sc_mul(r, bi);
-    const ec::Aff Vp = ec::jac_to_aff(ec::jac_add(ec::jac_mul_gen(u1), ec::jac_mul(u2, Y)));
-    okv = !Vp.inf && ec::u256_eq(ec::sc_reduce(Vp.x.w, 8), r);                                          // :725-731
-  }
-  if (!okv) { fail(status, pi, 601); return; }
+  // the recid of :697-698, the low-s flip of :699-703, invert().ok_or(InvalidSig) :715 and the check of :725-731: GG20's, one definition
+  int recid;
+  if (!gg::output_signature_check(s, recid, ec::sc_reduce(msg + (size_t)b * 8, 8), r, ry, y + (size_t)b * 16)) { fail(status, pi, 601); return; }
   ec::u256_store(r_out + (size_t)pi * 8, r);
   ec::u256_store(s_out + (size_t)pi * 8, s);
   recid_out[pi] = recid;

@@ -632,6 +632,26 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r7_kernel(Dim d, const uint32_t
   if (fault_step == 7 && ((fault_mask >> d.loc[pi % d.L]) & 1u)) si = ec::sc_add(si, si);              // test.rs:679-686
   ec::u256_store(s_i + (size_t)pi * 8, si);
 }
+// output_signature + verify (party_i.rs:873-936) behind the sum: s is normalised to the low half with the recid flip (recid starts as
+// the parity of R.y, `ry`), then the plain ECDSA check u1 G + u2 y == r under the key y16 (x[8] | y[8]).  false: the reference's
+// InvalidSig.  The one definition: complete_kernel, the presignature pool's presig_complete_kernel (mpe_presig.h) and GG18's output_kernel.
+__device__ __forceinline__ bool output_signature_check(ec::U256& s, int& recid, const ec::U256& m, const ec::U256& r, const ec::U256& ry,
+                                                       const uint32_t* y16) {
+  recid = (int)(ry.w[0] & 1u);
+  const ec::U256 neg = ec::sc_neg(s);
+  {  // if s > q - s: s = q - s, recid ^= 1
+    bool gt = false;
+    for (int j = 7; j >= 0; --j) { if (s.w[j] != neg.w[j]) { gt = s.w[j] > neg.w[j]; break; } }
+    if (gt) { s = neg; recid ^= 1; }
+  }
+  bool okv = !ec::u256_is_zero(s);
+  if (okv) {
+    const ec::U256 bi = ec::sc_inv(s), u1 = ec::sc_mul(m, bi), u2 = ec::sc_mul(r, bi);
+    const ec::Aff V = ec::jac_to_aff(ec::jac_add(ec::jac_mul_gen(u1), ec::jac_mul(u2, ec::aff_load(y16))));
+    okv = !V.inf && ec::u256_eq(ec::sc_reduce(V.x.w, 8), r);
+  }
+  return okv;
+}
 // SignManual::complete -> output_signature + verify (party_i.rs:873-936); outputs are [L][B], zero unless status == 0
 __global__ void __launch_bounds__(64) MPE_EC_OCC complete_kernel(Dim d, Slab in6, const uint32_t* __restrict__ R, const uint32_t* __restrict__ mq,
                           const uint32_t* __restrict__ rq, const uint32_t* __restrict__ s_i, const uint32_t* __restrict__ y,
@@ -644,19 +664,8 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC complete_kernel(Dim d, Slab in6
   for (int j = 0; j < d.S; ++j) if (j != i) s = ec::sc_add(s, ec::sc_reduce(rec_of(in6, j, b) + M7.s_i.off, 8));
   const ec::U256 m = ec::u256_load(mq + (size_t)pi * 8), r = ec::u256_load(rq + (size_t)pi * 8);
   const ec::U256 ry = ec::sc_reduce(R + (size_t)pi * 16 + 8, 8);
-  int recid = (int)(ry.w[0] & 1u);
-  const ec::U256 neg = ec::sc_neg(s);
-  {  // if s > q - s: s = q - s, recid ^= 1
-    bool gt = false;
-    for (int j = 7; j >= 0; --j) { if (s.w[j] != neg.w[j]) { gt = s.w[j] > neg.w[j]; break; } }
-    if (gt) { s = neg; recid ^= 1; }
-  }
-  bool okv = !ec::u256_is_zero(s);
-  if (okv) {
-    const ec::U256 bi = ec::sc_inv(s), u1 = ec::sc_mul(m, bi), u2 = ec::sc_mul(r, bi);
-    const ec::Aff V = ec::jac_to_aff(ec::jac_add(ec::jac_mul_gen(u1), ec::jac_mul(u2, ec::aff_load(y + (size_t)ks_of(d, b) * 16))));
-    okv = !V.inf && ec::u256_eq(ec::sc_reduce(V.x.w, 8), r);
-  }
+  int recid;
+  const bool okv = output_signature_check(s, recid, m, r, ry, y + (size_t)ks_of(d, b) * 16);
   const size_t nPI = (size_t)d.B * d.L;
   if (!okv) fail(status + 8 * nPI, bad + 8 * nPI, pi, 701, 0);
   const bool good = resolve_status(status, nPI, pi, NR - 1, nullptr, nullptr) == 0;
@@ -1428,7 +1437,8 @@ int mpe_gg20_session_rearm(mpe_gg20_session* s, const int32_t* d_keyset, const m
 }
 
 int mpe_gg20_session_abort(mpe_gg20_session* s, void* stream) {
-  // the caller gives the running batch up (it stopped after the offline stage, a peer vanished, a round call failed): everything
+  // the caller gives the running batch up (a peer vanished, a round call failed; stopping after the offline stage to sign later is
+  // mpe_gg20_presig_deposit, which wipes the same way): everything
   // nonce-derived is wiped now and the object waits for mpe_gg20_session_rearm; the round entry points refuse until then
   if (!s) return MPE_E_ARG;
   const hipError_t em = mpe::gg::wipe_batch_state(s, (hipStream_t)stream);

@@ -608,6 +608,176 @@ def gg20_sign(ctx, keys, nonces, B, dedup_verify=False, chunk=0, want_R=False, k
     return (r, s, recid, status, R) if want_R else (r, s, recid, status)
 
 
+class PresigPool:
+    """Device-resident presignatures in single-use slots (`mpe_gg20_presig_*`): `CompletedOfflineStage` of `capacity` sessions for the
+    local parties `local` (signer ordinals), kept until the message arrives.  The C-ABI is mechanism only; this object owns the POLICY:
+    a host-side free list that hands slots to `deposit` / `import_` and takes them back when a row failed, a signature completed, or
+    the slots were exported or discarded.  Slot arguments are lists, numpy arrays or device int32 tensors."""
+    STATES = ("EMPTY", "READY", "SIGNED", "BUSY")
+
+    def __init__(self, ctx, keys, local, capacity):
+        self.ctx, self.keys, self.local, self.capacity = ctx, keys, [int(x) for x in local], int(capacity)
+        self.S, self.L = keys.S, len(self.local)
+        lc = (C.c_int32 * self.L)(*self.local)
+        h = C.c_void_p()
+        N_.check(N_.lib.mpe_gg20_presig_pool_create(ctx.h, keys.h, self.L, lc, self.capacity, C.byref(h)), "mpe_gg20_presig_pool_create")
+        self.h = h
+        self.capacity = N_.lib.mpe_gg20_presig_pool_capacity(h)
+        self.record_words = N_.lib.mpe_gg20_presig_record_words(h)
+        self._used = set()                       # slots the free list has handed out (or the caller named) and not got back
+        self._pending = []                       # (slots, device status, rows-per-slot) of calls whose freed slots are not yet counted
+        self.last_status = None                  # numpy row statuses of the last deposit / import_
+
+    # ---- the free list -----------------------------------------------------------------------------------------------------
+    def _slots(self, slots):
+        if torch.is_tensor(slots):
+            return slots.to(device=self.ctx.device, dtype=torch.int32).contiguous()
+        return torch.from_numpy(np.ascontiguousarray(slots, dtype=np.int32)).to(self.ctx.device)
+
+    def _reap(self):
+        """takes back the slots that completed, exported or discarded rows have emptied"""
+        for d_slot, d_status in self._pending:
+            sl = d_slot.cpu().numpy()
+            ok = np.ones(len(sl), dtype=bool) if d_status is None else (d_status.cpu().numpy().reshape(-1, len(sl)) < 800).all(axis=0)
+            self._used.difference_update(int(x) for x in sl[ok])
+        self._pending = []
+
+    def free_slots(self):
+        self._reap()
+        return self.capacity - len(self._used)
+
+    def _take(self, count):
+        self._reap()
+        out = [s for s in range(self.capacity) if s not in self._used][:count]
+        if len(out) < count:
+            raise N_.MpeError(f"presignature pool: {count} slots wanted, {len(out)} free")
+        return out
+
+    def _filled(self, slots, status, chosen_by_caller):
+        """after deposit / import_: the rows that filled their slot keep it; returns the usable slots, -1 for the other rows"""
+        self.last_status = status
+        good = status == 0
+        if chosen_by_caller:
+            self._used.update(int(x) for x in np.asarray(slots)[good])
+        else:
+            self._used.difference_update(int(x) for x in np.asarray(slots)[~good])
+        return np.where(good, np.asarray(slots, dtype=np.int32), -1).astype(np.int32)
+
+    # ---- the calls ---------------------------------------------------------------------------------------------------------------
+    def deposit(self, session, slots=None):
+        """moves the presignatures of a session behind round 6 into free slots (or into `slots`, one per session row) and wipes the
+        session, which then waits for rearm().  Returns the usable slots [B] (numpy int32; -1 where the row failed: last_status)."""
+        mine = slots is None
+        if mine:
+            slots = self._take(session.B)
+            self._used.update(slots)
+        d_slot = self._slots(slots)
+        if d_slot.numel() != session.B:
+            raise ValueError("deposit: one slot per session row")
+        d_status = torch.empty((session.B,), dtype=torch.int32, device=self.ctx.device)
+        try:
+            N_.check(N_.lib.mpe_gg20_presig_deposit(self.h, session.h, _ptr(d_slot), _ptr(d_status), self.ctx.stream()), "mpe_gg20_presig_deposit")
+        except N_.MpeError:
+            if mine:
+                self._used.difference_update(slots)
+            raise
+        return self._filled(d_slot.cpu().numpy(), d_status.cpu().numpy(), not mine)
+
+    def sign(self, slots, msg):
+        """`Round7::new` for READY slots: (s_i [L, count, 8], status [count]) device tensors; msg [count, 8] as round 7 takes it"""
+        d_slot = self._slots(slots)
+        count = d_slot.numel()
+        s_i = torch.empty((self.L, count, 8), dtype=torch.int32, device=self.ctx.device)
+        status = torch.empty((count,), dtype=torch.int32, device=self.ctx.device)
+        N_.check(N_.lib.mpe_gg20_presig_sign(self.h, count, _ptr(d_slot), _ptr(msg), _ptr(s_i), _ptr(status), self.ctx.stream()), "mpe_gg20_presig_sign")
+        return s_i, status
+
+    def complete(self, slots, d_in, in_off=None):
+        """`SignManual::complete` for SIGNED slots.  d_in: the partial signatures of all S senders (sender j's [count][8] block at record
+        in_off[j], default j * count).  Returns dict r, s [L, count, 8], recid, status [L, count]; the slots are EMPTY afterwards."""
+        d_slot = self._slots(slots)
+        count, L, dv = d_slot.numel(), self.L, self.ctx.device
+        o = dict(r=torch.empty((L, count, 8), dtype=torch.int32, device=dv), s=torch.empty((L, count, 8), dtype=torch.int32, device=dv),
+                 recid=torch.empty((L, count), dtype=torch.int32, device=dv), status=torch.empty((L, count), dtype=torch.int32, device=dv))
+        off = None if in_off is None else (C.c_int64 * self.S)(*[int(x) for x in in_off])
+        N_.check(N_.lib.mpe_gg20_presig_complete(self.h, count, _ptr(d_slot), _ptr(d_in), off, _ptr(o["r"]), _ptr(o["s"]), _ptr(o["recid"]),
+                                                 _ptr(o["status"]), self.ctx.stream()), "mpe_gg20_presig_complete")
+        self._pending.append((d_slot, o["status"]))          # 0 and 701 emptied the slot, 821 / 822 did not
+        return o
+
+    def export(self, slots):
+        """READY slots -> (records [count, record_words], status [count]); the slots are EMPTY afterwards, the records the only copy"""
+        d_slot = self._slots(slots)
+        count = d_slot.numel()
+        rec = torch.empty((count, self.record_words), dtype=torch.int32, device=self.ctx.device)
+        status = torch.empty((count,), dtype=torch.int32, device=self.ctx.device)
+        N_.check(N_.lib.mpe_gg20_presig_export(self.h, count, _ptr(d_slot), _ptr(rec), _ptr(status), self.ctx.stream()), "mpe_gg20_presig_export")
+        self._pending.append((d_slot, status))
+        return rec, status
+
+    def import_(self, records, slots=None):
+        """records [count, record_words] (device int32) -> free slots (or `slots`); returns the usable slots, -1 where refused"""
+        count = records.shape[0]
+        mine = slots is None
+        if mine:
+            slots = self._take(count)
+            self._used.update(slots)
+        d_slot = self._slots(slots)
+        status = torch.empty((count,), dtype=torch.int32, device=self.ctx.device)
+        N_.check(N_.lib.mpe_gg20_presig_import(self.h, count, _ptr(d_slot), _ptr(records.contiguous()), _ptr(status), self.ctx.stream()),
+                 "mpe_gg20_presig_import")
+        return self._filled(d_slot.cpu().numpy(), status.cpu().numpy(), not mine)
+
+    def discard(self, slots):
+        d_slot = self._slots(slots)
+        N_.check(N_.lib.mpe_gg20_presig_discard(self.h, d_slot.numel(), _ptr(d_slot), self.ctx.stream()), "mpe_gg20_presig_discard")
+        self._pending.append((d_slot[(d_slot >= 0) & (d_slot < self.capacity)], None))
+
+    def audit(self):
+        """dict EMPTY, READY, SIGNED, BUSY (slots per state) and stray (non-zero words of k_i, sigma_i outside READY slots: must be 0)"""
+        out = (C.c_int64 * 5)()
+        N_.check(N_.lib.mpe_gg20_presig_pool_audit(self.h, out, self.ctx.stream()), "mpe_gg20_presig_pool_audit")
+        return dict(zip(self.STATES + ("stray",), [int(x) for x in out]))
+
+    def close(self):
+        if self.h:
+            N_.lib.mpe_gg20_presig_pool_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def gg20_presign(ctx, keys, nonces, B, pool, keyset=None, dedup_verify=False):
+    """The offline stage alone: rounds 0-6 of B sessions with every signer local (nonces: [B][S] layout, `msg` not needed), deposited
+    into `pool` (a PresigPool over all S signers of `keys`).  Returns the usable slots [B] (numpy int32; -1 where the session failed)."""
+    sess = Gg20Session(ctx, keys, B, list(range(keys.S)), nonces, keyset=keyset, dedup_verify=dedup_verify)
+    try:
+        prev = None
+        for rnd in range(7):
+            prev = sess.round(rnd, d_in=prev)                # an output [L, B, W] is the next round's input
+        return pool.deposit(sess)
+    finally:
+        sess.close()
+        ctx.wipe()                                           # the composites' workspace held nonce-derived values, as after mpe_gg20_sign
+
+
+def gg20_sign_online(pool, slots, msg):
+    """The online step for a pool that holds every signer: sign + complete.  slots: distinct READY slots; msg [count, 8].  Returns what
+    gg20_sign returns: r, s [count, 8], recid, status [count] (the smallest non-zero party status, or the sign call's 811 / 812)."""
+    d_slot = pool._slots(slots)
+    s_i, st7 = pool.sign(d_slot, msg)
+    res = pool.complete(torch.where(st7 == 0, d_slot, torch.full_like(d_slot, -1)), s_i)      # a row that lost the claim completes nothing
+    st = res["status"]
+    big = torch.where(st == 0, torch.full_like(st, 2 ** 31 - 1), st).amin(dim=0)
+    status = torch.where(st7 != 0, st7, torch.where(big == 2 ** 31 - 1, torch.zeros_like(big), big))
+    good = status == 0
+    return res["r"][0] * good[:, None], res["s"][0] * good[:, None], res["recid"][0] * good, status
+
+
 PLACE_PARTY, PLACE_ROTATED = 0, 1
 
 
