@@ -162,14 +162,26 @@ struct Paillier {
   // `Paillier::keypair()` (party_i.rs:160) x count, on the device: p, q from streams counter | 0 << 56, counter | 1 << 56 of `seed` (32 bytes,
   // never reused with the same counter); a key whose search gave up is all zero and counts in `failed`
   static Keypairs keypair(Context& ctx, const uint8_t* seed32, uint64_t counter, int count) {
+    return mint(ctx, seed32, counter, count, mpe_paillier_keygen, "mpe_paillier_keygen");
+  }
+  // `Paillier::keypair_safe_primes()` (`Keys::create_safe_prime`, party_i.rs:179-199: "we recommend using safe primes if the code is used in
+  // production") x count: the same streams, p and q the first SAFE primes of the sequences keypair() walks — one (seed, counter) mints one
+  // key, the plain or the safe one; ~1000 times the search of keypair()
+  static Keypairs keypair_safe_primes(Context& ctx, const uint8_t* seed32, uint64_t counter, int count) {
+    return mint(ctx, seed32, counter, count, mpe_paillier_keygen_safe_primes, "mpe_paillier_keygen_safe_primes");
+  }
+ private:
+  using KeygenFn = int (*)(mpe_ctx*, int, const uint8_t*, uint64_t, int, uint32_t*, uint32_t*, uint32_t*, int32_t*, void*);
+  static Keypairs mint(Context& ctx, const uint8_t* seed32, uint64_t counter, int count, KeygenFn fn, const char* what) {
     Dev<uint32_t> dp((size_t)count * W_PRIME, true), dq((size_t)count * W_PRIME, true), dn((size_t)count * W_N);
     Dev<int32_t> df(std::vector<int32_t>(1, 0));
-    check(mpe_paillier_keygen(ctx.get(), count, seed32, counter, 0, dp.get(), dq.get(), dn.get(), df.get(), nullptr), "mpe_paillier_keygen");
+    check(fn(ctx.get(), count, seed32, counter, 0, dp.get(), dq.get(), dn.get(), df.get(), nullptr), what);
     ctx.sync();
     Keypairs k{down(dp, W_PRIME), down(dq, W_PRIME), down(dn, W_N), 0};
     k.failed = df.download()[0];
     return k;
   }
+ public:
   // `Paillier::encrypt_with_chosen_randomness(&ek, RawPlaintext::from(m), &Randomness::from(r))`   mta/mod.rs:68-75,133-137
   template <class Keys>
   static Batch encrypt_with_chosen_randomness(Context& ctx, const Keys& ek, const Index& key_idx, const Batch& m, const Batch& r) {

@@ -81,6 +81,7 @@ int mpe_ctx_set_device_share(mpe_ctx* ctx, int contexts);
  *                  no_crt_n (the provers' r^e mod N on the 2048-bit ladder instead of through p | q)
  *   integers       fb_window_bits 4..16 | window_bits 0 (auto), 2..6 | wide_div 1..64 | xwide_div 0 (off).. | waves_per_cu 1..8
  *                  fb_budget_mb | fb_split 0 (auto)..64 | sampler_max_attempts 1.. (default 128)
+ *                  safe_pass_log 16..26 (default 24: mpe_sample_safe_prime fills a pass with about 2^24 candidates)
  *   names          grid = equal | full | hybrid
  * MPE_E_ARG (and mpe_last_error) for an unknown key or a value out of range.  mpe_ctx_get_option returns the integer form;
  * mpe_ctx_option_count / _name enumerate the integer-valued keys. */
@@ -805,16 +806,43 @@ int mpe_is_probable_prime(mpe_ctx* ctx, int batch, const uint32_t* d_n, int roun
  * `batch` nor the other items.  bits must be 1024.  Synchronises the stream (once per pass over the unfinished items). */
 int mpe_sample_prime(mpe_ctx* ctx, int batch, const uint8_t* h_seed32, uint64_t stream_id, int bits, int max_attempts, uint32_t* d_out,
                      int32_t* d_attempt, int32_t* d_fail, void* stream);
+/* kzen-paillier `sample_safe_prime` [RECALLED]: loop { q = sample_prime(bits); if is_prime((q - 1) / 2) return q } — the key generation
+ * the reference recommends "if the code is used in production" (`Keys::create_safe_prime`, party_i.rs:179-199).  Every call of
+ * sample_prime goes on with fresh draws, so on the statement above: d_out [batch][32] = the candidate c of the LOWEST attempt
+ * < max_attempts (0 = 2^24, the largest value) for which c AND (c - 1) / 2 pass mpe_is_probable_prime with 8 rounds; d_attempt, d_fail,
+ * the give-up (zero row, -1, a count; probability ~e^-44 at the default) and the independence of `batch` as for mpe_sample_prime.
+ * A result costs ~380 000 attempts (mpe_sample_prime: ~355).  bits must be 1024.  Synchronises the stream once per pass (about
+ * 2^safe_pass_log candidates whatever the batch, at most 2^20 attempts of an item; the option changes no result).  Workspace: three
+ * survivor lists of min(2^safe_pass_log, batch * 2^20) entries, 192 MB at the default from batch 16 on (12 MB at batch 1);
+ * mpe_ntilde_generate_safe_primes reserves it twice. */
+int mpe_sample_safe_prime(mpe_ctx* ctx, int batch, const uint8_t* h_seed32, uint64_t stream_id, int bits, int max_attempts, uint32_t* d_out,
+                          int32_t* d_attempt, int32_t* d_fail, void* stream);
+/* UNSTABLE measurement aid (tools/exp_safe_primes.py reads it; it may change or go without a version step; a context serves one thread
+ * at a time, the counters are not synchronised): what the searches of this context have counted so far (the list lengths of their
+ * passes); reset != 0 clears them.
+ * h_out9 = plain search: attempts sieved, survivors of the sieve, of round 1; safe search: attempts sieved, survivors of the sieve's
+ * head, of the whole sieve, of round 1 on c, of round 1 on (c - 1) / 2, of rounds 2..8 on c. */
+int mpe_prime_search_counts(mpe_ctx* ctx, int64_t* h_out9, int reset);
 /* Field f of these two calls draws stream `counter | f << 56` (counter < 2^56; the convention of mpe_gg20_sample_nonces), item = row:
  * f = 0 p, 1 q, 2 p~, 3 q~, 4 h1, 5 xi.  A failed prime or draw zeroes EVERY output row of that item and adds 1 to *d_fail.
  * `Paillier::keypair()`: d_p, d_q [nkeys][32], d_N [nkeys][64] = p q (as in the reference: no retry for a 2047-bit product or p == q). */
 int mpe_paillier_keygen(mpe_ctx* ctx, int nkeys, const uint8_t* h_seed32, uint64_t counter, int max_attempts, uint32_t* d_p, uint32_t* d_q,
                         uint32_t* d_N, int32_t* d_fail, void* stream);
+/* `Paillier::keypair_safe_primes()`: the same arguments and stream fields 0, 1 as mpe_paillier_keygen, p and q through
+ * mpe_sample_safe_prime — the safe key of a (seed, counter) holds the first safe prime of each sequence the plain call walks.  A
+ * (seed, counter) pair therefore mints ONE key: use it for the plain call or for this one, never for both (the two keys would be
+ * drawn from the same keystream). */
+int mpe_paillier_keygen_safe_primes(mpe_ctx* ctx, int nkeys, const uint8_t* h_seed32, uint64_t counter, int max_attempts, uint32_t* d_p,
+                                    uint32_t* d_q, uint32_t* d_N, int32_t* d_fail, void* stream);
 /* `generate_h1_h2_N_tilde()`: N~ = p~ q~, phi = (p~ - 1)(q~ - 1), h1 = sample_below(N~), xi = sample_below(phi) redrawn with fresh
  * bytes (bounded by option sampler_max_attempts) until gcd(xi, phi) = 1, h2 = h1^xi mod N~; outputs xhi = phi - xi and
  * xhi_inv = phi - xi^-1 mod phi (the secrets of the two CompositeDLogProofs).  All rows [count][64]. */
 int mpe_ntilde_generate(mpe_ctx* ctx, int count, const uint8_t* h_seed32, uint64_t counter, int max_attempts, uint32_t* d_Nt, uint32_t* d_h1,
                         uint32_t* d_h2, uint32_t* d_xhi, uint32_t* d_xhi_inv, int32_t* d_fail, void* stream);
+/* `generate_h1_h2_N_tilde()` with the line the reference comments "note, should be safe primes" (party_i.rs:138-139) taken at its
+ * word: p~, q~ (fields 2, 3) through mpe_sample_safe_prime; everything behind them is mpe_ntilde_generate's own body. */
+int mpe_ntilde_generate_safe_primes(mpe_ctx* ctx, int count, const uint8_t* h_seed32, uint64_t counter, int max_attempts, uint32_t* d_Nt,
+                                    uint32_t* d_h1, uint32_t* d_h2, uint32_t* d_xhi, uint32_t* d_xhi_inv, int32_t* d_fail, void* stream);
 
 /* ---- Lindell'17 two-party ECDSA, signing ---------------------------------------------- */
 /* Party two, `PartialSig::compute(ek, encrypted_secret_share, local_share, ephemeral_local_share,

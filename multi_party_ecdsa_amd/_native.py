@@ -261,6 +261,10 @@ def _load():
         "mpe_sample_prime": (ip, [vp, ip, C.c_char_p, C.c_uint64, ip, ip, u32p, i32p, i32p, vp]),
         "mpe_paillier_keygen": (ip, [vp, ip, C.c_char_p, C.c_uint64, ip, u32p, u32p, u32p, i32p, vp]),
         "mpe_ntilde_generate": (ip, [vp, ip, C.c_char_p, C.c_uint64, ip, u32p, u32p, u32p, u32p, u32p, i32p, vp]),
+        "mpe_sample_safe_prime": (ip, [vp, ip, C.c_char_p, C.c_uint64, ip, ip, u32p, i32p, i32p, vp]),
+        "mpe_prime_search_counts": (ip, [vp, C.POINTER(C.c_int64), ip]),
+        "mpe_paillier_keygen_safe_primes": (ip, [vp, ip, C.c_char_p, C.c_uint64, ip, u32p, u32p, u32p, i32p, vp]),
+        "mpe_ntilde_generate_safe_primes": (ip, [vp, ip, C.c_char_p, C.c_uint64, ip, u32p, u32p, u32p, u32p, u32p, i32p, vp]),
         "mpe_hash_commit_bigint": (ip, [vp, ip, u32p, u32p, u32p, vp]),
         "mpe_lindell_keygen_first_msg": (ip, [vp, ip] + [u32p] * 9 + [vp]),
         "mpe_lindell_keygen_verify_first_msg": (ip, [vp, ip] + [u32p] * 7 + [vp, vp]),
@@ -318,6 +322,7 @@ EXPORTED = ["mpe_version", "mpe_last_error", "mpe_ctx_create", "mpe_ctx_destroy"
             "mpe_ctx_option_name", "mpe_comm_library", "mpe_gg20_pipeline_ticket_rc", "mpe_gg20_pipeline_inject_fault",
             "mpe_gg20_pipeline_set_deadline_us", "mpe_gg20_pipeline_set_eager", "mpe_gg20_pipeline_poll", "mpe_gg20_pipeline_counters",
             "mpe_is_probable_prime", "mpe_sample_prime", "mpe_paillier_keygen", "mpe_ntilde_generate",
+            "mpe_sample_safe_prime", "mpe_prime_search_counts", "mpe_paillier_keygen_safe_primes", "mpe_ntilde_generate_safe_primes",
             "mpe_vss_share", "mpe_keygen_construct_keypair", "mpe_keygen_verify_round3",
             "mpe_hash_commit_bigint", "mpe_lindell_keygen_first_msg", "mpe_lindell_keygen_verify_first_msg", "mpe_lindell_eph_first_msg",
             "mpe_lindell_eph_verify_first_msg", "mpe_ecdsa_verify", "mpe_scalar_mul", "mpe_lindell_ntilde_generate",

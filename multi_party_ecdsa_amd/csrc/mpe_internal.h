@@ -44,6 +44,7 @@ struct mpe_ctx {
   int modexp_waves_per_cu = 8;    // 2 waves/SIMD: the montmul loop holds ~230 VGPRs and already issues back-to-back
   int fb_split = 0;               // fixed-base ladders: lane groups that share one item's windows (0 = chosen per launch, mpe_fixedbase.h)
   int gg20_trace = 0;             // option gg20_trace: synchronise and report after every composite of a round
+  int safe_pass_log = 24;         // the safe prime search fills a pass with about 2^safe_pass_log candidates (option safe_pass_log, mpe_primes.h)
   int sampler_max_attempts = 128; // rejection loops of the device sampler give up after this many candidates (mpe_sample.h)
   int no_primaries = 0;           // option no_primaries: launches with at most one unit per SIMD keep static units (the queue of multi-pass launches stays)
   int no_elect = 0;               // option no_elect: the dispatcher's placement is taken as it comes (rounds 1-5), mpe_sched.h
@@ -75,6 +76,7 @@ struct mpe_ctx {
   void* slab_buf = nullptr;
   size_t slab_bytes = 0;
   mpe_launch_info last = {};
+  long long search_counts[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // what the prime searches of this context sieved and tested so far (mpe_primes.h, mpe_prime_search_counts)
   // byte-level conventions of the un-vendored crates (include/mpecdsa_hip.h: mpe_encoding); kernels take it by value
   mpe_encoding enc = {};
   // optional per-launch timing of the heavy kernels (HIP events on the launch stream)

@@ -25,6 +25,7 @@
 //   mr_kernel rounds 2..8 on that list; who passes lowers best[item] with atomicMin
 //   finalize_kernel   items with a best attempt write their row; the others form the item list of the next pass
 // A pass covers attempts [a0, a0 + A) of every unfinished item, A a power of two chosen so that a pass has ~2^20 candidates.
+// The SAFE search (`sample_safe_prime`: c and (c - 1) / 2 both prime) is further down, with its joint sieve and its own pass rule.
 #pragma once
 #include <mutex>
 #include "mpe_keygen.h"
@@ -101,12 +102,14 @@ static int sieve_table(int device, SieveTab* out) {
   return MPE_OK;
 }
 
-// the smallest table prime that divides the odd integer w (32 words), or 0.  The product loop is wave-uniform (scalar table
-// operands); lanes with on == false only wait.
-__device__ __forceinline__ uint32_t small_factor(const uint32_t (&w)[32], bool on, const SieveTab& T) {
+// the smallest table prime of products [j0, j1) that divides the odd integer w (32 words), or 0.  JOINT: or that divides (w - 1) / 2,
+// which an odd prime l does exactly when w = 1 (mod l) — the same residue serves both numbers.  The product loop is wave-uniform
+// (scalar table operands); lanes with on == false only wait.
+template <bool JOINT>
+__device__ __forceinline__ uint32_t small_factor_range(const uint32_t (&w)[32], bool on, const SieveTab& T, int j0, int j1) {
   uint32_t found = on ? 0u : 1u;
 #pragma unroll 1
-  for (int j = 0; j < T.nprod; ++j) {
+  for (int j = j0; j < j1; ++j) {
     if (__ballot(found == 0u) == 0ull) break;
     const uint32_t* __restrict__ pw = T.pw + (size_t)j * 32;
     uint64_t acc = 0;                                         // < 32 * 2^32 * 2^26 = 2^63
@@ -122,11 +125,12 @@ __device__ __forceinline__ uint32_t small_factor(const uint32_t (&w)[32], bool o
     for (int k = (int)T.first[j]; k < k1; ++k) {
       const uint32_t p = T.prime[k];
       const uint32_t t = r - __umulhi(r, T.pinv[k]) * p;      // r mod p, or that + p
-      if (found == 0u && (t == 0u || t == p)) found = p;
+      if (found == 0u && (t == 0u || t == p || (JOINT && (t == 1u || t == p + 1u)))) found = p;
     }
   }
   return on ? found : 0u;
 }
+__device__ __forceinline__ uint32_t small_factor(const uint32_t (&w)[32], bool on, const SieveTab& T) { return small_factor_range<false>(w, on, T, 0, T.nprod); }
 
 // candidate of (item, attempt): words 16 h .. 16 h + 15 of the big-endian reading of blocks 2a, 2a + 1 come from block 2a + 1 - h
 __device__ __forceinline__ void candidate_half(const smp::Seed& key, uint32_t item, uint32_t sid_lo, uint32_t sid_hi, uint32_t attempt, int h, uint32_t (&o)[16]) {
@@ -179,6 +183,61 @@ __global__ void __launch_bounds__(64) sieve_kernel(int U, Source src, int max_at
   if (pos >= 0) list[pos] = (int32_t)c;
 }
 
+// ---------------------------------------------------------------------------------------------
+// joint sieve of the SAFE search, in two launches.  Head: thread c = (u << logA) | j as above; a candidate whose bit 1 is clear is out
+// before any product ((c - 1) / 2 would be even), the others meet the first SAFE_HEAD_PRODUCTS products (the primes up to 107) with
+// the joint test; ~1.8 % of a pass reach the list.  Tail: the remaining products on that list with every lane of a wave in use —
+// the list IS the compaction of live lanes (units of 64 entries from a queue; the candidate is rebuilt from its id: two ChaCha20
+// blocks against ~400 products); ~0.5 % of a pass reach the second list.
+// ---------------------------------------------------------------------------------------------
+constexpr int SAFE_HEAD_PRODUCTS = 6;
+
+__device__ __forceinline__ void candidate_words(const Source& src, unsigned c, uint32_t (&w)[32]) {
+  const unsigned u = c >> src.logA, j = c & ((1u << src.logA) - 1u);
+  const uint32_t item = (uint32_t)src.items[u], a = (uint32_t)src.a0 + j;
+  uint32_t lo[16], hi[16];
+  candidate_half(src.key, item, src.sid_lo, src.sid_hi, a, 0, lo);
+  candidate_half(src.key, item, src.sid_lo, src.sid_hi, a, 1, hi);
+#pragma unroll
+  for (int k = 0; k < 16; ++k) { w[k] = lo[k]; w[16 + k] = hi[k]; }
+}
+
+__global__ void __launch_bounds__(64) safe_sieve_head_kernel(int U, Source src, int max_attempts, SieveTab T, int32_t* __restrict__ list, int32_t* __restrict__ cnt) {
+  const unsigned c = blockIdx.x * 64u + threadIdx.x;
+  const unsigned u = c >> src.logA, j = c & ((1u << src.logA) - 1u);
+  const bool in = u < (unsigned)U && src.a0 + (int)j < max_attempts;
+  uint32_t w[32];
+  candidate_words(src, in ? c : 0u, w);
+  const bool on = in && (w[0] & 2u) != 0u;
+  const int head = T.nprod < SAFE_HEAD_PRODUCTS ? T.nprod : SAFE_HEAD_PRODUCTS;
+  const uint32_t f = small_factor_range<true>(w, on, T, 0, head);
+  const int pos = wave_append(on && f == 0u, cnt);
+  if (pos >= 0) list[pos] = (int32_t)c;
+}
+
+__global__ void __launch_bounds__(64) safe_sieve_tail_kernel(const int32_t* __restrict__ count, int cap, const int32_t* __restrict__ list, Source src, SieveTab T,
+                                                             int32_t* __restrict__ queue, int32_t* __restrict__ list2, int32_t* __restrict__ cnt2) {
+  int total = *count;
+  if (total > cap) total = cap;
+  const int lane = threadIdx.x & 63;
+  const int head = T.nprod < SAFE_HEAD_PRODUCTS ? T.nprod : SAFE_HEAD_PRODUCTS;
+#pragma unroll 1
+  for (;;) {
+    int unit = 0;
+    if (lane == 0) unit = atomicAdd(queue, 1);
+    unit = __builtin_amdgcn_readfirstlane(unit);
+    if ((long long)unit * 64 >= (long long)total) break;
+    const int pos = unit * 64 + lane;
+    const bool on = pos < total;
+    const int32_t id = list[on ? pos : total - 1];
+    uint32_t w[32];
+    candidate_words(src, (unsigned)id, w);
+    const uint32_t f = small_factor_range<true>(w, on, T, head, T.nprod);
+    const int p2 = wave_append(on && f == 0u, cnt2);
+    if (p2 >= 0 && p2 < cap) list2[p2] = id;
+  }
+}
+
 // table side of mpe_is_probable_prime: ok[i] = "prime by the table alone"; values the table cannot decide go to the list
 __global__ void __launch_bounds__(64) table_kernel(int B, const uint32_t* __restrict__ n, SieveTab T, uint8_t* __restrict__ ok, int32_t* __restrict__ list,
                                                    int32_t* __restrict__ cnt) {
@@ -208,10 +267,11 @@ __global__ void __launch_bounds__(64) table_kernel(int B, const uint32_t* __rest
 // The operation sequence depends on the candidate through the positions of those comparisons (s) and the early exit of a wave whose
 // groups are all decided — never on the bits of d: the multiplier of the scaling is selected, not branched on.
 // Results: ok[id] (rows), or an append to list2 (round 1 of the search), or atomicMin(best[item slot], attempt in block).
+// HALF (the safe search): the number under test is (c - 1) / 2 = c >> 1 of the stream's candidate c, 1023 bits.
 // ---------------------------------------------------------------------------------------------
 __device__ const uint32_t kBases[16] = {2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37, 41, 43, 47, 53};
 
-template <class C>
+template <class C, bool HALF = false>
 __global__ void __launch_bounds__(64) mr_kernel(const int32_t* __restrict__ count, int cap, const int32_t* __restrict__ list, Source src, int first_base, int rounds,
                                                 int32_t* __restrict__ queue, uint8_t* __restrict__ ok, int32_t* __restrict__ list2, int32_t* __restrict__ cnt2,
                                                 int32_t* __restrict__ best) {
@@ -241,6 +301,15 @@ __global__ void __launch_bounds__(64) mr_kernel(const int32_t* __restrict__ coun
       candidate_half(src.key, (uint32_t)src.items[u], src.sid_lo, src.sid_hi, (uint32_t)src.a0 + j, ln.t, o);
 #pragma unroll
       for (int k = 0; k < 16; ++k) nw[16 * ln.t + k] = o[k];
+      if (HALF) {                                             // shift right by one across the two lanes' halves
+        wave_lds_sync();
+        const uint32_t in = ln.t == 0 ? nw[16] : 0u;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) o[k] = (o[k] >> 1) | ((k < 15 ? o[k + 1] : in) << 31);
+        wave_lds_sync();
+#pragma unroll
+        for (int k = 0; k < 16; ++k) nw[16 * ln.t + k] = o[k];
+      }
     }
     wave_lds_sync();
     for (int q = ln.t; q <= (C::W * C::K - 1) / 32 + 1; q += C::TPI) gl[q] = q < 32 ? nw[q] : 0u;
@@ -383,14 +452,15 @@ __global__ void giveup_kernel(int U, const int32_t* __restrict__ items, uint32_t
   if (fail) atomicAdd(fail, 1);
 }
 
-static int block_log(int U) {
-  int want = PASS_CANDIDATES / (U > 0 ? U : 1), lg = MIN_BLOCK_LOG;
-  while (lg < MAX_BLOCK_LOG && (2 << lg) <= want) ++lg;
+static int block_log(int U, int max_log = MAX_BLOCK_LOG, int pass = PASS_CANDIDATES) {
+  int want = pass / (U > 0 ? U : 1), lg = MIN_BLOCK_LOG;
+  while (lg < max_log && (2 << lg) <= want) ++lg;
   return lg;
 }
-static size_t pass_candidates(int batch) {
+static long long attempts_in_block(int a0, int logA, int max_attempts) { return max_attempts - a0 < (1 << logA) ? max_attempts - a0 : (1 << logA); }
+static size_t pass_candidates(int batch, int pass = PASS_CANDIDATES) {
   const size_t a = (size_t)batch << MIN_BLOCK_LOG;
-  return a > (size_t)PASS_CANDIDATES ? a : (size_t)PASS_CANDIDATES;
+  return a > (size_t)pass ? a : (size_t)pass;
 }
 // bytes of context workspace one search of `batch` items takes (the caller reserves, the search only allocates)
 static size_t search_ws_bytes(int batch) { return (2 * pass_candidates(batch) + 3 * (size_t)batch + 64) * 4 + 8 * 256; }
@@ -426,16 +496,94 @@ static int search_primes(mpe_ctx* ctx, int batch, const smp::Seed& key, uint64_t
     hipLaunchKernelGGL(mr_kernel<Cfg1024>, dim3(mr_grid(ctx, C / 8)), dim3(64), 0, st, (const int32_t*)(cnt + 1), (int)C, (const int32_t*)list2, src, 1,
                        SEARCH_ROUNDS - 1, cnt + 4, (uint8_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, best);
     hipLaunchKernelGGL(finalize_kernel, dim3(blocks_for(U, 64)), dim3(64), 0, st, U, src, best, d_out, d_attempt, items[cur ^ 1], cnt + 2);
-    int h_next = 0;
-    hipError_t e = hipMemcpyAsync(&h_next, cnt + 2, sizeof(int), hipMemcpyDeviceToHost, st);
+    int32_t h_cnt[3] = {0, 0, 0};
+    hipError_t e = hipMemcpyAsync(h_cnt, cnt, sizeof h_cnt, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) { mpe_set_error("prime search", e); return MPE_E_HIP; }
+    const int h_next = h_cnt[2];
     if (h_next < 0 || h_next > U) { mpe_set_error_msg("prime search: corrupt item count"); return MPE_E_HIP; }
+    ctx->search_counts[0] += (long long)U * attempts_in_block(a0, logA, max_attempts);    // mpe_prime_search_counts: attempts, the two list lengths
+    ctx->search_counts[1] += h_cnt[0]; ctx->search_counts[2] += h_cnt[1];
     U = h_next; cur ^= 1; a0 += 1 << logA;
   }
   if (U > 0) hipLaunchKernelGGL(giveup_kernel, dim3(blocks_for(U, 256)), dim3(256), 0, st, U, (const int32_t*)items[cur], d_out, d_attempt, d_fail);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) { mpe_set_error("prime search", e); return MPE_E_HIP; }
+  return MPE_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The SAFE search: kzen-paillier's `sample_safe_prime` [RECALLED: kzen-paillier 0.4 `keygen.rs`, un-vendored]:
+//   loop { q = sample_prime(bits); if is_prime((q - 1) / 2) return q }
+// Every call of sample_prime goes on with fresh draws, so on the statement above the result of an item is the candidate c of the
+// LOWEST attempt a < max_attempts for which c AND (c - 1) / 2 pass the primality test (table primes, 8 rounds) — a pure function of
+// (seed, stream, item), whatever the batch, the pass size and the order of the tests.  The density of such attempts is
+// 2 C2 / (ln 2^1023 ln 2^1024) ~ 2.6e-6 (C2 ~ 0.66), ~380 000 attempts per result; the default (and largest) cap 2^24 gives up with
+// probability ~e^-44.
+// A pass: joint sieve (head, tail) -> round 1 on c -> round 1 on (c - 1) / 2 -> rounds 2..8 on c -> rounds 2..8 on (c - 1) / 2 ->
+// atomicMin into best; then finalize_kernel / giveup_kernel as above.  A pass fills ~2^safe_pass_log candidates (a context option,
+// default 24) WHATEVER the batch, up to 2^20 attempts per item: 1 024 attempts per item and pass would synchronise the host hundreds
+// of times for a small batch, and the six Miller-Rabin stages of a pass are a chain of 16 exponentiations one behind the other whose
+// lists (0.5 % of the pass and less) must be long enough to fill the device.
+// ---------------------------------------------------------------------------------------------
+constexpr int SAFE_DEFAULT_MAX_ATTEMPTS = 1 << 24;
+constexpr int SAFE_MAX_BLOCK_LOG = 20;
+
+// entries of a survivor list: a pass never holds more than batch << SAFE_MAX_BLOCK_LOG candidates, so a small batch does not pay for the
+// whole pass size (batch 1: 2^20 entries, 4 MB a list, instead of 2^24)
+static size_t safe_pass_capacity(int batch, int pass) {
+  const size_t most = (size_t)batch << SAFE_MAX_BLOCK_LOG;
+  return pass_candidates(batch, (int)(most < (size_t)pass ? most : (size_t)pass));
+}
+static size_t safe_search_ws_bytes(const mpe_ctx* ctx, int batch) { return (3 * safe_pass_capacity(batch, 1 << ctx->safe_pass_log) + 3 * (size_t)batch + 64) * 4 + 12 * 256; }
+
+static int search_safe_primes(mpe_ctx* ctx, int batch, const smp::Seed& key, uint64_t sid, int max_attempts, uint32_t* d_out, int32_t* d_attempt, int32_t* d_fail,
+                              hipStream_t st) {
+  if (batch == 0) return MPE_OK;
+  SieveTab T;
+  MPE_TRY(sieve_table(ctx->device, &T));
+  const int pass = 1 << ctx->safe_pass_log;
+  const size_t capC = safe_pass_capacity(batch, pass);
+  int32_t* items[2] = {ws_array<int32_t>(ctx, batch), ws_array<int32_t>(ctx, batch)};
+  int32_t* best = ws_array<int32_t>(ctx, batch);
+  int32_t* list[3] = {ws_array<int32_t>(ctx, capC), ws_array<int32_t>(ctx, capC), ws_array<int32_t>(ctx, capC)};
+  // [0] head survivors, [1] sieve survivors, [2] round 1 on c, [3] round 1 on the half, [4] rounds 2..8 on c, [5] next items, [8..12] unit queues
+  int32_t* cnt = ws_array<int32_t>(ctx, 16);
+  if (!items[0] || !items[1] || !best || !list[0] || !list[1] || !list[2] || !cnt) { mpe_set_error_msg("safe prime search: workspace under-reserved"); return MPE_E_NOMEM; }
+  hipLaunchKernelGGL(iota_kernel, dim3(blocks_for(batch, 256)), dim3(256), 0, st, batch, items[0], best);
+  int32_t* const none = nullptr;
+  int U = batch, a0 = 0, cur = 0;
+  while (U > 0 && a0 < max_attempts) {
+    const int logA = block_log(U, SAFE_MAX_BLOCK_LOG, pass);
+    const size_t C = (size_t)U << logA;                       // <= capC
+    const int cap = (int)C;
+    Source src{nullptr, key, (uint32_t)sid, (uint32_t)(sid >> 32), items[cur], a0, logA};
+    (void)hipMemsetAsync(cnt, 0, 16 * sizeof(int32_t), st);
+    hipLaunchKernelGGL(safe_sieve_head_kernel, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, st, U, src, max_attempts, T, list[0], cnt);
+    hipLaunchKernelGGL(safe_sieve_tail_kernel, dim3(mr_grid(ctx, C / 32)), dim3(64), 0, st, (const int32_t*)cnt, cap, (const int32_t*)list[0], src, T, cnt + 8,
+                       list[1], cnt + 1);
+    hipLaunchKernelGGL((mr_kernel<Cfg1024, false>), dim3(mr_grid(ctx, C / 16)), dim3(64), 0, st, (const int32_t*)(cnt + 1), cap, (const int32_t*)list[1], src, 0, 1,
+                       cnt + 9, (uint8_t*)nullptr, list[2], cnt + 2, none);
+    hipLaunchKernelGGL((mr_kernel<Cfg1024, true>), dim3(mr_grid(ctx, C / 64)), dim3(64), 0, st, (const int32_t*)(cnt + 2), cap, (const int32_t*)list[2], src, 0, 1,
+                       cnt + 10, (uint8_t*)nullptr, list[0], cnt + 3, none);
+    hipLaunchKernelGGL((mr_kernel<Cfg1024, false>), dim3(mr_grid(ctx, C / 64)), dim3(64), 0, st, (const int32_t*)(cnt + 3), cap, (const int32_t*)list[0], src, 1,
+                       SEARCH_ROUNDS - 1, cnt + 11, (uint8_t*)nullptr, list[1], cnt + 4, none);
+    hipLaunchKernelGGL((mr_kernel<Cfg1024, true>), dim3(mr_grid(ctx, C / 64)), dim3(64), 0, st, (const int32_t*)(cnt + 4), cap, (const int32_t*)list[1], src, 1,
+                       SEARCH_ROUNDS - 1, cnt + 12, (uint8_t*)nullptr, none, none, best);
+    hipLaunchKernelGGL(finalize_kernel, dim3(blocks_for(U, 64)), dim3(64), 0, st, U, src, best, d_out, d_attempt, items[cur ^ 1], cnt + 5);
+    int32_t h_cnt[6] = {0, 0, 0, 0, 0, 0};
+    hipError_t e = hipMemcpyAsync(h_cnt, cnt, sizeof h_cnt, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { mpe_set_error("safe prime search", e); return MPE_E_HIP; }
+    const int h_next = h_cnt[5];
+    if (h_next < 0 || h_next > U) { mpe_set_error_msg("safe prime search: corrupt item count"); return MPE_E_HIP; }
+    ctx->search_counts[3] += (long long)U * attempts_in_block(a0, logA, max_attempts);    // mpe_prime_search_counts: attempts, the five list lengths
+    for (int i = 0; i < 5; ++i) ctx->search_counts[4 + i] += h_cnt[i];
+    U = h_next; cur ^= 1; a0 += 1 << logA;
+  }
+  if (U > 0) hipLaunchKernelGGL(giveup_kernel, dim3(blocks_for(U, 256)), dim3(256), 0, st, U, (const int32_t*)items[cur], d_out, d_attempt, d_fail);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { mpe_set_error("safe prime search", e); return MPE_E_HIP; }
   return MPE_OK;
 }
 
@@ -565,39 +713,71 @@ int mpe_sample_prime(mpe_ctx* ctx, int batch, const uint8_t* h_seed32, uint64_t 
                            (hipStream_t)stream);
 }
 
-int mpe_paillier_keygen(mpe_ctx* ctx, int nkeys, const uint8_t* h_seed32, uint64_t counter, int max_attempts, uint32_t* d_p, uint32_t* d_q, uint32_t* d_N,
-                        int32_t* d_fail, void* stream) {
-  if (!ctx || !h_seed32 || !d_p || !d_q || !d_N || nkeys < 0 || nkeys > (1 << 22) || (counter >> 56) != 0 || max_attempts < 0 || max_attempts > (1 << 24))
-    return MPE_E_ARG;
-  if (nkeys == 0) return MPE_OK;
+int mpe_sample_safe_prime(mpe_ctx* ctx, int batch, const uint8_t* h_seed32, uint64_t stream_id, int bits, int max_attempts, uint32_t* d_out, int32_t* d_attempt,
+                          int32_t* d_fail, void* stream) {
+  if (!ctx || !h_seed32 || !d_out || batch < 0 || batch > (1 << 22) || bits != 1024 || max_attempts < 0 || max_attempts > (1 << 24)) return MPE_E_ARG;
+  if (batch == 0) return MPE_OK;
   using namespace mpe;
-  hipStream_t st = (hipStream_t)stream;
-  const smp::Seed key = smp::seed_of(h_seed32);
-  const int cap = max_attempts ? max_attempts : pr::DEFAULT_MAX_ATTEMPTS;
-  uint32_t* prime[2] = {d_p, d_q};
-  for (int f = 0; f < 2; ++f) {                                // field f draws stream counter | f << 56 (the convention of mpe_gg20_sample_nonces)
-    MPE_TRY(ws_reserve(ctx, pr::search_ws_bytes(nkeys), st));
-    MPE_TRY(pr::search_primes(ctx, nkeys, key, counter | ((uint64_t)f << 56), cap, prime[f], nullptr, nullptr, st));
-  }
-  MPE_LAUNCH_1D(pr::keypair_kernel, nkeys, st, nkeys, d_p, d_q, d_N, d_fail);
+  MPE_TRY(ws_reserve(ctx, pr::safe_search_ws_bytes(ctx, batch), (hipStream_t)stream));
+  return pr::search_safe_primes(ctx, batch, smp::seed_of(h_seed32), stream_id, max_attempts ? max_attempts : pr::SAFE_DEFAULT_MAX_ATTEMPTS, d_out, d_attempt, d_fail,
+                                (hipStream_t)stream);
+}
+
+int mpe_prime_search_counts(mpe_ctx* ctx, int64_t* h_out9, int reset) {
+  if (!ctx || !h_out9) return MPE_E_ARG;
+  for (int i = 0; i < 9; ++i) { h_out9[i] = ctx->search_counts[i]; if (reset) ctx->search_counts[i] = 0; }
   return MPE_OK;
 }
 
-int mpe_ntilde_generate(mpe_ctx* ctx, int count, const uint8_t* h_seed32, uint64_t counter, int max_attempts, uint32_t* d_Nt, uint32_t* d_h1, uint32_t* d_h2,
-                        uint32_t* d_xhi, uint32_t* d_xhi_inv, int32_t* d_fail, void* stream) {
+namespace mpe {
+namespace pr {
+// one search of the key-material calls: plain (`sample_prime`) or safe (`sample_safe_prime`), the cap's default with it
+static int search_any(mpe_ctx* ctx, bool safe, int n, const smp::Seed& key, uint64_t sid, int max_attempts, uint32_t* d_out, hipStream_t st) {
+  if (safe) return search_safe_primes(ctx, n, key, sid, max_attempts ? max_attempts : SAFE_DEFAULT_MAX_ATTEMPTS, d_out, nullptr, nullptr, st);
+  return search_primes(ctx, n, key, sid, max_attempts ? max_attempts : DEFAULT_MAX_ATTEMPTS, d_out, nullptr, nullptr, st);
+}
+static size_t search_any_ws_bytes(const mpe_ctx* ctx, bool safe, int n) { return safe ? safe_search_ws_bytes(ctx, n) : search_ws_bytes(n); }
+
+static int paillier_keygen(mpe_ctx* ctx, bool safe, int nkeys, const uint8_t* h_seed32, uint64_t counter, int max_attempts, uint32_t* d_p, uint32_t* d_q, uint32_t* d_N,
+                           int32_t* d_fail, hipStream_t st) {
+  if (!ctx || !h_seed32 || !d_p || !d_q || !d_N || nkeys < 0 || nkeys > (1 << 22) || (counter >> 56) != 0 || max_attempts < 0 || max_attempts > (1 << 24))
+    return MPE_E_ARG;
+  if (nkeys == 0) return MPE_OK;
+  const smp::Seed key = smp::seed_of(h_seed32);
+  uint32_t* prime[2] = {d_p, d_q};
+  for (int f = 0; f < 2; ++f) {                                // field f draws stream counter | f << 56 (the convention of mpe_gg20_sample_nonces)
+    MPE_TRY(ws_reserve(ctx, search_any_ws_bytes(ctx, safe, nkeys), st));
+    MPE_TRY(search_any(ctx, safe, nkeys, key, counter | ((uint64_t)f << 56), max_attempts, prime[f], st));
+  }
+  MPE_LAUNCH_1D(keypair_kernel, nkeys, st, nkeys, d_p, d_q, d_N, d_fail);
+  return MPE_OK;
+}
+}  // namespace pr
+}  // namespace mpe
+
+int mpe_paillier_keygen(mpe_ctx* ctx, int nkeys, const uint8_t* h_seed32, uint64_t counter, int max_attempts, uint32_t* d_p, uint32_t* d_q, uint32_t* d_N,
+                        int32_t* d_fail, void* stream) {
+  return mpe::pr::paillier_keygen(ctx, false, nkeys, h_seed32, counter, max_attempts, d_p, d_q, d_N, d_fail, (hipStream_t)stream);
+}
+int mpe_paillier_keygen_safe_primes(mpe_ctx* ctx, int nkeys, const uint8_t* h_seed32, uint64_t counter, int max_attempts, uint32_t* d_p, uint32_t* d_q, uint32_t* d_N,
+                                    int32_t* d_fail, void* stream) {
+  return mpe::pr::paillier_keygen(ctx, true, nkeys, h_seed32, counter, max_attempts, d_p, d_q, d_N, d_fail, (hipStream_t)stream);
+}
+
+namespace mpe {
+namespace pr {
+static int ntilde_generate(mpe_ctx* ctx, bool safe, int count, const uint8_t* h_seed32, uint64_t counter, int max_attempts, uint32_t* d_Nt, uint32_t* d_h1, uint32_t* d_h2,
+                           uint32_t* d_xhi, uint32_t* d_xhi_inv, int32_t* d_fail, hipStream_t st) {
   if (!ctx || !h_seed32 || !d_Nt || !d_h1 || !d_h2 || !d_xhi || !d_xhi_inv || count < 0 || count > (1 << 22) || (counter >> 56) != 0 || max_attempts < 0 ||
       max_attempts > (1 << 24))
     return MPE_E_ARG;
   if (count == 0) return MPE_OK;
-  using namespace mpe;
-  hipStream_t st = (hipStream_t)stream;
   const smp::Seed key = smp::seed_of(h_seed32);
-  const int cap = max_attempts ? max_attempts : pr::DEFAULT_MAX_ATTEMPTS;
   auto sid = [&](int f) { return counter | ((uint64_t)f << 56); };
   // the secrets of the call (p~, q~, phi, xi, phi^-1 mod xi) live in the context workspace: mpe_ctx_wipe covers them.  The two prime
   // searches allocate below these arrays, one after the other (the first one's lists are dead when the second starts).
   const size_t own = (size_t)count * (32 + 32 + 64 * 4 + 1) * 4 + (size_t)count + 16 * 256;
-  MPE_TRY(ws_reserve(ctx, own + 2 * pr::search_ws_bytes(count), st));
+  MPE_TRY(ws_reserve(ctx, own + 2 * search_any_ws_bytes(ctx, safe, count), st));
   uint32_t* pt = ws_array<uint32_t>(ctx, (size_t)count * 32);
   uint32_t* qt = ws_array<uint32_t>(ctx, (size_t)count * 32);
   uint32_t* nt_ms = ws_array<uint32_t>(ctx, (size_t)count * 64);
@@ -607,12 +787,12 @@ int mpe_ntilde_generate(mpe_ctx* ctx, int count, const uint8_t* h_seed32, uint64
   int32_t* bad = ws_array<int32_t>(ctx, count);
   uint8_t* inv_ok = ws_array<uint8_t>(ctx, count);
   if (!pt || !qt || !nt_ms || !phi || !xi || !phi_inv || !bad || !inv_ok) return MPE_E_NOMEM;
-  MPE_TRY(pr::search_primes(ctx, count, key, sid(2), cap, pt, nullptr, nullptr, st));
-  MPE_TRY(pr::search_primes(ctx, count, key, sid(3), cap, qt, nullptr, nullptr, st));
-  MPE_LAUNCH_1D(pr::nt_setup_kernel, count, st, count, pt, qt, nt_ms, phi, bad);
+  MPE_TRY(search_any(ctx, safe, count, key, sid(2), max_attempts, pt, st));
+  MPE_TRY(search_any(ctx, safe, count, key, sid(3), max_attempts, qt, st));
+  MPE_LAUNCH_1D(nt_setup_kernel, count, st, count, pt, qt, nt_ms, phi, bad);
   (void)hipMemsetAsync(xi, 0, (size_t)count * 64 * 4, st);
   MPE_TRY(smp::launch_sample(count, h_seed32, sid(4), 0, nt_ms, 64, nullptr, count, 0, 64, d_h1, nullptr, st, nullptr, ctx->sampler_max_attempts, bad));
-  hipLaunchKernelGGL(pr::xi_kernel, dim3(blocks_for(count, 64)), dim3(64), 0, st, count, key, (uint32_t)sid(5), (uint32_t)(sid(5) >> 32), (const uint32_t*)phi, xi,
+  hipLaunchKernelGGL(xi_kernel, dim3(blocks_for(count, 64)), dim3(64), 0, st, count, key, (uint32_t)sid(5), (uint32_t)(sid(5) >> 32), (const uint32_t*)phi, xi,
                      ctx->sampler_max_attempts, bad);
   hipLaunchKernelGGL(modinv_lane_kernel<64>, dim3(blocks_for(count, 64)), dim3(64), 0, st, count, (const uint32_t*)xi, Rows{nullptr, nullptr, 1, 0, 0},
                      rows(phi, 64), (const uint8_t*)nullptr, phi_inv, inv_ok);
@@ -620,7 +800,7 @@ int mpe_ntilde_generate(mpe_ctx* ctx, int count, const uint8_t* h_seed32, uint64
   MPE_TRY(modset_create_dev(ctx, 2048, count, nt_ms, &ms, st));
   int rc = launch_modexp(ctx, ms, count, Rows{nullptr, nullptr, 1, 0, 0}, rows(d_h1, 64), no_rows(), rows(xi, 64), 64, d_h2, st);     // h2 = h1^xi mod N~
   if (rc == MPE_OK) {
-    hipLaunchKernelGGL(pr::nt_final_kernel, dim3(blocks_for(count, 64)), dim3(64), 0, st, count, (const uint32_t*)nt_ms, (const uint32_t*)phi, (const uint32_t*)xi,
+    hipLaunchKernelGGL(nt_final_kernel, dim3(blocks_for(count, 64)), dim3(64), 0, st, count, (const uint32_t*)nt_ms, (const uint32_t*)phi, (const uint32_t*)xi,
                        (const uint32_t*)phi_inv, (const uint8_t*)inv_ok, (const int32_t*)bad, d_Nt, d_h1, d_h2, d_xhi, d_xhi_inv, d_fail);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(st);        // the moduli set is released below
@@ -630,6 +810,17 @@ int mpe_ntilde_generate(mpe_ctx* ctx, int count, const uint8_t* h_seed32, uint64
   }
   mpe_modset_destroy(ms);
   return rc;
+}
+}  // namespace pr
+}  // namespace mpe
+
+int mpe_ntilde_generate(mpe_ctx* ctx, int count, const uint8_t* h_seed32, uint64_t counter, int max_attempts, uint32_t* d_Nt, uint32_t* d_h1, uint32_t* d_h2,
+                        uint32_t* d_xhi, uint32_t* d_xhi_inv, int32_t* d_fail, void* stream) {
+  return mpe::pr::ntilde_generate(ctx, false, count, h_seed32, counter, max_attempts, d_Nt, d_h1, d_h2, d_xhi, d_xhi_inv, d_fail, (hipStream_t)stream);
+}
+int mpe_ntilde_generate_safe_primes(mpe_ctx* ctx, int count, const uint8_t* h_seed32, uint64_t counter, int max_attempts, uint32_t* d_Nt, uint32_t* d_h1,
+                                    uint32_t* d_h2, uint32_t* d_xhi, uint32_t* d_xhi_inv, int32_t* d_fail, void* stream) {
+  return mpe::pr::ntilde_generate(ctx, true, count, h_seed32, counter, max_attempts, d_Nt, d_h1, d_h2, d_xhi, d_xhi_inv, d_fail, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -26,7 +26,7 @@ def _to_np_u32(t):
 # when it creates a context: MPE_NO_PAR=1 -> ("no_par", "1"), MPE_WIDE_DIV=4 -> ("wide_div", "4"), MPE_GRID=full -> ("grid", "full").
 _ENV_OPTIONS = ["no_fixed_base", "no_crt", "no_multiexp", "no_pair", "no_pown", "no_sliding", "no_par", "no_wide", "no_adaptive_lanes",
                 "no_merge_xn", "no_merge_r1", "fb_window_bits", "window_bits", "wide_div", "xwide_div", "waves_per_cu", "grid", "fb_budget_mb",
-                "fb_split", "gg20_trace", "sampler_max_attempts", "no_elect", "no_primaries", "merge_r1_quarters",
+                "fb_split", "gg20_trace", "sampler_max_attempts", "safe_pass_log", "no_elect", "no_primaries", "merge_r1_quarters",
                 "no_r1_inversion_ahead", "no_r1_dlog_first", "no_prio", "no_pdl_ahead", "no_crt_n"]
 
 
@@ -1030,22 +1030,44 @@ def sample_prime(ctx, batch, seed, stream_id, bits=1024, max_attempts=0):
     return out, attempt, fail
 
 
-def paillier_keygen(ctx, nkeys, seed, counter, max_attempts=0):
-    """`Paillier::keypair()` x nkeys: device (p [nkeys, 32], q [nkeys, 32], N [nkeys, 64], failures [1]); PaillierKeys(ctx, p=p, q=q) takes p, q"""
+def sample_safe_prime(ctx, batch, seed, stream_id, bits=1024, max_attempts=0):
+    """kzen-paillier sample_safe_prime per item — the lowest attempt of sample_prime's sequence whose candidate c and (c - 1) / 2 are both
+    prime: (primes [batch, 32], attempt [batch] (-1: gave up), failures [1]); max_attempts 0 = 2^24"""
+    out = _new(ctx, batch, bits // 32)
+    attempt = torch.zeros((batch,), dtype=torch.int32, device=ctx.device)
+    fail = torch.zeros((1,), dtype=torch.int32, device=ctx.device)
+    N_.check(N_.lib.mpe_sample_safe_prime(ctx.h, batch, _seed(seed), stream_id, bits, max_attempts, _ptr(out), _ptr(attempt), _ptr(fail), ctx.stream()),
+             "mpe_sample_safe_prime")
+    return out, attempt, fail
+
+
+def prime_search_counts(ctx, reset=False):
+    """what this context's prime searches counted so far, a measurement aid: attempts sieved and the length of the list behind each stage,
+    for the plain search (3 figures) and the safe one (6)"""
+    v = (C.c_int64 * 9)()
+    N_.check(N_.lib.mpe_prime_search_counts(ctx.h, v, int(reset)), "mpe_prime_search_counts")
+    names = ("attempts", "sieve", "round1", "safe_attempts", "safe_sieve_head", "safe_sieve", "safe_round1_c", "safe_round1_half", "safe_rounds2_8_c")
+    return dict(zip(names, (int(x) for x in v)))
+
+
+def paillier_keygen(ctx, nkeys, seed, counter, max_attempts=0, safe_primes=False):
+    """`Paillier::keypair()` x nkeys — `Paillier::keypair_safe_primes()` with safe_primes=True (one (seed, counter) mints one key: the plain or
+    the safe one): device (p [nkeys, 32], q [nkeys, 32], N [nkeys, 64], failures [1]); PaillierKeys(ctx, p=p, q=q) takes p, q"""
     p, q, n = _new(ctx, nkeys, 32), _new(ctx, nkeys, 32), _new(ctx, nkeys, 64)
     fail = torch.zeros((1,), dtype=torch.int32, device=ctx.device)
-    N_.check(N_.lib.mpe_paillier_keygen(ctx.h, nkeys, _seed(seed), int(counter), max_attempts, _ptr(p), _ptr(q), _ptr(n), _ptr(fail), ctx.stream()),
-             "mpe_paillier_keygen")
+    name = "mpe_paillier_keygen_safe_primes" if safe_primes else "mpe_paillier_keygen"
+    N_.check(getattr(N_.lib, name)(ctx.h, nkeys, _seed(seed), int(counter), max_attempts, _ptr(p), _ptr(q), _ptr(n), _ptr(fail), ctx.stream()), name)
     return p, q, n, fail
 
 
-def ntilde_generate(ctx, count, seed, counter, max_attempts=0):
-    """`generate_h1_h2_N_tilde()` x count: dict of device [count, 64] tensors Nt, h1, h2 (Statements(ctx, Nt, h1, h2) takes them), xhi, xhi_inv
-    and the failures [1]"""
+def ntilde_generate(ctx, count, seed, counter, max_attempts=0, safe_primes=False):
+    """`generate_h1_h2_N_tilde()` x count (safe_primes=True: p~, q~ are safe primes, as the reference's comment asks): dict of device [count, 64]
+    tensors Nt, h1, h2 (Statements(ctx, Nt, h1, h2) takes them), xhi, xhi_inv and the failures [1]"""
     o = {f: _new(ctx, count, 64) for f in ("Nt", "h1", "h2", "xhi", "xhi_inv")}
     fail = torch.zeros((1,), dtype=torch.int32, device=ctx.device)
-    N_.check(N_.lib.mpe_ntilde_generate(ctx.h, count, _seed(seed), int(counter), max_attempts, _ptr(o["Nt"]), _ptr(o["h1"]), _ptr(o["h2"]), _ptr(o["xhi"]),
-                                        _ptr(o["xhi_inv"]), _ptr(fail), ctx.stream()), "mpe_ntilde_generate")
+    name = "mpe_ntilde_generate_safe_primes" if safe_primes else "mpe_ntilde_generate"
+    N_.check(getattr(N_.lib, name)(ctx.h, count, _seed(seed), int(counter), max_attempts, _ptr(o["Nt"]), _ptr(o["h1"]), _ptr(o["h2"]), _ptr(o["xhi"]),
+                                   _ptr(o["xhi_inv"]), _ptr(fail), ctx.stream()), name)
     o["fail"] = fail
     return o
 
@@ -1150,12 +1172,15 @@ def keygen_verify_round3(ctx, n_parties, d_commits, d_pk, d_R, d_z, want_xi=Fals
 KEYGEN_MATERIAL_FIELDS = ("p", "q", "pt", "qt", "h1", "xi")        # rows [B*n, 32] x 4, [B*n, 64] x 2
 
 
-def gg20_keygen(ctx, t, n, B, seed, counter=0, material=None, _fault=None):
+def gg20_keygen(ctx, t, n, B, seed, counter=0, material=None, _fault=None, safe_primes=False, safe_ntilde=False):
     """`Keygen` (gg_2020/state_machine/keygen/rounds.rs) for B wallets in lock step with all n parties local, the counterpart of gg20_sign:
     a chain of C-ABI calls, rows = (wallet, party).
       material: None = mint the Paillier / N~ material on the device (streams counter | 0..5 << 56 of `seed`); or a dict of uint32
                 arrays KEYGEN_MATERIAL_FIELDS (p, q, p~, q~ [B n, 32]; h1, xi [B n, 64]) taken as generate_h1_h2_N_tilde would have
                 drawn them (N, N~, h2 = h1^xi and the two proof secrets are derived on the host).
+      safe_primes: mint every party's Paillier key from safe primes — `Keys::create_safe_prime` (party_i.rs:179-199), the key generation
+                the reference recommends for production; safe_ntilde additionally mints N~ from safe primes (its "note, should be safe
+                primes").  Both only apply to material minted here; a safe prime costs ~1000 plain ones.
       u_i, blind factors, VSS coefficients, the DLog nonces and the two CompositeDLog nonces: streams counter | 8..13 << 56.
       _fault:   a test aid, not part of the interface: (wallet, dealer, party) flips bit 0 of the share that dealer sends to that party
                 before round 2, as Gg20Session.fault_inject does for signing (tests/test_keygen_deal_gpu.py walks the blame path with it).
@@ -1167,9 +1192,11 @@ def gg20_keygen(ctx, t, n, B, seed, counter=0, material=None, _fault=None):
         raise ValueError("counter < 2^56")
     sid = lambda f: int(counter) | (f << 56)
     fails = []
+    if material is not None and (safe_primes or safe_ntilde):
+        raise ValueError("safe_primes / safe_ntilde apply to material minted on the device")
     if material is None:
-        p, q, N, f = paillier_keygen(ctx, P, seed, counter)
-        nt = ntilde_generate(ctx, P, seed, counter)
+        p, q, N, f = paillier_keygen(ctx, P, seed, counter, safe_primes=safe_primes)
+        nt = ntilde_generate(ctx, P, seed, counter, safe_primes=safe_ntilde)
         Nt, h1, h2, xhi, xhi_inv = nt["Nt"], nt["h1"], nt["h2"], nt["xhi"], nt["xhi_inv"]
         fails += [f, nt["fail"]]
     else:
