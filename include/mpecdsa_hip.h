@@ -346,6 +346,15 @@ int mpe_gg20_keys_create(mpe_ctx* ctx, int t, int n, int n_signers, const int32_
                          const int32_t* h_own, const uint32_t* d_x, const uint32_t* d_p, const uint32_t* d_q,
                          const uint32_t* d_N, const uint32_t* d_Nt, const uint32_t* d_h1, const uint32_t* d_h2,
                          const uint32_t* d_y, const uint32_t* d_X, mpe_gg20_keys** out, void* stream);
+/* The same with SEVERAL signer sets, so that one key object (one set of fixed-base tables, Paillier objects and sampling bounds) signs
+ * for any quorum of the wallet: h_sets [n_sets][n_signers] (HOST), every row ascending distinct party indices < n, 1 <= n_sets <= 256,
+ * two equal rows are MPE_E_ARG.  Every session of a batch then names its set through d_sigset (the *_sets calls below); set 0 is what
+ * h_signers is above: mpe_gg20_keys_create is the n_sets == 1 case, and every entry point that takes no per-session set means set 0.
+ * n_signers is one value per key object. */
+int mpe_gg20_keys_create_sets(mpe_ctx* ctx, int t, int n, int n_signers, int n_sets, const int32_t* h_sets, int nkeysets, int n_own,
+                              const int32_t* h_own, const uint32_t* d_x, const uint32_t* d_p, const uint32_t* d_q,
+                              const uint32_t* d_N, const uint32_t* d_Nt, const uint32_t* d_h1, const uint32_t* d_h2,
+                              const uint32_t* d_y, const uint32_t* d_X, mpe_gg20_keys** out, void* stream);
 int mpe_gg20_keys_destroy(mpe_gg20_keys* keys);
 int mpe_gg20_keys_fb_window_bits(const mpe_gg20_keys* keys);
 
@@ -410,6 +419,12 @@ int mpe_gg20_nonces_free(mpe_gg20_nonce_buf* buf);
 int mpe_gg20_sample_nonces(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, int n_local, const int32_t* h_local,
                            const int32_t* d_keyset, const uint8_t* h_seed32, uint64_t batch_counter, const mpe_gg20_nonces* out,
                            int32_t* d_fail, void* stream);
+/* ... for sessions that name their signer set (d_sigset [batch], device; local_by_party as for mpe_gg20_session_create_sets).  Stream
+ * ids and item indices are those of mpe_gg20_sample_nonces; only the bound row an item reads follows the session's set: row b equals
+ * row b of the uniform call on a key object whose signer set is that session's, under the same (seed, batch_counter). */
+int mpe_gg20_sample_nonces_sets(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, int n_local, const int32_t* h_local,
+                                const int32_t* d_keyset, const int32_t* d_sigset, int local_by_party, const uint8_t* h_seed32,
+                                uint64_t batch_counter, const mpe_gg20_nonces* out, int32_t* d_fail, void* stream);
 
 /* GG20 round messages.  One fixed-size record of 32-bit words per (sender, session); a slab holds, for every sender,
  * a [B][W] block of records.  P2P messages travel like broadcast ones and are filtered by the receiver, exactly as the
@@ -448,16 +463,33 @@ int mpe_gg20_msg_words(int n_signers, int n, int round);
  *      marks the party of a session one of whose rejection loops gave up this way (mpe_gg20_sample_nonces: after
  *      sampler_max_attempts candidates, default 128 — probability < 2^-128 per draw; curv's loops are unbounded, a deliberate
  *      divergence) so that a session NEVER signs on zeroed values; a caller's own out-of-range k_i / gamma_i is refused alike
+ *   92 (MPE_GG20_STATUS_BAD_SET, round 0) the session names no quorum this party signs in: d_sigset[b] is outside [0, n_sets), or the
+ *      local party given by index is not a member of the session's set.  Checked on the device (the host never reads d_sigset); the
+ *      party emits zero records and never signs
  * with `bad_actors` (a bit mask over signer ordinals, the reference's `ErrorType::bad_actors`, gg_2020/mod.rs:23-27) set
  * for 401 (the peers whose decommitment is bad), 501 (the first failing prover) and 601 (every failing prover).
  * mpe_gg20_session_result: d_status, d_bad_actors, d_recid [n_local][batch]; d_r, d_s [n_local][batch][8] (after
  * mpe_gg20_complete; zero unless status == 0); d_R [n_local][batch][16] (after round 4).  Any pointer may be NULL.
  * Destroying a session zeroes its state (k_i, gamma_i, w_i, sigma_i, ...). */
 #define MPE_GG20_STATUS_BAD_NONCE 91
+#define MPE_GG20_STATUS_BAD_SET 92
 typedef struct mpe_gg20_session mpe_gg20_session;
 int mpe_gg20_session_create(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, int n_local, const int32_t* h_local,
                             const int32_t* d_keyset, const mpe_gg20_nonces* nonces, int dedup_verify, mpe_gg20_session** out,
                             void* stream);
+/* Sessions that name their signer set: d_sigset [batch] (device int32) = the set of `keys` (mpe_gg20_keys_create_sets) session b signs
+ * with; NULL = set 0 for all, which computes exactly what mpe_gg20_session_create computes.  Signer ORDINALS — senders of a slab, peer
+ * slots, bad_actors bits, fault-injection masks — are positions in the session's OWN set.  The local parties come in two forms:
+ *   local_by_party = 0  h_local[] are ordinals, as above: local slot l is the party at position h_local[l] of each session's set, so
+ *                       `keys` must hold the secrets of every party that can stand there in ANY of its sets (checked here, MPE_E_ARG);
+ *   local_by_party = 1  n_local = 1 and h_local[0] is a PARTY INDEX whose secrets `keys` holds (one party per process, the reference's
+ *                       deployment): its ordinal in session b is its rank in set d_sigset[b].  The incoming slabs stay
+ *                       [sender ordinal][batch][W], ordinals taken in each session's own set; routing records is the relay's job.
+ * A session whose d_sigset[b] is out of range, or whose by-index party is not in its set, gets MPE_GG20_STATUS_BAD_SET.
+ * d_sigset, like d_keyset, must stay valid until the batch is completed, deposited or given up (the rounds read it). */
+int mpe_gg20_session_create_sets(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, int n_local, const int32_t* h_local,
+                                 const int32_t* d_keyset, const int32_t* d_sigset, int local_by_party, const mpe_gg20_nonces* nonces,
+                                 int dedup_verify, mpe_gg20_session** out, void* stream);
 int mpe_gg20_session_destroy(mpe_gg20_session* sess, void* stream);
 /* The next batch of the same shape on the same object (a party process signs batch after batch: `SignManual::new` again
  * with fresh `SignKeys`, sign.rs:540-569): new sampled values (and key-set choice), state of the previous batch zeroed, rounds
@@ -467,6 +499,10 @@ int mpe_gg20_session_destroy(mpe_gg20_session* sess, void* stream);
  * half-way through the protocol and healthy (finish it with mpe_gg20_complete, or give it up with mpe_gg20_session_abort);
  * MPE_E_HIP when the wipe fails. */
 int mpe_gg20_session_rearm(mpe_gg20_session* sess, const int32_t* d_keyset, const mpe_gg20_nonces* nonces, void* stream);
+/* ... with the next batch's signer sets, for a session made by mpe_gg20_session_create_sets with a d_sigset (MPE_E_ARG otherwise: the
+ * local parties' secrets were then checked against set 0 alone).  NULL = set 0 for all; mpe_gg20_session_rearm is that case. */
+int mpe_gg20_session_rearm_sets(mpe_gg20_session* sess, const int32_t* d_keyset, const int32_t* d_sigset, const mpe_gg20_nonces* nonces,
+                                void* stream);
 /* Gives the running batch up (a peer vanished, a round call returned an error): the
  * nonce-derived state is wiped at once, every round entry point refuses, and mpe_gg20_session_rearm starts the next batch.  (A caller
  * that stops after the offline stage to sign later does not abort: mpe_gg20_presig_deposit moves the presignatures into a pool.)  A
@@ -522,8 +558,8 @@ int mpe_gg20_session_fault_inject(mpe_gg20_session* sess, int step, uint32_t par
  *     d_r, d_s [n_local][count][8], d_recid, d_status [n_local][count]: low-s normalised with the recid flip, zero unless status 0.
  *     The slot returns to EMPTY whatever the verdict.
  * mpe_gg20_presig_export    moves READY slots out (READY -> EMPTY, secrets zeroed in the pool): the record is then the only copy.
- * mpe_gg20_presig_import    EMPTY -> READY.  Refused (832): a version, signer-set mask, number of local parties or ordinals that are
- *     not the pool's; a key-set index out of range or a y that is not that key set's; an R that is no valid curve point; a k_i outside
+ * mpe_gg20_presig_import    EMPTY -> READY.  Refused (832): a version, number of local parties or ordinals that are not the pool's; a
+ *     signer-set mask that is none of the key object's sets (the slot remembers which one); a key-set index out of range or a y that is not that key set's; an R that is no valid curve point; a k_i outside
  *     (0, q) or a sigma_i outside [0, q).
  *     The RECORD, mpe_gg20_presig_record_words(pool) = 28 + 32 n_local little-endian 32-bit words:
  *       [0] MPE_GG20_PRESIG_RECORD_VERSION | [1] signer-set mask (bit = party index) | [2] n_local | [3..10] local ordinals (unused: 0)
@@ -532,6 +568,9 @@ int mpe_gg20_session_fault_inject(mpe_gg20_session* sess, int step, uint32_t par
  *     claim.  A record holds k_i in the clear: importing one record twice, or into two pools, is the nonce reuse the slots prevent.
  * mpe_gg20_presig_discard   READY, SIGNED or EMPTY -> EMPTY with the wipe (a slot that a running call on another stream holds BUSY is
  *     left to that call).
+ * A slot remembers the signer set its session signed with (mpe_gg20_session_create_sets; set 0 otherwise) beside the key set: export
+ * writes that set's party mask into word [1].  sign and complete need no set.  Sessions whose local party was given by index are not
+ * deposited (MPE_E_ARG): the pool's local parties are ordinals.
  * mpe_gg20_presig_pool_audit  h_out[0..3] = slots that are EMPTY, READY, SIGNED, BUSY; h_out[4] = non-zero words of k_i, sigma_i in
  *     slots that are not READY (must be 0).  Synchronises the stream. */
 #define MPE_GG20_PRESIG_RECORD_VERSION 1
@@ -584,6 +623,12 @@ int mpe_gg20_blame5(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, const in
 typedef struct { const uint32_t *k, *k_rand, *miu, *miu_rand, *a1, *a2, *z, *S, *c_a, *c_b, *R; } mpe_gg20_blame6_in;
 int mpe_gg20_blame6(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, const int32_t* d_keyset, const mpe_gg20_blame6_in* in,
                     uint32_t* d_bad_actors, void* stream);
+/* The two for sessions that name their signer set (d_sigset [batch], NULL = set 0; an index out of range reads as set 0): the [S]
+ * dimension and the bad_actors bits are ordinals of each session's own set.  blame7 needs no set. */
+int mpe_gg20_blame5_sets(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, const int32_t* d_keyset, const int32_t* d_sigset,
+                         const mpe_gg20_blame5_in* in, uint32_t* d_bad_actors, void* stream);
+int mpe_gg20_blame6_sets(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, const int32_t* d_keyset, const int32_t* d_sigset,
+                         const mpe_gg20_blame6_in* in, uint32_t* d_bad_actors, void* stream);
 /* `GlobalStatePhase7::phase7_blame` (blame.rs:434-454), called when the signature did not verify (status 701):
  *   s [B][S][8] (partial signatures); r, m [B][8]; R_dash, S [B][S][16]; R [B][16]:  R s_i == m R_dash_i + r S_i. */
 typedef struct { const uint32_t *s, *r, *R_dash, *m, *R, *S; } mpe_gg20_blame7_in;
@@ -613,6 +658,11 @@ int mpe_ecddh_verify(mpe_ctx* ctx, int batch, const mpe_ecddh_statement* stateme
 int mpe_gg20_sign(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, const int32_t* d_keyset, const mpe_gg20_nonces* nonces,
                   uint32_t* d_r, uint32_t* d_s, int32_t* d_recid, uint32_t* d_R, int32_t* d_status, int dedup_verify, int chunk,
                   void* stream);
+/* ... with a signer set per session (d_sigset [batch], device; NULL = mpe_gg20_sign): `keys` must hold the secrets of every member of
+ * every one of its sets.  A session whose index is out of range ends with status MPE_GG20_STATUS_BAD_SET and zero outputs. */
+int mpe_gg20_sign_sets(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, const int32_t* d_keyset, const int32_t* d_sigset,
+                       const mpe_gg20_nonces* nonces, uint32_t* d_r, uint32_t* d_s, int32_t* d_recid, uint32_t* d_R, int32_t* d_status,
+                       int dedup_verify, int chunk, void* stream);
 
 /* ---- a stream of batches: the pipelined engine ------------------------------------------------------------------------
  * A signing service receives batch after batch of `batch` sessions (BASELINE config 4: 1 024) and one such batch alone is

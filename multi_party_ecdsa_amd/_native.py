@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("MPE_LIB_PATH") or os.path.join(_HERE, "libmpecdsa_hip
 
 MPE_OK, MPE_E_ARG, MPE_E_HIP, MPE_E_NOMEM = 0, -1, -2, -3
 GG20_STATUS_BAD_NONCE = 91                    # include/mpecdsa_hip.h MPE_GG20_STATUS_BAD_NONCE
+GG20_STATUS_BAD_SET = 92                      # MPE_GG20_STATUS_BAD_SET
 # the presignature pool's row statuses and record version (include/mpecdsa_hip.h MPE_GG20_PRESIG_*)
 PRESIG_RECORD_VERSION = 1
 PRESIG_DEPOSIT_RANGE, PRESIG_DEPOSIT_NOT_EMPTY, PRESIG_SESSION_FAILED = 801, 802, 803
@@ -163,10 +164,12 @@ def _load():
                                   C.POINTER(BobProof), u32p, vp]),
         "mpe_bob_verify": (ip, [vp, vp, vp, ip, i32p, i32p, u32p, u32p, C.POINTER(BobProof), u32p, u32p, vp, vp]),
         "mpe_gg20_keys_create": (ip, [vp, ip, ip, ip, C.POINTER(C.c_int32), ip, ip, C.POINTER(C.c_int32)] + [u32p] * 9 + [C.POINTER(vp), vp]),
+        "mpe_gg20_keys_create_sets": (ip, [vp, ip, ip, ip, ip, C.POINTER(C.c_int32), ip, ip, C.POINTER(C.c_int32)] + [u32p] * 9 + [C.POINTER(vp), vp]),
         "mpe_gg20_keys_destroy": (ip, [vp]),
         "mpe_gg20_keys_fb_window_bits": (ip, [vp]),
         "mpe_gg20_msg_words": (ip, [ip, ip, ip]),
         "mpe_gg20_session_create": (ip, [vp, vp, ip, ip, C.POINTER(C.c_int32), i32p, C.POINTER(Gg20Nonces), ip, C.POINTER(vp), vp]),
+        "mpe_gg20_session_create_sets": (ip, [vp, vp, ip, ip, C.POINTER(C.c_int32), i32p, i32p, ip, C.POINTER(Gg20Nonces), ip, C.POINTER(vp), vp]),
         "mpe_gg20_session_destroy": (ip, [vp, vp]),
         "mpe_gg20_round0": (ip, [vp, u32p, vp]),
         "mpe_gg20_round1": (ip, [vp, u32p, C.POINTER(C.c_int64), u32p, vp]),
@@ -186,6 +189,11 @@ def _load():
         "mpe_hash_commit_point": (ip, [vp, ip, u32p, u32p, u32p, vp]),
         "mpe_gg20_session_fault_inject": (ip, [vp, ip, C.c_uint32]),
         "mpe_gg20_session_rearm": (ip, [vp, i32p, C.POINTER(Gg20Nonces), vp]),
+        "mpe_gg20_session_rearm_sets": (ip, [vp, i32p, i32p, C.POINTER(Gg20Nonces), vp]),
+        "mpe_gg20_sign_sets": (ip, [vp, vp, ip, i32p, i32p, C.POINTER(Gg20Nonces), u32p, u32p, vp, u32p, vp, ip, ip, vp]),
+        "mpe_gg20_blame5_sets": (ip, [vp, vp, ip, i32p, i32p, C.POINTER(Blame5In), u32p, vp]),
+        "mpe_gg20_blame6_sets": (ip, [vp, vp, ip, i32p, i32p, C.POINTER(Blame6In), u32p, vp]),
+        "mpe_gg20_sample_nonces_sets": (ip, [vp, vp, ip, ip, C.POINTER(C.c_int32), i32p, i32p, ip, C.c_char_p, C.c_uint64, C.POINTER(Gg20Nonces), i32p, vp]),
         "mpe_gg20_session_abort": (ip, [vp, vp]),
         "mpe_gg20_presig_pool_create": (ip, [vp, vp, ip, C.POINTER(C.c_int32), ip, C.POINTER(vp)]),
         "mpe_gg20_presig_pool_destroy": (ip, [vp]),
@@ -330,7 +338,9 @@ EXPORTED = ["mpe_version", "mpe_last_error", "mpe_ctx_create", "mpe_ctx_destroy"
             "mpe_gg18_phase5d", "mpe_gg18_output_signature",
             "mpe_gg20_presig_pool_create", "mpe_gg20_presig_pool_destroy", "mpe_gg20_presig_pool_capacity", "mpe_gg20_presig_record_words",
             "mpe_gg20_presig_deposit", "mpe_gg20_presig_sign", "mpe_gg20_presig_complete", "mpe_gg20_presig_export", "mpe_gg20_presig_import",
-            "mpe_gg20_presig_discard", "mpe_gg20_presig_pool_audit"]
+            "mpe_gg20_presig_discard", "mpe_gg20_presig_pool_audit",
+            "mpe_gg20_keys_create_sets", "mpe_gg20_session_create_sets", "mpe_gg20_session_rearm_sets", "mpe_gg20_sign_sets",
+            "mpe_gg20_sample_nonces_sets", "mpe_gg20_blame5_sets", "mpe_gg20_blame6_sets"]
 
 
 def check(rc, what):

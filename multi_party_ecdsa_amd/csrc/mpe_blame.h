@@ -89,7 +89,7 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC gni_kernel(Dim d, const uint32_
   const int S = d.S, P1 = S - 1;
   if (pp >= d.B * S * P1) return;
   const int j = pp % P1, pi = pp / P1, i = pi % S, b = pi / S, ind = ind_of(i, j);
-  const ec::Jac a = ec::jac_mul(ec::sc_reduce(k + (size_t)pi * 8, 8), ec::aff_load(gw + ((size_t)gg::ks_of(d, b) * S + ind) * 16));
+  const ec::Jac a = ec::jac_mul(ec::sc_reduce(k + (size_t)pi * 8, 8), ec::aff_load(gg::gw_of(d, gw, b, ind)));
   const ec::Jac m = ec::jac_mul_gen(ec::sc_neg(ec::sc_reduce(miu + (size_t)pp * 64, 64)));
   ec::aff_store(gni + (size_t)pp * 16, ec::jac_to_aff(ec::jac_add(a, m)));
 }
@@ -108,7 +108,7 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC gsigma_kernel(Dim d, const uint
   const int S = d.S, P1 = S - 1;
   if (pi >= d.B * S) return;
   const int i = pi % S, b = pi / S;
-  ec::Jac acc = ec::jac_mul(ec::sc_reduce(k + (size_t)pi * 8, 8), ec::aff_load(gw + ((size_t)gg::ks_of(d, b) * S + i) * 16));
+  ec::Jac acc = ec::jac_mul(ec::sc_reduce(k + (size_t)pi * 8, 8), ec::aff_load(gg::gw_of(d, gw, b, i)));
   ec::U256 ms = ec::u256_zero();
   for (int j = 0; j < P1; ++j) ms = ec::sc_add(ms, ec::sc_reduce(miu + ((size_t)pi * P1 + j) * 64, 64));
   acc = ec::jac_add(acc, ec::jac_mul_gen(ms));
@@ -202,11 +202,12 @@ __global__ void miu_out_kernel(Dim d, const uint32_t* __restrict__ miu, uint32_t
   out[((pi % d.L) * d.B + pi / d.L) * per + w] = miu[g];
 }
 
-static Dim blame_dim(const mpe_ctx* ctx, const mpe_gg20_keys* K, int B, const int32_t* d_keyset) {
+static Dim blame_dim(const mpe_ctx* ctx, const mpe_gg20_keys* K, int B, const int32_t* d_keyset, const int32_t* d_sigset) {
   Dim d{};
   d.enc = ctx->enc;
-  d.B = B; d.S = K->S; d.n = K->n; d.L = K->S; d.K = K->K; d.n_own = K->n_own; d.ks = d_keyset;
-  for (int i = 0; i < 8; ++i) { d.loc[i] = i; d.sg[i] = K->signers[i]; d.oslot[i] = K->own_slot[i] < 0 ? 0 : K->own_slot[i]; }
+  gg::dim_of_keys(d, K, d_keyset, d_sigset);
+  d.B = B; d.L = K->S;
+  for (int i = 0; i < 8; ++i) d.loc[i] = i;
   return d;
 }
 
@@ -274,13 +275,17 @@ int mpe_paillier_open(mpe_ctx* ctx, const mpe_paillier* sk, int batch, const int
 
 int mpe_gg20_blame5(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, const int32_t* d_keyset, const mpe_gg20_blame5_in* in,
                     uint32_t* d_bad_actors, void* stream) {
+  return mpe_gg20_blame5_sets(ctx, keys, batch, d_keyset, nullptr, in, d_bad_actors, stream);
+}
+int mpe_gg20_blame5_sets(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, const int32_t* d_keyset, const int32_t* d_sigset,
+                         const mpe_gg20_blame5_in* in, uint32_t* d_bad_actors, void* stream) {
   if (!ctx || !keys || !in || !d_bad_actors || batch < 0 || (keys->K > 1 && !d_keyset)) return MPE_E_ARG;
   if (!in->k || !in->k_rand || !in->gamma || !in->beta_tag || !in->beta_rand || !in->delta || !in->g_gamma || !in->c_a || !in->c_b) return MPE_E_ARG;
   if (batch == 0) return MPE_OK;
   using namespace mpe;
   hipStream_t st = (hipStream_t)stream;
   const int S = keys->S, P1 = S - 1, nPI = batch * S, nPP = nPI * P1;
-  const bl::Dim d = bl::blame_dim(ctx, keys, batch, d_keyset);
+  const bl::Dim d = bl::blame_dim(ctx, keys, batch, d_keyset, d_sigset);
   // own arrays at the top of the workspace (never handed out, never moved: ws_top), the Paillier composites below
   const size_t own = ((size_t)nPI * (64 + 128) + (size_t)nPP * 128) * 4 + ((size_t)nPI + 3 * (size_t)nPP) * 4 + (size_t)nPI * 2 + nPP + 16 * 256;   // BIdx: one [nPI] + three [nPP] arrays; 256 B slack per take()
   MPE_TRY(ws_reserve(ctx, own + ws_need_encrypt(nPI) + ws_need_mul_add_enc(nPP) + (1u << 20), st));
@@ -315,13 +320,17 @@ int mpe_gg20_blame5(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, const in
 
 int mpe_gg20_blame6(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, const int32_t* d_keyset, const mpe_gg20_blame6_in* in,
                     uint32_t* d_bad_actors, void* stream) {
+  return mpe_gg20_blame6_sets(ctx, keys, batch, d_keyset, nullptr, in, d_bad_actors, stream);
+}
+int mpe_gg20_blame6_sets(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, const int32_t* d_keyset, const int32_t* d_sigset,
+                         const mpe_gg20_blame6_in* in, uint32_t* d_bad_actors, void* stream) {
   if (!ctx || !keys || !in || !d_bad_actors || batch < 0 || (keys->K > 1 && !d_keyset)) return MPE_E_ARG;
   if (!in->k || !in->k_rand || !in->miu || !in->miu_rand || !in->a1 || !in->a2 || !in->z || !in->S || !in->c_a || !in->c_b || !in->R) return MPE_E_ARG;
   if (batch == 0) return MPE_OK;
   using namespace mpe;
   hipStream_t st = (hipStream_t)stream;
   const int S = keys->S, P1 = S - 1, nPI = batch * S, nPP = nPI * P1;
-  const bl::Dim d = bl::blame_dim(ctx, keys, batch, d_keyset);
+  const bl::Dim d = bl::blame_dim(ctx, keys, batch, d_keyset, d_sigset);
   const size_t own = ((size_t)nPI * (64 + 128) + (size_t)nPP * (128 + 16)) * 4 + ((size_t)nPI + 3 * (size_t)nPP) * 4 + (size_t)nPI * 2 + nPP + 16 * 256;   // BIdx: one [nPI] + three [nPP] arrays; 256 B slack per take()
   MPE_TRY(ws_reserve(ctx, own + ws_need_encrypt(nPP) + (1u << 20), st));
   char* top = (char*)ctx->ws + ctx->ws_bytes;

@@ -51,7 +51,11 @@ __global__ void bounds_kernel(int count, const uint32_t* __restrict__ N, const u
 
 struct mpe_gg20_keys {
   int t = 0, n = 0, S = 0, K = 1, n_own = 0;
-  int signers[8] = {0};
+  int signers[8] = {0};            // signer set 0: what every entry point without a per-session set means
+  int nsets = 1;                    // signer sets of this object (mpe_gg20_keys_create_sets), all of S parties
+  uint32_t sets4[256] = {0};        // set -> its party indices, ascending, four bits each (ordinal i in bits [4 i, 4 i + 4))
+  uint32_t masks[256] = {0};        // set -> bit mask over party indices
+  uint32_t* d_sets = nullptr;       // [nsets] sets4 on the device, then [nsets] the sets as bit masks over party indices
   int own[8] = {0};                 // party indices whose secrets this object holds
   int own_slot[8] = {0};            // party index -> slot in own, or -1
   mpe_paillier* pub = nullptr;      // K*n public Paillier keys (key set kk, party a = key kk*n + a)
@@ -62,7 +66,7 @@ struct mpe_gg20_keys {
   uint32_t* x = nullptr;            // [K][n_own][8]  key shares of the own parties
   uint32_t* X = nullptr;            // [K][n][16]     pk_vec
   uint32_t* y = nullptr;            // [K][16]        group public key
-  uint32_t* gw = nullptr;           // [K][S][16]     g_w_vec = lambda_j X_j (SignKeys::g_w_vec, party_i.rs:527-544)
+  uint32_t* gw = nullptr;           // [K][nsets][S][16]  g_w_vec = lambda_j X_j of every set (SignKeys::g_w_vec, party_i.rs:527-544)
   mpe::smp::Bounds bounds{};        // sampling ranges (mpe_sample.h): q [8], q^3 [24], N-2 [K*n][64], q N~ [K*n][72], q^3 N~ [K*n][88]
 };
 
@@ -77,12 +81,40 @@ struct Dim {
   int oslot[8];      // party index -> slot among the own parties
   const int32_t* ks; // [B] key set of a session, or null
   ec::Enc enc;       // the context's transcript conventions (include/mpecdsa_hip.h: mpe_encoding), copied when the object is built
+  // per-session signer sets (mpe_gg20_*_sets); ss == null: every session signs with set 0 = sg
+  const int32_t* ss;     // [B] signer set of a session, or null
+  const uint32_t* sets;  // [nsets] a set's party indices, four bits per signer ordinal (mpe_gg20_keys::d_sets)
+  uint32_t sg4;          // sg in that form
+  int nsets;             // sets of the key object (the gw table is [K][nsets][S][16])
+  int lparty;            // >= 0: the ONE local party, by party index: its ordinal in session b is its rank in that session's set; -1: loc
 };
 __device__ __forceinline__ int ind_of(int i, int jj) { return jj < i ? jj : jj + 1; }
 __device__ __forceinline__ int jme_of(int i, int ind) { return i < ind ? i : i - 1; }
 __device__ __forceinline__ int ks_of(const Dim& d, int b) { return d.ks ? d.ks[b] : 0; }
-__device__ __forceinline__ int kpub(const Dim& d, int b, int i) { return ks_of(d, b) * d.n + d.sg[i]; }
-__device__ __forceinline__ int kown(const Dim& d, int b, int i) { return ks_of(d, b) * d.n_own + d.oslot[d.sg[i]]; }
+// the signer set of session b: its index (an index outside the table reads as set 0 — r0_kernel stops such a session with
+// MPE_GG20_STATUS_BAD_SET, here it only has to index inside the tables), its packed party indices, the party of ordinal i
+__device__ __forceinline__ bool ss_valid(const Dim& d, int b) { return !d.ss || (unsigned)d.ss[b] < (unsigned)d.nsets; }
+__device__ __forceinline__ int ss_of(const Dim& d, int b) { return d.ss && ss_valid(d, b) ? d.ss[b] : 0; }
+__device__ __forceinline__ uint32_t set4_of(const Dim& d, int b) { return d.ss ? d.sets[ss_of(d, b)] : d.sg4; }
+__device__ __forceinline__ int sg_of(const Dim& d, int b, int i) { return (int)((set4_of(d, b) >> (4 * i)) & 15u); }
+__device__ __forceinline__ int rank_in(uint32_t set4, int S, int party) {
+  int r = -1;
+  for (int i = 0; i < S; ++i) if ((int)((set4 >> (4 * i)) & 15u) == party) r = i;
+  return r;
+}
+// signer ordinal of local slot li in session b (a by-index party that is not in the session's set: ordinal 0, stopped by r0_kernel)
+__device__ __forceinline__ int loc_of(const Dim& d, int b, int li) {
+  if (d.lparty < 0) return d.loc[li];
+  const int r = rank_in(set4_of(d, b), d.S, d.lparty);
+  return r < 0 ? 0 : r;
+}
+__device__ __forceinline__ int kpub(const Dim& d, int b, int i) { return ks_of(d, b) * d.n + sg_of(d, b, i); }
+// (i is a LOCAL party's ordinal)
+__device__ __forceinline__ int kown(const Dim& d, int b, int i) { return ks_of(d, b) * d.n_own + d.oslot[d.lparty >= 0 ? d.lparty : sg_of(d, b, i)]; }
+// g_w of signer ordinal `ind` in session b
+__device__ __forceinline__ const uint32_t* gw_of(const Dim& d, const uint32_t* gw, int b, int ind) {
+  return gw + (((size_t)ks_of(d, b) * d.nsets + ss_of(d, b)) * d.S + ind) * 16;
+}
 
 // incoming message slab: sender j's [B][W] block starts at record off[j]
 struct Slab { const uint32_t* p; long long off[8]; int W; };
@@ -102,28 +134,28 @@ __global__ void idx_kernel(Dim d, Idx x, int total) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= total) return;
   const int S = d.S, n = d.n, L = d.L, P1 = S - 1;
-  if (g < d.B * L) { const int b = g / L; x.kown_pi[g] = kown(d, b, d.loc[g % L]); }
+  if (g < d.B * L) { const int b = g / L; x.kown_pi[g] = kown(d, b, loc_of(d, b, g % L)); }
   if (g < d.B * L * n) {
     const int pi = g / n, b = pi / L;
-    x.pi_ap[g] = pi; x.kown_ap[g] = kown(d, b, d.loc[pi % L]); x.st_ap[g] = ks_of(d, b) * n + g % n;
+    x.pi_ap[g] = pi; x.kown_ap[g] = kown(d, b, loc_of(d, b, pi % L)); x.st_ap[g] = ks_of(d, b) * n + g % n;
   }
   if (g < d.B * L * P1 * d.V * n) {
-    const int st = g % n, r1 = g / n, r2 = r1 / d.V, jj = r2 % P1, pi = r2 / P1, i = d.loc[pi % L], b = pi / L;
+    const int st = g % n, r1 = g / n, r2 = r1 / d.V, jj = r2 % P1, pi = r2 / P1, b = pi / L, i = loc_of(d, b, pi % L);
     const int ind = ind_of(i, jj);
     x.ca_vi[g] = ind * d.B + b; x.kpub_vi[g] = kpub(d, b, ind); x.st_vi[g] = ks_of(d, b) * n + st;
   }
   if (g < d.B * L * P1 * 2) {
-    const int pp = g >> 1, jj = pp % P1, pi = pp / P1, i = d.loc[pi % L], b = pi / L, ind = ind_of(i, jj);
+    const int pp = g >> 1, jj = pp % P1, pi = pp / P1, b = pi / L, i = loc_of(d, b, pi % L), ind = ind_of(i, jj);
     x.ca_mb[g] = ind * d.B + b; x.kpub_mb[g] = kpub(d, b, ind); x.kown_mb[g] = kown(d, b, i);
   }
   if (g < d.B * L * P1) {
-    const int jj = g % P1, pi = g / P1, i = d.loc[pi % L], b = pi / L;
-    x.pi_pp[g] = pi; x.kown_pp[g] = kown(d, b, i); x.st_pp[g] = ks_of(d, b) * n + d.sg[ind_of(i, jj)];
+    const int jj = g % P1, pi = g / P1, b = pi / L, i = loc_of(d, b, pi % L);
+    x.pi_pp[g] = pi; x.kown_pp[g] = kown(d, b, i); x.st_pp[g] = ks_of(d, b) * n + sg_of(d, b, ind_of(i, jj));
   }
   if (g < d.B * d.PV * S * P1) {
     const int jj = g % P1, r1 = g / P1, i = r1 % S, r2 = r1 / S, vl = r2 % d.PV, b = r2 / d.PV;
     x.ca_pv[g] = i * d.B + b; x.pi_pv[g] = b * L + vl; x.kpub_pv[g] = kpub(d, b, i);
-    x.st_pv[g] = ks_of(d, b) * n + d.sg[ind_of(i, jj)];
+    x.st_pv[g] = ks_of(d, b) * n + sg_of(d, b, ind_of(i, jj));
   }
 }
 
@@ -173,7 +205,7 @@ __global__ void __launch_bounds__(64) validate_kernel(Dim d, Slab in, int round,
   MPE_FOREGROUND();
   const int pi = blockIdx.x * blockDim.x + threadIdx.x;
   if (pi >= d.B * d.L) return;
-  const int i = d.loc[pi % d.L], b = pi / d.L, P1 = d.S - 1;
+  const int b = pi / d.L, i = loc_of(d, b, pi % d.L), P1 = d.S - 1;
   uint32_t mask = 0;
   for (int j = 0; j < d.S; ++j) {
     if (j == i) continue;
@@ -211,12 +243,25 @@ __device__ inline ec::U256 lagrange0(const int* sg, int S, int i) {
   }
   return ec::sc_mul(num, ec::sc_inv(den));
 }
-// g_w_vec of a key set: lambda_j X_j for every signer (once per key object)
+// the same over a set in its packed form (party index of ordinal j in bits [4 j, 4 j + 4))
+__device__ inline ec::U256 lagrange0(uint32_t set4, int S, int i) {
+  ec::U256 num = ec::u256_one(), den = ec::u256_one();
+  ec::U256 xi = ec::u256_zero(); xi.w[0] = ((set4 >> (4 * i)) & 15u) + 1u;
+  for (int j = 0; j < S; ++j) {
+    if (j == i) continue;
+    ec::U256 xj = ec::u256_zero(); xj.w[0] = ((set4 >> (4 * j)) & 15u) + 1u;
+    num = ec::sc_mul(num, xj);
+    den = ec::sc_mul(den, ec::sc_sub(xj, xi));
+  }
+  return ec::sc_mul(num, ec::sc_inv(den));
+}
+// g_w_vec of a key set: lambda_j X_j for every signer of every signer set (once per key object); gw [K][nsets][S][16]
 __global__ void __launch_bounds__(64) MPE_EC_OCC gw_kernel(Dim d, const uint32_t* __restrict__ Xs, uint32_t* __restrict__ gw) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= d.K * d.S) return;
-  const int kk = g / d.S, j = g % d.S;
-  ec::aff_store(gw + (size_t)g * 16, ec::mul_aff(lagrange0(d.sg, d.S, j), ec::aff_load(Xs + ((size_t)kk * d.n + d.sg[j]) * 16)));
+  if (g >= d.K * d.nsets * d.S) return;
+  const int kk = g / (d.nsets * d.S), j = g % d.S;
+  const uint32_t set4 = d.sets[(g / d.S) % d.nsets];
+  ec::aff_store(gw + (size_t)g * 16, ec::mul_aff(lagrange0(set4, d.S, j), ec::aff_load(Xs + ((size_t)kk * d.n + ((set4 >> (4 * j)) & 15u)) * 16)));
 }
 
 // ---- Round 0: SignKeys::create + phase1_broadcast (party_i.rs:546-589) ----------------------------
@@ -226,14 +271,17 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r0_kernel(Dim d, const uint32_t
                           uint32_t* __restrict__ com, int32_t* __restrict__ status, uint32_t* __restrict__ bad) {
   const int pi = blockIdx.x * blockDim.x + threadIdx.x;
   if (pi >= d.B * d.L) return;
-  const int i = d.loc[pi % d.L], b = pi / d.L;
+  const int b = pi / d.L, i = loc_of(d, b, pi % d.L);
+  // a session whose set index is not one of the key object's, or whose by-index local party is not in its set, names no quorum this
+  // party can sign in: it stops here with MPE_GG20_STATUS_BAD_SET (everything it indexed went through set 0 / ordinal 0)
+  if (!ss_valid(d, b) || (d.lparty >= 0 && rank_in(set4_of(d, b), d.S, d.lparty) < 0)) fail(status, bad, pi, MPE_GG20_STATUS_BAD_SET, 0);
   // k_i, gamma_i are `Scalar::random()` (party_i.rs:561-563): non-zero and below q.  Anything else is not a value the reference can
   // hold — it is what the device sampler leaves when a rejection loop gave up (mpe_sample.h), or a caller's mistake — and the
   // party stops here: status MPE_GG20_STATUS_BAD_NONCE, no message leaves it
   const bool k_ok = ec::sc_is_canonical_nonzero(k_in + (size_t)pi * 8), g_ok = ec::sc_is_canonical_nonzero(gamma_in + (size_t)pi * 8);
   if (!k_ok || !g_ok) fail(status, bad, pi, MPE_GG20_STATUS_BAD_NONCE, 0);
   const ec::U256 k = ec::sc_reduce(k_in + (size_t)pi * 8, 8), g = ec::sc_reduce(gamma_in + (size_t)pi * 8, 8);
-  const ec::U256 wi = ec::sc_mul(lagrange0(d.sg, d.S, i), ec::sc_reduce(xs + (size_t)kown(d, b, i) * 8, 8));
+  const ec::U256 wi = ec::sc_mul(lagrange0(set4_of(d, b), d.S, i), ec::sc_reduce(xs + (size_t)kown(d, b, i) * 8, 8));
   ec::u256_store(kq + (size_t)pi * 8, k);
   ec::u256_store(gq + (size_t)pi * 8, g);
   ec::u256_store(w + (size_t)pi * 8, wi);
@@ -249,7 +297,7 @@ __global__ void idx1_kernel(Dim d, Slab in0, int32_t* __restrict__ sub0_vi) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
   const int P1 = d.S - 1;
   if (g >= d.B * d.L * P1 * d.V * d.n) return;
-  const int st = g % d.n, r1 = g / d.n, r2 = r1 / d.V, jj = r2 % P1, pi = r2 / P1, i = d.loc[pi % d.L], b = pi / d.L;
+  const int st = g % d.n, r1 = g / d.n, r2 = r1 / d.V, jj = r2 % P1, pi = r2 / P1, b = pi / d.L, i = loc_of(d, b, pi % d.L);
   sub0_vi[g] = (int32_t)(rec_index(in0, ind_of(i, jj), b) * (d.n + 1) + st);
 }
 // per MessageB the multiplier b, beta_tag mod q, beta = -beta_tag (mta/mod.rs:132,146)
@@ -282,7 +330,7 @@ __global__ void idx2_kernel(Dim d, Slab in1, int32_t* __restrict__ sub1_rv) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
   const int P1 = d.S - 1;
   if (g >= d.B * d.L * P1 * 2) return;
-  const int v = g & 1, pp = g >> 1, jj = pp % P1, pi = pp / P1, i = d.loc[pi % d.L], b = pi / d.L, ind = ind_of(i, jj);
+  const int v = g & 1, pp = g >> 1, jj = pp % P1, pi = pp / P1, b = pi / d.L, i = loc_of(d, b, pi % d.L), ind = ind_of(i, jj);
   sub1_rv[g] = (int32_t)(rec_index(in1, ind, b) * (2 * P1) + jme_of(i, ind) * 2 + v);
 }
 // MessageB::verify_proofs_get_alpha after the decryption (mta/mod.rs:166-178) and the check of rounds.rs:281
@@ -290,7 +338,7 @@ __global__ void idx2_kernel(Dim d, Slab in1, int32_t* __restrict__ sub1_rv) {
 __device__ __forceinline__ void r2a_finish(const Dim& d, int rv, int v, int pp, int b, int ind, const ec::Aff& Bpk, bool good,
                                            const uint32_t* gw, uint32_t* bpk_in, uint8_t* code) {
   uint8_t c = good ? 0 : 1;
-  if (v == 1) { if (!c && !ec::aff_eq(Bpk, ec::aff_load(gw + ((size_t)ks_of(d, b) * d.S + ind) * 16))) c = 2; }   // rounds.rs:281
+  if (v == 1) { if (!c && !ec::aff_eq(Bpk, ec::aff_load(gw_of(d, gw, b, ind)))) c = 2; }   // rounds.rs:281
   else ec::aff_store(bpk_in + (size_t)pp * 16, Bpk);                                          // mb_gamma_s[jj].b_proof.pk, for phase4
   code[rv] = c;
 }
@@ -301,7 +349,7 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r2a_kernel(Dim d, const int32_t
   const int rv = blockIdx.x * blockDim.x + threadIdx.x;
   const int P1 = d.S - 1;
   if (rv >= d.B * d.L * P1 * 2) return;
-  const int v = rv & 1, pp = rv >> 1, jj = pp % P1, pi = pp / P1, i = d.loc[pi % d.L], b = pi / d.L, ind = ind_of(i, jj);
+  const int v = rv & 1, pp = rv >> 1, jj = pp % P1, pi = pp / P1, b = pi / d.L, i = loc_of(d, b, pi % d.L), ind = ind_of(i, jj);
   const uint32_t* m = in1 + (size_t)sub1_rv[rv] * SUB1;
   const ec::U256 al = ec::sc_reduce(alpha_full + (size_t)rv * 64, 64);
   ec::u256_store(alpha + (size_t)rv * 8, al);
@@ -348,7 +396,7 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r2b_kernel(Dim d, const uint32_
     for (int v = 0; v < 2 && !st; ++v) if (code[m0 + v]) st = 200 + code[m0 + v];          // the loop order of rounds.rs:260-286
   }
   if (st) fail(status, bad, pi, st, 0);
-  if ((fault_mask >> d.loc[pi % d.L]) & 1u) {          // the corrupt_step of the reference's tests (test.rs:458-465)
+  if ((fault_mask >> loc_of(d, pi / d.L, pi % d.L)) & 1u) {          // the corrupt_step of the reference's tests (test.rs:458-465)
     if (fault_step == 5) de = ec::sc_add(de, de);
     if (fault_step == 6) si = ec::sc_add(si, si);
   }
@@ -411,7 +459,7 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r4_kernel(Dim d, Slab in3, cons
   MPE_FOREGROUND();
   const int pi = blockIdx.x * blockDim.x + threadIdx.x;
   if (pi >= d.B * d.L) return;
-  const int P1 = d.S - 1, i = d.loc[pi % d.L], b = pi / d.L;
+  const int P1 = d.S - 1, b = pi / d.L, i = loc_of(d, b, pi % d.L);
   uint32_t mask = 0;
   for (int jj = 0; jj < P1; ++jj) {
     const int ind = ind_of(i, jj);
@@ -523,7 +571,7 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r2a_group_kernel(Dim d, const i
   const int P1 = d.S - 1;
   const bool live = rv < d.B * d.L * P1 * 2;
   const int rvc = live ? rv : 0;
-  const int v = rvc & 1, pp = rvc >> 1, jj = pp % P1, pi = pp / P1, i = d.loc[pi % d.L], b = pi / d.L, ind = ind_of(i, jj);
+  const int v = rvc & 1, pp = rvc >> 1, jj = pp % P1, pi = pp / P1, b = pi / d.L, i = loc_of(d, b, pi % d.L), ind = ind_of(i, jj);
   const uint32_t* m = in1 + (size_t)sub1_rv[rvc] * SUB1;
   const ec::U256 al = ec::sc_reduce(alpha_full + (size_t)rvc * 64, 64);
   const ec::Aff Bpk = ec::aff_load(m + M1.b_pk.off), BTpk = ec::aff_load(m + M1.bt_pk.off);
@@ -629,7 +677,7 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r7_kernel(Dim d, const uint32_t
   ec::u256_store(mq + (size_t)pi * 8, m);
   ec::u256_store(rq + (size_t)pi * 8, r);
   ec::U256 si = ec::sc_add(ec::sc_mul(m, ec::u256_load(kq + (size_t)pi * 8)), ec::sc_mul(r, ec::u256_load(sigma_i + (size_t)pi * 8)));
-  if (fault_step == 7 && ((fault_mask >> d.loc[pi % d.L]) & 1u)) si = ec::sc_add(si, si);              // test.rs:679-686
+  if (fault_step == 7 && ((fault_mask >> loc_of(d, b, pi % d.L)) & 1u)) si = ec::sc_add(si, si);              // test.rs:679-686
   ec::u256_store(s_i + (size_t)pi * 8, si);
 }
 // output_signature + verify (party_i.rs:873-936) behind the sum: s is normalised to the low half with the recid flip (recid starts as
@@ -659,7 +707,7 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC complete_kernel(Dim d, Slab in6
                           uint32_t* __restrict__ s_out, int32_t* __restrict__ recid_out) {
   const int pi = blockIdx.x * blockDim.x + threadIdx.x;
   if (pi >= d.B * d.L) return;
-  const int li = pi % d.L, i = d.loc[li], b = pi / d.L;
+  const int li = pi % d.L, b = pi / d.L, i = loc_of(d, b, li);
   ec::U256 s = ec::u256_load(s_i + (size_t)pi * 8);
   for (int j = 0; j < d.S; ++j) if (j != i) s = ec::sc_add(s, ec::sc_reduce(rec_of(in6, j, b) + M7.s_i.off, 8));
   const ec::U256 m = ec::u256_load(mq + (size_t)pi * 8), r = ec::u256_load(rq + (size_t)pi * 8);
@@ -727,6 +775,7 @@ struct mpe_gg20_session {
   mpe_ctx* ctx = nullptr;
   const mpe_gg20_keys* K = nullptr;
   int B = 0, L = 0, dedup = 0, next_round = 0;
+  bool any_set = false;            // created with d_sigset: the local parties' secrets were checked against every set of the key object
   bool failed = false;             // a round call returned an error (MPE_E_NOMEM, a HIP failure): the batch cannot go on; rearm / abort start afresh
   mpe::gg::Dim d{};
   mpe_gg20_nonces Z{};
@@ -768,6 +817,35 @@ static void gg_trace(const mpe_ctx* ctx, hipStream_t st, const char* what, int r
   } while (0)
 
 static Counts counts_of(const Dim& d) { return counts_of(d.B, d.S, d.n, d.L, d.V, d.PV); }
+// what a Dim takes from the key object and the per-session choices (B, L, V, PV, loc are the caller's)
+static void dim_of_keys(Dim& d, const mpe_gg20_keys* K, const int32_t* d_keyset, const int32_t* d_sigset) {
+  d.S = K->S; d.n = K->n; d.K = K->K; d.n_own = K->n_own; d.ks = d_keyset;
+  d.ss = d_sigset; d.sets = K->d_sets; d.sg4 = K->sets4[0]; d.nsets = K->nsets; d.lparty = -1;
+  for (int i = 0; i < 8; ++i) { d.sg[i] = K->signers[i]; d.oslot[i] = K->own_slot[i] < 0 ? 0 : K->own_slot[i]; }
+}
+// The local parties of a batch: signer ordinals (positions in each session's own set), or with by_party ONE party index.  Checks that
+// the key object holds the secrets of every party a local ordinal can mean: with d_sigset in EVERY set of the object (the host never
+// sees the array), without it in set 0.  By index without d_sigset is the party's ordinal in set 0.
+static int local_parties(Dim& d, const mpe_gg20_keys* K, int n_local, const int32_t* h_local, const int32_t* d_sigset, int by_party) {
+  if (n_local < 1 || n_local > K->S || !h_local) return MPE_E_ARG;
+  d.L = n_local;
+  for (int i = 0; i < 8; ++i) d.loc[i] = 0;
+  if (by_party) {
+    if (n_local != 1) { mpe_set_error_msg("gg20: one local party by index"); return MPE_E_ARG; }
+    const int p = h_local[0];
+    if (p < 0 || p >= K->n || K->own_slot[p] < 0) { mpe_set_error_msg("gg20: the local party's secrets are not in the key object"); return MPE_E_ARG; }
+    if (d_sigset) { d.lparty = p; return MPE_OK; }
+    for (int i = 0; i < K->S; ++i) if (K->signers[i] == p) { d.loc[0] = i; return MPE_OK; }
+    mpe_set_error_msg("gg20: the local party is not a signer"); return MPE_E_ARG;
+  }
+  for (int i = 0; i < n_local; ++i) {
+    if (h_local[i] < 0 || h_local[i] >= K->S || (i && h_local[i] <= h_local[i - 1])) return MPE_E_ARG;
+    d.loc[i] = h_local[i];
+    for (int k = 0; k < (d_sigset ? K->nsets : 1); ++k)
+      if (K->own_slot[(K->sets4[k] >> (4 * h_local[i])) & 15u] < 0) { mpe_set_error_msg("gg20: a local party's secrets are not in the key object"); return MPE_E_ARG; }
+  }
+  return MPE_OK;
+}
 static bool small_batch(const mpe_ctx* ctx, size_t items) { return ctx->allow_par && items <= (size_t)ctx->par_items; }      // its composites fork
 static size_t ec_lanes_fit(const mpe_ctx* ctx) { return ctx->ec_lane_groups ? (size_t)ctx->cus * 4 * 64 * 2 / ctx->device_share : 0; }      // two waves per SIMD
 // assigns every state array (base == nullptr: only sizes)
@@ -1303,36 +1381,57 @@ int mpe_gg20_keys_create(mpe_ctx* ctx, int t, int n, int n_signers, const int32_
                          const int32_t* h_own, const uint32_t* d_x, const uint32_t* d_p, const uint32_t* d_q, const uint32_t* d_N,
                          const uint32_t* d_Nt, const uint32_t* d_h1, const uint32_t* d_h2, const uint32_t* d_y, const uint32_t* d_X,
                          mpe_gg20_keys** out, void* stream) {
+  return mpe_gg20_keys_create_sets(ctx, t, n, n_signers, 1, h_signers, nkeysets, n_own, h_own, d_x, d_p, d_q, d_N, d_Nt, d_h1, d_h2, d_y, d_X, out, stream);
+}
+
+int mpe_gg20_keys_create_sets(mpe_ctx* ctx, int t, int n, int n_signers, int n_sets, const int32_t* h_sets, int nkeysets, int n_own,
+                              const int32_t* h_own, const uint32_t* d_x, const uint32_t* d_p, const uint32_t* d_q, const uint32_t* d_N,
+                              const uint32_t* d_Nt, const uint32_t* d_h1, const uint32_t* d_h2, const uint32_t* d_y, const uint32_t* d_X,
+                              mpe_gg20_keys** out, void* stream) {
+  const int32_t* h_signers = h_sets;              // set 0
   if (!ctx || !h_signers || !h_own || !d_x || !d_p || !d_q || !d_N || !d_Nt || !d_h1 || !d_h2 || !d_y || !d_X || !out) return MPE_E_ARG;
   if (n < 2 || n > 8 || n_signers < 2 || n_signers > n || t < 1 || n_signers <= t || nkeysets < 1 || n_own < 1 || n_own > n) return MPE_E_ARG;
-  for (int i = 0; i < n_signers; ++i)
-    if (h_signers[i] < 0 || h_signers[i] >= n || (i && h_signers[i] <= h_signers[i - 1])) return MPE_E_ARG;
+  if (n_sets < 1 || n_sets > 256) return MPE_E_ARG;
+  uint32_t sets4[256], masks[256];
+  for (int k = 0; k < n_sets; ++k) {
+    const int32_t* row = h_sets + (size_t)k * n_signers;
+    sets4[k] = 0; masks[k] = 0;
+    for (int i = 0; i < n_signers; ++i) {
+      if (row[i] < 0 || row[i] >= n || (i && row[i] <= row[i - 1])) return MPE_E_ARG;
+      sets4[k] |= (uint32_t)row[i] << (4 * i); masks[k] |= 1u << row[i];
+    }
+    for (int m = 0; m < k; ++m) if (sets4[m] == sets4[k]) { mpe_set_error_msg("gg20 keys: two equal signer sets"); return MPE_E_ARG; }
+  }
   for (int i = 0; i < n_own; ++i)
     if (h_own[i] < 0 || h_own[i] >= n || (i && h_own[i] <= h_own[i - 1])) return MPE_E_ARG;
   hipStream_t st = (hipStream_t)stream;
   mpe_gg20_keys* K = new (std::nothrow) mpe_gg20_keys();
   if (!K) return MPE_E_NOMEM;
-  K->t = t; K->n = n; K->S = n_signers; K->K = nkeysets; K->n_own = n_own;
+  K->t = t; K->n = n; K->S = n_signers; K->K = nkeysets; K->n_own = n_own; K->nsets = n_sets;
+  for (int k = 0; k < n_sets; ++k) { K->sets4[k] = sets4[k]; K->masks[k] = masks[k]; }
   for (int a = 0; a < 8; ++a) K->own_slot[a] = -1;
   for (int i = 0; i < n_signers; ++i) K->signers[i] = h_signers[i];
   for (int i = 0; i < n_own; ++i) { K->own[i] = h_own[i]; K->own_slot[h_own[i]] = i; }
   const size_t kk = (size_t)nkeysets;
-  const size_t words = kk * n_own * 8 + kk * n * 16 + kk * 16 + kk * n_signers * 16 + 32 + kk * n * (64 + 72 + 88);
+  const size_t ngw = kk * n_sets * n_signers;
+  const size_t words = kk * n_own * 8 + kk * n * 16 + kk * 16 + ngw * 16 + 32 + kk * n * (64 + 72 + 88) + 2 * (size_t)n_sets;
   hipError_t e = hipMalloc(&K->blob, words * 4);
   if (e != hipSuccess) { delete K; mpe_set_error("hipMalloc(gg20 keys)", e); return MPE_E_NOMEM; }
   K->blob_bytes = words * 4;
   K->x = (uint32_t*)K->blob; K->X = K->x + kk * n_own * 8; K->y = K->X + kk * n * 16; K->gw = K->y + kk * 16;
-  K->bounds.q = K->gw + kk * n_signers * 16; K->bounds.q3 = K->bounds.q + 8; K->bounds.Nm2 = K->bounds.q3 + 24;
+  K->bounds.q = K->gw + ngw * 16; K->bounds.q3 = K->bounds.q + 8; K->bounds.Nm2 = K->bounds.q3 + 24;
   K->bounds.qNt = K->bounds.Nm2 + kk * n * 64; K->bounds.q3Nt = K->bounds.qNt + kk * n * 72;
+  K->d_sets = K->bounds.q3Nt + kk * n * 88;
+  (void)hipMemcpyAsync(K->d_sets, K->sets4, (size_t)n_sets * 4, hipMemcpyHostToDevice, st);
+  (void)hipMemcpyAsync(K->d_sets + n_sets, K->masks, (size_t)n_sets * 4, hipMemcpyHostToDevice, st);
   hipLaunchKernelGGL(mpe::smp::bounds_kernel, dim3(mpe::blocks_for(nkeysets * n + 1, 64)), dim3(64), 0, st, nkeysets * n, d_N, d_Nt, K->bounds);
   (void)hipMemcpyAsync(K->x, d_x, kk * n_own * 8 * 4, hipMemcpyDeviceToDevice, st);
   (void)hipMemcpyAsync(K->X, d_X, kk * n * 16 * 4, hipMemcpyDeviceToDevice, st);
   (void)hipMemcpyAsync(K->y, d_y, kk * 16 * 4, hipMemcpyDeviceToDevice, st);
   {
     mpe::gg::Dim d{};
-    d.S = n_signers; d.n = n; d.K = nkeysets;
-    for (int i = 0; i < n_signers; ++i) d.sg[i] = h_signers[i];
-    hipLaunchKernelGGL(mpe::gg::gw_kernel, dim3(mpe::blocks_for(nkeysets * n_signers, 64)), dim3(64), 0, st, d, K->X, K->gw);
+    d.S = n_signers; d.n = n; d.K = nkeysets; d.nsets = n_sets; d.sets = K->d_sets; d.lparty = -1;
+    hipLaunchKernelGGL(mpe::gg::gw_kernel, dim3(mpe::blocks_for((int)ngw, 64)), dim3(64), 0, st, d, K->X, K->gw);
   }
   int rc = mpe_paillier_create_public(ctx, nkeysets * n, d_N, &K->pub, stream);
   if (rc == MPE_OK) rc = mpe_paillier_create_private(ctx, nkeysets * n_own, d_p, d_q, &K->prv, stream);
@@ -1372,20 +1471,23 @@ int mpe_gg20_msg_words(int n_signers, int n, int round) { return mpe::gg::msg_wo
 
 int mpe_gg20_session_create(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, int n_local, const int32_t* h_local,
                             const int32_t* d_keyset, const mpe_gg20_nonces* nonces, int dedup_verify, mpe_gg20_session** out, void* stream) {
+  return mpe_gg20_session_create_sets(ctx, keys, batch, n_local, h_local, d_keyset, nullptr, 0, nonces, dedup_verify, out, stream);
+}
+int mpe_gg20_session_create_sets(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, int n_local, const int32_t* h_local, const int32_t* d_keyset,
+                                 const int32_t* d_sigset, int local_by_party, const mpe_gg20_nonces* nonces, int dedup_verify,
+                                 mpe_gg20_session** out, void* stream) {
   if (!ctx || !keys || !nonces || !out || batch <= 0 || n_local < 1 || n_local > keys->S || !h_local) return MPE_E_ARG;
-  for (int i = 0; i < n_local; ++i) {
-    if (h_local[i] < 0 || h_local[i] >= keys->S || (i && h_local[i] <= h_local[i - 1])) return MPE_E_ARG;
-    if (keys->own_slot[keys->signers[h_local[i]]] < 0) { mpe_set_error_msg("gg20: a local party's secrets are not in the key object"); return MPE_E_ARG; }
-  }
+  mpe::gg::Dim d0{};
+  mpe::gg::dim_of_keys(d0, keys, d_keyset, d_sigset);
+  MPE_TRY(mpe::gg::local_parties(d0, keys, n_local, h_local, d_sigset, local_by_party));
   if (keys->K > 1 && !d_keyset) return MPE_E_ARG;
   hipStream_t st = (hipStream_t)stream;
   mpe_gg20_session* s = new (std::nothrow) mpe_gg20_session();
   if (!s) return MPE_E_NOMEM;
-  s->ctx = ctx; s->K = keys; s->B = batch; s->L = n_local; s->dedup = dedup_verify ? 1 : 0; s->Z = *nonces;
+  s->ctx = ctx; s->K = keys; s->B = batch; s->L = n_local; s->dedup = dedup_verify ? 1 : 0; s->Z = *nonces; s->any_set = d_sigset != nullptr;
   mpe::gg::Dim& d = s->d;
-  d.B = batch; d.S = keys->S; d.n = keys->n; d.L = n_local; d.V = dedup_verify ? 1 : 2; d.PV = dedup_verify ? 1 : n_local; d.K = keys->K;
-  d.n_own = keys->n_own; d.ks = d_keyset; d.enc = ctx->enc;
-  for (int i = 0; i < 8; ++i) { d.loc[i] = i < n_local ? h_local[i] : 0; d.sg[i] = keys->signers[i]; d.oslot[i] = keys->own_slot[i] < 0 ? 0 : keys->own_slot[i]; }
+  d = d0;
+  d.B = batch; d.V = dedup_verify ? 1 : 2; d.PV = dedup_verify ? 1 : n_local; d.enc = ctx->enc;
   const size_t bytes = mpe::gg::layout(s, nullptr);
   if (!ctx->sess_in_use) {
     if (bytes > ctx->sess_bytes) {
@@ -1417,10 +1519,15 @@ int mpe_gg20_session_destroy(mpe_gg20_session* s, void* stream) {
 }
 
 int mpe_gg20_session_rearm(mpe_gg20_session* s, const int32_t* d_keyset, const mpe_gg20_nonces* nonces, void* stream) {
+  return mpe_gg20_session_rearm_sets(s, d_keyset, nullptr, nonces, stream);
+}
+// (a session made without d_sigset checked its local parties' secrets against set 0 alone: it re-arms without one; null here means set 0 again)
+int mpe_gg20_session_rearm_sets(mpe_gg20_session* s, const int32_t* d_keyset, const int32_t* d_sigset, const mpe_gg20_nonces* nonces, void* stream) {
   // a long-lived party process signs batch after batch with the same (keys, batch, local parties) shape: the state arrays and
   // the index tables stay, everything nonce-derived is zeroed and the round counter starts again
   if (!s || !nonces) return MPE_E_ARG;
   if (s->K->K > 1 && !d_keyset) return MPE_E_ARG;
+  if (d_sigset && !s->any_set) { mpe_set_error_msg("gg20 session rearm: the session was created without per-session signer sets"); return MPE_E_ARG; }
   // a batch that is half-way through the protocol is not silently thrown away: finish it (round 8 = complete) or destroy it
   // — unless a round call FAILED (MPE_E_NOMEM, a HIP error: the batch cannot go on) or the caller abandoned it (mpe_gg20_session_abort)
   if (s->next_round != 0 && s->next_round <= 8 && !s->failed) { mpe_set_error_msg("gg20 session rearm: the previous batch has not completed (finish it, or mpe_gg20_session_abort)"); return MPE_E_ARG; }
@@ -1429,7 +1536,7 @@ int mpe_gg20_session_rearm(mpe_gg20_session* s, const int32_t* d_keyset, const m
   hipStream_t st = (hipStream_t)stream;
   const hipError_t em = mpe::gg::wipe_batch_state(s, st);
   if (em != hipSuccess) { mpe_set_error("gg20 session rearm (wipe)", em); return MPE_E_HIP; }
-  s->Z = *nonces; s->d.ks = d_keyset; s->next_round = 0; s->failed = false; s->fault_step = 0; s->fault_mask = 0;
+  s->Z = *nonces; s->d.ks = d_keyset; s->d.ss = d_sigset; s->next_round = 0; s->failed = false; s->fault_step = 0; s->fault_mask = 0;
   mpe::gg::launch_idx(s, st);           // the key indices follow the (possibly different) key-set choice
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) { mpe_set_error("gg20 session rearm", e); return MPE_E_HIP; }
@@ -1500,9 +1607,15 @@ int mpe_gg20_session_result(const mpe_gg20_session* s, int32_t* d_status, uint32
 
 int mpe_gg20_sign(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, const int32_t* d_keyset, const mpe_gg20_nonces* nonces, uint32_t* d_r,
                   uint32_t* d_s, int32_t* d_recid, uint32_t* d_R, int32_t* d_status, int dedup_verify, int chunk, void* stream) {
+  return mpe_gg20_sign_sets(ctx, keys, batch, d_keyset, nullptr, nonces, d_r, d_s, d_recid, d_R, d_status, dedup_verify, chunk, stream);
+}
+int mpe_gg20_sign_sets(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, const int32_t* d_keyset, const int32_t* d_sigset, const mpe_gg20_nonces* nonces,
+                       uint32_t* d_r, uint32_t* d_s, int32_t* d_recid, uint32_t* d_R, int32_t* d_status, int dedup_verify, int chunk, void* stream) {
   if (!ctx || !keys || !nonces || !d_r || !d_s || !d_recid || !d_status || batch < 0) return MPE_E_ARG;
   const int S = keys->S, n = keys->n;
-  for (int i = 0; i < S; ++i) if (keys->own_slot[keys->signers[i]] < 0) { mpe_set_error_msg("mpe_gg20_sign needs every signer's secrets"); return MPE_E_ARG; }
+  for (int k = 0; k < (d_sigset ? keys->nsets : 1); ++k)
+    for (int i = 0; i < S; ++i)
+      if (keys->own_slot[(keys->sets4[k] >> (4 * i)) & 15u] < 0) { mpe_set_error_msg("mpe_gg20_sign needs every signer's secrets"); return MPE_E_ARG; }
   hipStream_t st = (hipStream_t)stream;
   int maxw = 0;                                     // the widest message record
   for (int r = 0; r < 8; ++r) { const int w = mpe::gg::msg_words(S, n, r); if (w > maxw) maxw = w; }
@@ -1551,7 +1664,7 @@ int mpe_gg20_sign(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, const int3
     Z.pdl_alpha += oPP * 24; Z.pdl_beta += oPP * 64; Z.pdl_rho += oPP * 72; Z.pdl_gamma += oPP * 88;
     Z.heg_s1 += oPI * 8; Z.heg_s2 += oPI * 8; Z.msg += (size_t)b0 * 8;
     mpe_gg20_session* s = nullptr;
-    int rc = mpe_gg20_session_create(ctx, keys, B, S, local, d_keyset ? d_keyset + b0 : nullptr, &Z, dedup_verify, &s, stream);
+    int rc = mpe_gg20_session_create_sets(ctx, keys, B, S, local, d_keyset ? d_keyset + b0 : nullptr, d_sigset ? d_sigset + b0 : nullptr, 0, &Z, dedup_verify, &s, stream);
     if (rc != MPE_OK) return rc;
     s->ahead.lockstep = true;                       // the message slabs never leave the library between two rounds
     rc = mpe::gg::round0(s, M[0], st);

@@ -1,7 +1,7 @@
 // The presignature pool: GG20's offline / online split as a device object.  `CompletedOfflineStage`
 // (gg_2020/state_machine/sign/rounds.rs:647-661) is a value in the reference — it leaves `OfflineStage::pick_output` and enters
 // `SignManual::new` whenever the message arrives; here one pool SLOT holds that value for the pool's L local parties:
-//   per party  k_i [8], sigma_i [8], R [16]          per slot  the key-set index and one 32-bit STATE word
+//   per party  k_i [8], sigma_i [8], R [16]          per slot  the key-set index, the signer-set index and one 32-bit STATE word
 // in structure-of-arrays form, [capacity][L][w] per field.  After `sign` the slot also keeps m [8] and, per party, r [8] and the own
 // s_i [8] for the completion.  The pool's memory is its own allocation, zeroed before it is freed.
 //
@@ -30,12 +30,14 @@ constexpr int REC_PARTY = 32;              // k_i [8] | sigma_i [8] | R [16]
 struct View {
   uint32_t* state;                         // [cap]
   int32_t* keyset;                         // [cap]
+  int32_t* sigset;                         // [cap] the signer set (of the key object) the slot's session signed with
   uint32_t *k, *sigma, *R;                 // [cap][L][8], [cap][L][8], [cap][L][16]
   uint32_t *m, *r, *s_own;                 // [cap][8], [cap][L][8], [cap][L][8]: written by sign, read by complete
   int cap, L, S, K;
   int loc[8];                              // local slot -> signer ordinal
   uint32_t loc4;                           // the same, four bits each: a row's loop over the parties reads it without indexing loc[]
-  uint32_t mask;                           // the signer set as a bit mask over party indices
+  const uint32_t* masks;                   // [nsets] the key object's signer sets as bit masks over party indices (a record's mask word)
+  int nsets;
 };
 
 // the claim: true for the one row that moves the slot from `from` to BUSY
@@ -57,14 +59,14 @@ __device__ __forceinline__ void wipe_slot(const View& P, int slot) {
   const size_t pl = (size_t)slot * P.L;
   zero_words(P.k + pl * 8, 8 * P.L); zero_words(P.sigma + pl * 8, 8 * P.L); zero_words(P.R + pl * 16, 16 * P.L);
   zero_words(P.m + (size_t)slot * 8, 8); zero_words(P.r + pl * 8, 8 * P.L); zero_words(P.s_own + pl * 8, 8 * P.L);
-  P.keyset[slot] = 0;
+  P.keyset[slot] = 0; P.sigset[slot] = 0;
 }
 
 // deposit: row b of a session behind round 6 -> slot d_slot[b].  kq, sigma_i, R: the session's [B][L] arrays.
 __global__ void __launch_bounds__(64) presig_deposit_kernel(View P, int B, const int32_t* __restrict__ d_slot, const uint32_t* __restrict__ kq,
                                                             const uint32_t* __restrict__ sigma_i, const uint32_t* __restrict__ R,
                                                             const int32_t* __restrict__ sess_status, const int32_t* __restrict__ ks,
-                                                            int32_t* __restrict__ status) {
+                                                            const int32_t* __restrict__ ss, int32_t* __restrict__ status) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   bool healthy = true;
@@ -80,6 +82,7 @@ __global__ void __launch_bounds__(64) presig_deposit_kernel(View P, int B, const
     copy_words(P.sigma + pl * 8, sigma_i + pi * 8, 8 * P.L);
     copy_words(P.R + pl * 16, R + pi * 16, 16 * P.L);
     P.keyset[slot] = ks ? ks[b] : 0;
+    P.sigset[slot] = ss ? ss[b] : 0;         // (a healthy session's index is one of the key object's: r0_kernel)
     settle(P.state + slot, READY);
   }
   if (status) status[b] = code;
@@ -153,7 +156,7 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC presig_complete_kernel(View P, 
   if (code == 0) {         // what a SIGNED slot still holds (sign zeroed k_i and sigma_i)
     const size_t pl = (size_t)slot * P.L;
     zero_words(P.R + pl * 16, 16 * P.L); zero_words(P.m + (size_t)slot * 8, 8); zero_words(P.r + pl * 8, 8 * P.L); zero_words(P.s_own + pl * 8, 8 * P.L);
-    P.keyset[slot] = 0;
+    P.keyset[slot] = 0; P.sigset[slot] = 0;
     settle(P.state + slot, EMPTY);
   }
 }
@@ -170,7 +173,7 @@ __global__ void __launch_bounds__(64) presig_export_kernel(View P, int count, co
   else if (!claim(P.state + slot, READY)) code = MPE_GG20_PRESIG_EXPORT_NOT_READY;
   if (code == 0) {
     const int kk = P.keyset[slot];
-    o[0] = REC_VERSION; o[1] = P.mask; o[2] = (uint32_t)P.L;
+    o[0] = REC_VERSION; o[1] = P.masks[P.sigset[slot]]; o[2] = (uint32_t)P.L;
     for (int j = 0; j < 8; ++j) o[3 + j] = j < P.L ? (uint32_t)P.loc[j] : 0u;
     o[11] = (uint32_t)kk;
     copy_words(o + 12, y + (size_t)kk * 16, 16);
@@ -187,7 +190,7 @@ __global__ void __launch_bounds__(64) presig_export_kernel(View P, int count, co
   if (status) status[g] = code;
 }
 
-// import: EMPTY -> READY for a record that is this pool's (version, signer set, local parties), names one of its key sets with that key
+// import: EMPTY -> READY for a record that is this pool's (version, one of the key object's signer sets, local parties), names one of its key sets with that key
 // set's y, and holds values a healthy offline stage leaves: every R on the curve, 0 < k_i < q, sigma_i < q.  The record is judged before
 // the slot is claimed: a refused record leaves the slot as it was.
 __global__ void __launch_bounds__(64) presig_import_kernel(View P, int count, const int32_t* __restrict__ d_slot, const uint32_t* __restrict__ y,
@@ -196,10 +199,13 @@ __global__ void __launch_bounds__(64) presig_import_kernel(View P, int count, co
   if (g >= count) return;
   const int slot = d_slot[g], W = REC_HEAD + REC_PARTY * P.L;
   const uint32_t* o = rec + (size_t)g * W;
-  int code = 0;
+  int code = 0, sigset = 0;
   if (slot < 0 || slot >= P.cap) code = MPE_GG20_PRESIG_RECORD_RANGE;
   else {
-    bool ok = o[0] == REC_VERSION && o[1] == P.mask && o[2] == (uint32_t)P.L && o[11] < (uint32_t)P.K;
+    int set = -1;
+    for (int k = 0; k < P.nsets; ++k) if (P.masks[k] == o[1]) set = k;
+    bool ok = o[0] == REC_VERSION && set >= 0 && o[2] == (uint32_t)P.L && o[11] < (uint32_t)P.K;
+    sigset = set < 0 ? 0 : set;
     for (int j = 0; j < 8; ++j) ok = ok && o[3 + j] == (j < P.L ? (uint32_t)P.loc[j] : 0u);
     if (ok) ok = gg::words_eq(o + 12, y + (size_t)o[11] * 16, 16);
 #pragma unroll 1
@@ -216,7 +222,7 @@ __global__ void __launch_bounds__(64) presig_import_kernel(View P, int count, co
       const uint32_t* p = o + REC_HEAD + REC_PARTY * li;
       copy_words(P.k + pl * 8, p, 8); copy_words(P.sigma + pl * 8, p + 8, 8); copy_words(P.R + pl * 16, p + 16, 16);
     }
-    P.keyset[slot] = (int32_t)o[11];
+    P.keyset[slot] = (int32_t)o[11]; P.sigset[slot] = sigset;
     settle(P.state + slot, READY);
   }
   if (status) status[g] = code;
@@ -265,7 +271,7 @@ namespace psg {
 static size_t layout(View& v, char* base) {
   gg::Bump m(base);
   const size_t cap = (size_t)v.cap, pl = cap * v.L;
-  v.state = m.w(cap); v.keyset = m.i(cap);
+  v.state = m.w(cap); v.keyset = m.i(cap); v.sigset = m.i(cap);
   v.k = m.w(pl * 8); v.sigma = m.w(pl * 8); v.R = m.w(pl * 16);
   v.m = m.w(cap * 8); v.r = m.w(pl * 8); v.s_own = m.w(pl * 8);
   return m.off;
@@ -299,10 +305,9 @@ int mpe_gg20_presig_pool_create(mpe_ctx* ctx, const mpe_gg20_keys* keys, int n_l
   if (!p) return MPE_E_NOMEM;
   p->ctx = ctx; p->K = keys;
   mpe::psg::View& v = p->v;
-  v.cap = capacity; v.L = n_local; v.S = keys->S; v.K = keys->K; v.mask = 0;
+  v.cap = capacity; v.L = n_local; v.S = keys->S; v.K = keys->K; v.masks = keys->d_sets + keys->nsets; v.nsets = keys->nsets;
   v.loc4 = 0;
   for (int i = 0; i < 8; ++i) { v.loc[i] = i < n_local ? h_local[i] : 0; v.loc4 |= (uint32_t)v.loc[i] << (4 * i); }
-  for (int i = 0; i < keys->S; ++i) v.mask |= 1u << keys->signers[i];
   p->mem_bytes = mpe::psg::layout(v, nullptr);
   hipError_t e = hipMalloc(&p->mem, p->mem_bytes);
   if (e != hipSuccess) { delete p; mpe_set_error("hipMalloc(presignature pool)", e); return MPE_E_NOMEM; }
@@ -329,12 +334,12 @@ int mpe_gg20_presig_record_words(const mpe_gg20_presig_pool* p) { return p ? mpe
 int mpe_gg20_presig_deposit(mpe_gg20_presig_pool* p, mpe_gg20_session* s, const int32_t* d_slot, int32_t* d_status, void* stream) {
   if (!p || !s || !d_slot) return MPE_E_ARG;
   if (s->failed || s->next_round != 7) { mpe_set_error_msg("presig deposit: the session is not behind round 6"); return MPE_E_ARG; }
-  bool same = s->K == p->K && s->ctx == p->ctx && s->L == p->v.L;
+  bool same = s->K == p->K && s->ctx == p->ctx && s->L == p->v.L && s->d.lparty < 0;      // (the pool's local parties are ordinals)
   for (int i = 0; same && i < s->L; ++i) same = s->d.loc[i] == p->v.loc[i];
   if (!same) { mpe_set_error_msg("presig deposit: the session's keys or local parties are not the pool's"); return MPE_E_ARG; }
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(mpe::psg::presig_deposit_kernel, dim3(mpe::blocks_for(s->B, 64)), dim3(64), 0, st, p->v, s->B, d_slot, s->kq, s->sigma_i,
-                     s->R, s->status, s->d.ks, d_status);
+                     s->R, s->status, s->d.ks, s->d.ss, d_status);
   int rc = mpe::psg::launched("presig_deposit_kernel");
   // deposited or not, the session's copy goes, as mpe_gg20_session_abort wipes it: the only live k_i is the pool's
   const hipError_t em = mpe::psg::wipe_session_after_deposit(s, st);

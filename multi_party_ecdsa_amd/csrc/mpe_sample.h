@@ -150,11 +150,13 @@ __device__ __forceinline__ void draw_item(Stream& s, const uint32_t* __restrict_
 }
 
 // row -> stream item of the GG20 arrays (L = 0: the row index itself): rows are [session][local party][per_owner sub-items]
-struct ItemMap { int L, S; unsigned per_owner; uint32_t loc_packed; };       // loc_packed: signer ordinal of local party li in bits [4 li, 4 li + 4)
+struct ItemMap { int L, S; unsigned per_owner; uint32_t loc_packed; const int32_t* ord = nullptr; };       // loc_packed: signer ordinal of local party li in bits [4 li, 4 li + 4)
+// ord: [sessions] the ordinal of the ONE local party that was named by its party index (per-session signer sets), or null
 __device__ __forceinline__ uint32_t stream_item(const ItemMap& m, unsigned row) {
   if (m.L == 0) return row;
   const unsigned pil = row / m.per_owner, sub = row % m.per_owner, b = pil / (unsigned)m.L, li = pil % (unsigned)m.L;
-  return (b * (unsigned)m.S + ((m.loc_packed >> (4 * li)) & 15u)) * m.per_owner + sub;
+  const unsigned i = m.ord ? (unsigned)m.ord[b] : ((m.loc_packed >> (4 * li)) & 15u);
+  return (b * (unsigned)m.S + i) * m.per_owner + sub;
 }
 // out[i] (out_words words, zero-extended) drawn below bound row sel(i); bits > 0: BigInt::sample(bits), no bound.
 template <int COPRIME_W>
@@ -176,7 +178,7 @@ __global__ void __launch_bounds__(64) sample_kernel(int batch, Seed key, uint32_
 // counter | f << 56, item = the row index inside the batch.  One slot = mpe_gg20_sample_nonces; several = the pipelined engine's groups.
 constexpr int MAX_SLOTS = 16;
 struct FieldDesc { uint32_t* out; const uint32_t* bound; const int32_t* idx; unsigned per_slot, per_owner; int bound_words, out_words, bits, flags, field; };
-struct FieldTable { FieldDesc f[NF]; unsigned start[NF + 1]; int n; int max_attempts; int32_t* owner_bad; int L, S; uint32_t loc_packed; };    // owner_bad [session-parties]: a draw of theirs gave up
+struct FieldTable { FieldDesc f[NF]; unsigned start[NF + 1]; int n; int max_attempts; int32_t* owner_bad; int L, S; uint32_t loc_packed; const int32_t* ord; };    // owner_bad [session-parties]: a draw of theirs gave up
 struct SlotTable { Seed key[MAX_SLOTS]; uint32_t ctr_lo[MAX_SLOTS], ctr_hi[MAX_SLOTS]; };
 __global__ void __launch_bounds__(64) sample_fields_kernel(FieldTable t, SlotTable sl, int32_t* __restrict__ fail) {
   __shared__ uint32_t ks[64][17];
@@ -189,7 +191,7 @@ __global__ void __launch_bounds__(64) sample_fields_kernel(FieldTable t, SlotTab
   while (g >= t.start[f + 1]) ++f;
   const FieldDesc& d = t.f[f];
   const unsigned row = g - t.start[f], slot = row / d.per_slot, i = row % d.per_slot;
-  const ItemMap map{t.L, t.S, d.per_owner, t.loc_packed};
+  const ItemMap map{t.L, t.S, d.per_owner, t.loc_packed, t.ord ? t.ord + (size_t)slot * (d.per_slot / d.per_owner / (unsigned)t.L) : nullptr};
   Stream s{&slots.key[slot], stream_item(map, i), slots.ctr_lo[slot], slots.ctr_hi[slot] | ((uint32_t)d.field << 24), ks[threadIdx.x], 0xffffffffu, 0ull};
   const uint32_t* bd = d.bound ? d.bound + (size_t)(d.idx ? d.idx[row] : 0) * d.bound_words : nullptr;
   draw_item<0>(s, bd, d.bound_words, d.bits, d.flags, d.out + (size_t)row * d.out_words, d.out_words, t.max_attempts, fail,
@@ -229,17 +231,19 @@ static int launch_sample(int batch, const uint8_t* h_seed, uint64_t sid, int bit
 }
 
 // which bound row every item of a nonce field uses (same index conventions as mpe_gg20.h)
-struct SIdx { int32_t *own_pi, *own_ap, *st_ap, *peer_mb, *own_pp, *st_pp; };
+// ord [B]: with a local party named by its index (d.lparty >= 0), its ordinal in every session (what stream_item needs), else null
+struct SIdx { int32_t *own_pi, *own_ap, *st_ap, *peer_mb, *own_pp, *st_pp, *ord; };
 __global__ void sidx_kernel(gg::Dim d, SIdx x, int total) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= total) return;
   const int n = d.n, L = d.L, P1 = d.S - 1;
-  if (g < d.B * L) x.own_pi[g] = gg::kpub(d, g / L, d.loc[g % L]);
-  if (g < d.B * L * n) { const int pi = g / n; x.own_ap[g] = gg::kpub(d, pi / L, d.loc[pi % L]); x.st_ap[g] = gg::ks_of(d, pi / L) * n + g % n; }
-  if (g < d.B * L * P1 * 2) { const int pp = g >> 1, pi = pp / P1; x.peer_mb[g] = gg::kpub(d, pi / L, gg::ind_of(d.loc[pi % L], pp % P1)); }
+  if (g < d.B && x.ord) x.ord[g] = gg::loc_of(d, g, 0);
+  if (g < d.B * L) x.own_pi[g] = gg::kpub(d, g / L, gg::loc_of(d, g / L, g % L));
+  if (g < d.B * L * n) { const int pi = g / n; x.own_ap[g] = gg::kpub(d, pi / L, gg::loc_of(d, pi / L, pi % L)); x.st_ap[g] = gg::ks_of(d, pi / L) * n + g % n; }
+  if (g < d.B * L * P1 * 2) { const int pp = g >> 1, pi = pp / P1; x.peer_mb[g] = gg::kpub(d, pi / L, gg::ind_of(gg::loc_of(d, pi / L, pi % L), pp % P1)); }
   if (g < d.B * L * P1) {
-    const int pi = g / P1, b = pi / L, i = d.loc[pi % L];
-    x.own_pp[g] = gg::kpub(d, b, i); x.st_pp[g] = gg::ks_of(d, b) * n + d.sg[gg::ind_of(i, g % P1)];
+    const int pi = g / P1, b = pi / L, i = gg::loc_of(d, b, pi % L);
+    x.own_pp[g] = gg::kpub(d, b, i); x.st_pp[g] = gg::ks_of(d, b) * n + gg::sg_of(d, b, gg::ind_of(i, g % P1));
   }
 }
 
@@ -273,24 +277,33 @@ namespace smp {
 
 // `nslots` consecutive batches of `per_batch` sessions each (arrays slot-major), slot k drawn from (h_seeds + 32 k, h_counters[k])
 static int sample_gg20(mpe_ctx* ctx, const mpe_gg20_keys* K, int per_batch, int nslots, int n_local, const int32_t* h_local, const int32_t* d_keyset,
-                       const uint8_t* h_seeds, const uint64_t* h_counters, const mpe_gg20_nonces* out, int32_t* d_fail, hipStream_t st) {
+                       const uint8_t* h_seeds, const uint64_t* h_counters, const mpe_gg20_nonces* out, int32_t* d_fail, hipStream_t st,
+                       const int32_t* d_sigset = nullptr, int local_by_party = 0) {
   if (!ctx || !K || !h_local || !h_seeds || !h_counters || !out || per_batch < 0 || nslots < 1 || nslots > MAX_SLOTS || n_local < 1 || n_local > K->S) return MPE_E_ARG;
   for (int k = 0; k < nslots; ++k) if ((h_counters[k] >> 56) != 0) return MPE_E_ARG;
   if (K->K > 1 && !d_keyset) return MPE_E_ARG;
   if (per_batch == 0) return MPE_OK;
   const int batch = per_batch * nslots;
   gg::Dim d{};
-  d.B = batch; d.S = K->S; d.n = K->n; d.L = n_local; d.K = K->K; d.n_own = K->n_own; d.ks = d_keyset;
-  for (int i = 0; i < 8; ++i) { d.loc[i] = i < n_local ? h_local[i] : 0; d.sg[i] = K->signers[i]; d.oslot[i] = K->own_slot[i] < 0 ? 0 : K->own_slot[i]; }
-  for (int i = 0; i < n_local; ++i) if (h_local[i] < 0 || h_local[i] >= K->S || (i && h_local[i] <= h_local[i - 1])) return MPE_E_ARG;
+  // (the bounds are public values of every party: the sampler does not ask whose secrets the key object holds)
+  gg::dim_of_keys(d, K, d_keyset, d_sigset);
+  d.B = batch; d.L = n_local;
+  if (local_by_party) {
+    if (n_local != 1 || h_local[0] < 0 || h_local[0] >= K->n) return MPE_E_ARG;
+    d.lparty = h_local[0];
+  } else {
+    for (int i = 0; i < n_local; ++i) if (h_local[i] < 0 || h_local[i] >= K->S || (i && h_local[i] <= h_local[i - 1])) return MPE_E_ARG;
+    for (int i = 0; i < 8; ++i) d.loc[i] = i < n_local ? h_local[i] : 0;
+  }
   const size_t P1 = (size_t)K->S - 1, nPI = (size_t)batch * n_local, nAP = nPI * K->n, nPP = nPI * P1, nMB = nPP * 2;
   // workspace: the bound-row index of every item + the batched coprimality verdict of from_modulo
   const mpe_modset* msn = K->pub->ms_n;
-  const size_t idx_words = 2 * nPI + 2 * nAP + nMB + 2 * nPP + 64;
+  const size_t idx_words = 2 * nPI + 2 * nAP + nMB + 2 * nPP + (size_t)batch + 128;
   const size_t inv_bytes = (modinv_ws_words(msn, (int)nAP) + nAP * 64) * 4 + nAP + 4096;
   MPE_TRY(ws_reserve(ctx, idx_words * 4 + inv_bytes + 16 * 256, st));
   SIdx x{ws_array<int32_t>(ctx, nPI), ws_array<int32_t>(ctx, nAP), ws_array<int32_t>(ctx, nAP), ws_array<int32_t>(ctx, nMB), ws_array<int32_t>(ctx, nPP),
-         ws_array<int32_t>(ctx, nPP)};
+         ws_array<int32_t>(ctx, nPP), nullptr};
+  if (local_by_party) { x.ord = ws_array<int32_t>(ctx, (size_t)batch); if (!x.ord) return MPE_E_NOMEM; }
   uint32_t* inv = ws_array<uint32_t>(ctx, nAP * 64);
   uint8_t* ok = ws_array<uint8_t>(ctx, nAP);
   int32_t* owner_bad = ws_array<int32_t>(ctx, nPI);           // a draw of this (session, party) gave up
@@ -298,6 +311,7 @@ static int sample_gg20(mpe_ctx* ctx, const mpe_gg20_keys* K, int per_batch, int 
   (void)hipMemsetAsync(owner_bad, 0, nPI * 4, st);
   size_t total = nMB > nAP ? nMB : nAP;
   if (total < nPI) total = nPI;
+  if (total < (size_t)batch) total = (size_t)batch;
   hipLaunchKernelGGL(sidx_kernel, dim3(blocks_for((int)total, 64)), dim3(64), 0, st, d, x, (int)total);
   const Bounds& b = K->bounds;
   const int nk = K->K * K->n;
@@ -306,8 +320,8 @@ static int sample_gg20(mpe_ctx* ctx, const mpe_gg20_keys* K, int per_batch, int 
   // field ids = the position in mpe_gg20_nonces (include/mpecdsa_hip.h); all fields in ONE launch
   FieldTable t{};
   t.n = 0; t.start[0] = 0; t.max_attempts = ctx->sampler_max_attempts; t.owner_bad = owner_bad;
-  t.L = n_local; t.S = K->S; t.loc_packed = 0;
-  for (int i = 0; i < n_local; ++i) t.loc_packed |= (uint32_t)h_local[i] << (4 * i);
+  t.L = n_local; t.S = K->S; t.loc_packed = 0; t.ord = x.ord;
+  for (int i = 0; i < n_local && !local_by_party; ++i) t.loc_packed |= (uint32_t)h_local[i] << (4 * i);
   auto add = [&](int f, const uint32_t* dst, size_t items, const uint32_t* bound, int bw, const int32_t* idx, int ow, int flags, int bits = 0) {
     t.f[t.n] = FieldDesc{U(dst), bound, idx, (unsigned)(items / nslots), (unsigned)(items / nPI), bw, ow, bits, flags, f};
     t.start[t.n + 1] = t.start[t.n] + (unsigned)items;
@@ -346,7 +360,7 @@ static int sample_gg20(mpe_ctx* ctx, const mpe_gg20_keys* K, int per_batch, int 
     for (int k = 0; k < nslots; ++k)
       MPE_TRY(launch_sample((int)per, h_seeds + 32 * k, h_counters[k] | ((uint64_t)5 << 56), 0, N, 64, x.own_ap + k * per, nk, F_COPRIME, 64,
                             U(out->al_beta) + k * per * 64, d_fail, st, ok + k * per, ctx->sampler_max_attempts, owner_bad + k * (per / K->n),
-                            ItemMap{n_local, K->S, (unsigned)K->n, t.loc_packed}));
+                            ItemMap{n_local, K->S, (unsigned)K->n, t.loc_packed, x.ord ? x.ord + (size_t)k * per_batch : nullptr}));
   }
   hipLaunchKernelGGL(poison_kernel, dim3(blocks_for((int)nPI * 8, 256)), dim3(256), 0, st, (int)nPI, owner_bad, U(out->k));
   // the verdict array and the discarded inverses are derived from secret values
@@ -414,6 +428,12 @@ int mpe_gg20_nonces_free(mpe_gg20_nonce_buf* nb) {
 int mpe_gg20_sample_nonces(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, int n_local, const int32_t* h_local, const int32_t* d_keyset,
                            const uint8_t* h_seed32, uint64_t batch_counter, const mpe_gg20_nonces* out, int32_t* d_fail, void* stream) {
   return mpe::smp::sample_gg20(ctx, keys, batch, 1, n_local, h_local, d_keyset, h_seed32, &batch_counter, out, d_fail, (hipStream_t)stream);
+}
+int mpe_gg20_sample_nonces_sets(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, int n_local, const int32_t* h_local, const int32_t* d_keyset,
+                                const int32_t* d_sigset, int local_by_party, const uint8_t* h_seed32, uint64_t batch_counter,
+                                const mpe_gg20_nonces* out, int32_t* d_fail, void* stream) {
+  return mpe::smp::sample_gg20(ctx, keys, batch, 1, n_local, h_local, d_keyset, h_seed32, &batch_counter, out, d_fail, (hipStream_t)stream, d_sigset,
+                               local_by_party);
 }
 
 }  // extern "C"

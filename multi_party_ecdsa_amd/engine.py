@@ -459,9 +459,17 @@ class Gg20Keys:
     """`LocalKey` material (keygen/rounds.rs:311-322) + the signer set, resident in HBM.
     arrays: dict of numpy uint32 arrays for ALL n parties of every key set: x [K*n,8], p, q [K*n,32], Nt, h1, h2 [K*n,64],
     y [K,16], X [K*n,16] (and optionally N [K*n,64], else p*q).  own: the party indices whose SECRETS (x, p, q) this
-    object gets (default: all — the Simulation harness); the other parties' rows of x, p, q never leave the host."""
+    object gets (default: all — the Simulation harness); the other parties' rows of x, p, q never leave the host.
+    signer_sets=[[...], ...] (instead of `signers`): one object that signs for several quorums of the wallet
+    (mpe_gg20_keys_create_sets); a session names its set by its index in this list (`sigset=`), set 0 where none is named."""
 
-    def __init__(self, ctx, t, n, signers, arrays, own=None, nkeysets=1):
+    def __init__(self, ctx, t, n, signers, arrays, own=None, nkeysets=1, signer_sets=None):
+        if signer_sets is None:
+            signer_sets = [list(signers)]
+        elif signers is not None and [int(x) for x in signers] != [int(x) for x in signer_sets[0]]:
+            raise ValueError("Gg20Keys: `signers` is set 0 of `signer_sets`")
+        self.signer_sets = [[int(x) for x in s] for s in signer_sets]
+        signers = self.signer_sets[0]
         self.ctx, self.t, self.n, self.S, self.K = ctx, t, n, len(signers), nkeysets
         own = list(range(n)) if own is None else sorted(int(a) for a in own)
         self.own = own
@@ -476,12 +484,20 @@ class Gg20Keys:
         for f in ("x", "p", "q"):
             h[f] = np.ascontiguousarray(a[f][rows])
         self.d = {f: torch.from_numpy(h[f].view(np.int32)).to(ctx.device) for f in h}
-        sg = (C.c_int32 * len(signers))(*[int(s) for s in signers])
         ow = (C.c_int32 * len(own))(*own)
         hd = C.c_void_p()
-        N_.check(N_.lib.mpe_gg20_keys_create(ctx.h, t, n, len(signers), sg, nkeysets, len(own), ow, *[_ptr(self.d[f]) for f in
-                                             ("x", "p", "q", "N", "Nt", "h1", "h2", "y", "X")], C.byref(hd), ctx.stream()),
-                 "mpe_gg20_keys_create")
+        dev = [_ptr(self.d[f]) for f in ("x", "p", "q", "N", "Nt", "h1", "h2", "y", "X")]
+        if len(self.signer_sets) == 1:
+            sg = (C.c_int32 * len(signers))(*signers)
+            N_.check(N_.lib.mpe_gg20_keys_create(ctx.h, t, n, len(signers), sg, nkeysets, len(own), ow, *dev, C.byref(hd), ctx.stream()),
+                     "mpe_gg20_keys_create")
+        else:
+            flat = [x for s in self.signer_sets for x in s]      # (the library checks the rows: its refusals are part of its contract)
+            sg = (C.c_int32 * len(flat))(*flat)
+            if len(flat) != len(self.signer_sets) * self.S:
+                raise ValueError("every signer set of a key object has the same number of signers")
+            N_.check(N_.lib.mpe_gg20_keys_create_sets(ctx.h, t, n, self.S, len(self.signer_sets), sg, nkeysets, len(own), ow, *dev, C.byref(hd),
+                                                      ctx.stream()), "mpe_gg20_keys_create_sets")
         self.h = hd
 
     def fb_window_bits(self):
@@ -501,11 +517,18 @@ class Gg20Keys:
 
 class Gg20Session:
     """`RoundN::proceed` for B sessions x the local parties `local` (signer ordinals).  nonces: dict of device int32
-    tensors with leading dimensions [B][len(local)] (fields _native.GG20_NONCE_FIELDS; `msg` optional)."""
+    tensors with leading dimensions [B][len(local)] (fields _native.GG20_NONCE_FIELDS; `msg` optional).
+    sigset: device int32 [B], the signer set (index into keys.signer_sets) of every session; ordinals are then positions in each
+    session's own set.  local_party=p (instead of `local`): the one local party by its party INDEX, its ordinal in a session is its
+    rank in that session's set (mpe_gg20_session_create_sets)."""
 
-    def __init__(self, ctx, keys, B, local, nonces, keyset=None, dedup_verify=False):
+    def __init__(self, ctx, keys, B, local, nonces, keyset=None, dedup_verify=False, sigset=None, local_party=None):
+        by_party = local_party is not None
+        if by_party:
+            local = [int(local_party)] if local is None else list(local)
         self.ctx, self.keys, self.B, self.local = ctx, keys, B, [int(x) for x in local]
         self.S, self.n, self.L = keys.S, keys.n, len(local)
+        self._sigset = sigset
         self._nonces = dict(nonces)
         if "msg" not in self._nonces:
             self._nonces["msg"] = torch.zeros((B, 8), dtype=torch.int32, device=ctx.device)
@@ -513,21 +536,29 @@ class Gg20Session:
         nn = _struct(N_.Gg20Nonces, self._nonces)
         lc = (C.c_int32 * self.L)(*self.local)
         h = C.c_void_p()
-        N_.check(N_.lib.mpe_gg20_session_create(ctx.h, keys.h, B, self.L, lc, _ptr(keyset), C.byref(nn), int(bool(dedup_verify)),
-                                                C.byref(h), ctx.stream()), "mpe_gg20_session_create")
+        if sigset is None and not by_party:
+            N_.check(N_.lib.mpe_gg20_session_create(ctx.h, keys.h, B, self.L, lc, _ptr(keyset), C.byref(nn), int(bool(dedup_verify)),
+                                                    C.byref(h), ctx.stream()), "mpe_gg20_session_create")
+        else:
+            N_.check(N_.lib.mpe_gg20_session_create_sets(ctx.h, keys.h, B, self.L, lc, _ptr(keyset), _ptr(sigset), int(by_party), C.byref(nn),
+                                                         int(bool(dedup_verify)), C.byref(h), ctx.stream()), "mpe_gg20_session_create_sets")
         self.h = h
 
     def _off(self, in_off):
         return None if in_off is None else (C.c_int64 * self.S)(*[int(x) for x in in_off])
 
-    def rearm(self, nonces, keyset=None):
-        """the next batch of the same shape on this object (mpe_gg20_session_rearm): fresh sampled values, rounds from 0"""
+    def rearm(self, nonces, keyset=None, sigset=None):
+        """the next batch of the same shape on this object (mpe_gg20_session_rearm[_sets]): fresh sampled values, rounds from 0"""
         self._nonces = dict(nonces)
         if "msg" not in self._nonces:
             self._nonces["msg"] = torch.zeros((self.B, 8), dtype=torch.int32, device=self.ctx.device)
         self._keyset = keyset
         nn = _struct(N_.Gg20Nonces, self._nonces)
-        N_.check(N_.lib.mpe_gg20_session_rearm(self.h, _ptr(keyset), C.byref(nn), self.ctx.stream()), "mpe_gg20_session_rearm")
+        self._sigset = sigset
+        if sigset is None:
+            N_.check(N_.lib.mpe_gg20_session_rearm(self.h, _ptr(keyset), C.byref(nn), self.ctx.stream()), "mpe_gg20_session_rearm")
+        else:
+            N_.check(N_.lib.mpe_gg20_session_rearm_sets(self.h, _ptr(keyset), _ptr(sigset), C.byref(nn), self.ctx.stream()), "mpe_gg20_session_rearm_sets")
 
     def abort(self):
         """mpe_gg20_session_abort: give the running batch up (state wiped now); rearm() starts the next one"""
@@ -595,16 +626,21 @@ class Gg20Session:
             pass
 
 
-def gg20_sign(ctx, keys, nonces, B, dedup_verify=False, chunk=0, want_R=False, keyset=None):
+def gg20_sign(ctx, keys, nonces, B, dedup_verify=False, chunk=0, want_R=False, keyset=None, sigset=None):
     """nonces: dict of device int32 tensors (fields _native.GG20_NONCE_FIELDS, [B][S] layout).  Returns device tensors
-    r [B,8], s [B,8], recid [B], status [B] (0 = signed and verified) and optionally R [B,16]."""
+    r [B,8], s [B,8], recid [B], status [B] (0 = signed and verified) and optionally R [B,16].  sigset: device int32 [B], the signer
+    set of every session (mpe_gg20_sign_sets)."""
     r, s = _new(ctx, B, 8), _new(ctx, B, 8)
     recid = torch.empty((B,), dtype=torch.int32, device=ctx.device)
     status = torch.full((B,), -1, dtype=torch.int32, device=ctx.device)
     R = _new(ctx, B, 16) if want_R else None
     nn = _struct(N_.Gg20Nonces, nonces)
-    N_.check(N_.lib.mpe_gg20_sign(ctx.h, keys.h, B, _ptr(keyset), C.byref(nn), _ptr(r), _ptr(s), _ptr(recid), _ptr(R), _ptr(status),
-                                  int(bool(dedup_verify)), int(chunk), ctx.stream()), "mpe_gg20_sign")
+    if sigset is None:
+        N_.check(N_.lib.mpe_gg20_sign(ctx.h, keys.h, B, _ptr(keyset), C.byref(nn), _ptr(r), _ptr(s), _ptr(recid), _ptr(R), _ptr(status),
+                                      int(bool(dedup_verify)), int(chunk), ctx.stream()), "mpe_gg20_sign")
+    else:
+        N_.check(N_.lib.mpe_gg20_sign_sets(ctx.h, keys.h, B, _ptr(keyset), _ptr(sigset), C.byref(nn), _ptr(r), _ptr(s), _ptr(recid), _ptr(R),
+                                           _ptr(status), int(bool(dedup_verify)), int(chunk), ctx.stream()), "mpe_gg20_sign_sets")
     return (r, s, recid, status, R) if want_R else (r, s, recid, status)
 
 
@@ -751,10 +787,10 @@ class PresigPool:
             pass
 
 
-def gg20_presign(ctx, keys, nonces, B, pool, keyset=None, dedup_verify=False):
+def gg20_presign(ctx, keys, nonces, B, pool, keyset=None, dedup_verify=False, sigset=None):
     """The offline stage alone: rounds 0-6 of B sessions with every signer local (nonces: [B][S] layout, `msg` not needed), deposited
     into `pool` (a PresigPool over all S signers of `keys`).  Returns the usable slots [B] (numpy int32; -1 where the session failed)."""
-    sess = Gg20Session(ctx, keys, B, list(range(keys.S)), nonces, keyset=keyset, dedup_verify=dedup_verify)
+    sess = Gg20Session(ctx, keys, B, list(range(keys.S)), nonces, keyset=keyset, dedup_verify=dedup_verify, sigset=sigset)
     try:
         prev = None
         for rnd in range(7):
@@ -996,10 +1032,11 @@ def gg20_nonce_shapes(S, n, L, B):
                 pdl_rho=(B * P, 72), pdl_gamma=(B * P, 88), heg_s1=(B * L, 8), heg_s2=(B * L, 8), msg=(B, 8))
 
 
-def gg20_sample_nonces(ctx, keys, B, seed, batch_counter, local=None, keyset=None, msg=None, out=None):
+def gg20_sample_nonces(ctx, keys, B, seed, batch_counter, local=None, keyset=None, msg=None, out=None, sigset=None, local_party=None):
     """mpe_gg20_sample_nonces: every value the local parties of B sessions draw while signing, from (seed, batch_counter).
     Returns (dict of device tensors in the layout gg20_sign / Gg20Session take, failures [1]); `msg` (device [B, 8]) is passed through."""
-    local = list(range(keys.S)) if local is None else list(local)
+    by_party = local_party is not None          # (sigset / local_party: as Gg20Session takes them; mpe_gg20_sample_nonces_sets)
+    local = ([int(local_party)] if by_party else list(range(keys.S))) if local is None else list(local)
     if out is None:
         out = {f: torch.zeros(shape, dtype=torch.int32, device=ctx.device) for f, shape in gg20_nonce_shapes(keys.S, keys.n, len(local), B).items()}
     if msg is not None:
@@ -1007,8 +1044,12 @@ def gg20_sample_nonces(ctx, keys, B, seed, batch_counter, local=None, keyset=Non
     fail = torch.zeros((1,), dtype=torch.int32, device=ctx.device)
     nn = _struct(N_.Gg20Nonces, out)
     lc = (C.c_int32 * len(local))(*local)
-    N_.check(N_.lib.mpe_gg20_sample_nonces(ctx.h, keys.h, B, len(local), lc, _ptr(keyset), _seed(seed), int(batch_counter), C.byref(nn), _ptr(fail),
-                                           ctx.stream()), "mpe_gg20_sample_nonces")
+    if sigset is None and not by_party:
+        N_.check(N_.lib.mpe_gg20_sample_nonces(ctx.h, keys.h, B, len(local), lc, _ptr(keyset), _seed(seed), int(batch_counter), C.byref(nn), _ptr(fail),
+                                               ctx.stream()), "mpe_gg20_sample_nonces")
+    else:
+        N_.check(N_.lib.mpe_gg20_sample_nonces_sets(ctx.h, keys.h, B, len(local), lc, _ptr(keyset), _ptr(sigset), int(by_party), _seed(seed),
+                                                    int(batch_counter), C.byref(nn), _ptr(fail), ctx.stream()), "mpe_gg20_sample_nonces_sets")
     return out, fail
 
 
@@ -1252,18 +1293,25 @@ def gg20_keygen(ctx, t, n, B, seed, counter=0, material=None, _fault=None, safe_
 
 
 # ---- identifiable abort (gg_2020/blame.rs) ----
-def gg20_blame5(ctx, keys, B, opened, keyset=None):
-    """opened: dict of device tensors (fields _native.Blame5In) -> bad_actors bit masks [B] (device int32)"""
+def gg20_blame5(ctx, keys, B, opened, keyset=None, sigset=None):
+    """opened: dict of device tensors (fields _native.Blame5In) -> bad_actors bit masks [B] (device int32); sigset: the sessions' signer
+    sets (mpe_gg20_blame5_sets)"""
     bad = torch.empty((B,), dtype=torch.int32, device=ctx.device)
     st_ = _struct(N_.Blame5In, opened)
-    N_.check(N_.lib.mpe_gg20_blame5(ctx.h, keys.h, B, _ptr(keyset), C.byref(st_), _ptr(bad), ctx.stream()), "mpe_gg20_blame5")
+    if sigset is None:
+        N_.check(N_.lib.mpe_gg20_blame5(ctx.h, keys.h, B, _ptr(keyset), C.byref(st_), _ptr(bad), ctx.stream()), "mpe_gg20_blame5")
+    else:
+        N_.check(N_.lib.mpe_gg20_blame5_sets(ctx.h, keys.h, B, _ptr(keyset), _ptr(sigset), C.byref(st_), _ptr(bad), ctx.stream()), "mpe_gg20_blame5_sets")
     return bad
 
 
-def gg20_blame6(ctx, keys, B, opened, keyset=None):
+def gg20_blame6(ctx, keys, B, opened, keyset=None, sigset=None):
     bad = torch.empty((B,), dtype=torch.int32, device=ctx.device)
     st_ = _struct(N_.Blame6In, opened)
-    N_.check(N_.lib.mpe_gg20_blame6(ctx.h, keys.h, B, _ptr(keyset), C.byref(st_), _ptr(bad), ctx.stream()), "mpe_gg20_blame6")
+    if sigset is None:
+        N_.check(N_.lib.mpe_gg20_blame6(ctx.h, keys.h, B, _ptr(keyset), C.byref(st_), _ptr(bad), ctx.stream()), "mpe_gg20_blame6")
+    else:
+        N_.check(N_.lib.mpe_gg20_blame6_sets(ctx.h, keys.h, B, _ptr(keyset), _ptr(sigset), C.byref(st_), _ptr(bad), ctx.stream()), "mpe_gg20_blame6_sets")
     return bad
 
 
