@@ -602,6 +602,16 @@ int mpe_gg20_presig_import(mpe_gg20_presig_pool* pool, int count, const int32_t*
                            void* stream);
 int mpe_gg20_presig_discard(mpe_gg20_presig_pool* pool, int count, const int32_t* d_slot, void* stream);
 int mpe_gg20_presig_pool_audit(mpe_gg20_presig_pool* pool, int64_t* h_out, void* stream);
+/* The online step in ONE launch, for a pool that holds all S signers (n_local == S; MPE_E_ARG otherwise): sign + complete of the rows'
+ * slots without the SIGNED state in between.  A row claims its READY slot with the same single compare-and-swap, computes every
+ * s_i = m k_i + r sigma_i (k_i and sigma_i zeroed at once), sums them, normalises to low s with the recid flip, runs output_signature's
+ * verify ONCE and returns the slot to EMPTY with the wipe.  One verify is exact: with every signer in the pool the S parties of
+ * sign + complete verify the same (r, s) under the same y — the argument of dedup_verify.  (A slot whose parties do not hold one and
+ * the same R, which no offline stage leaves and only an import can make, is 701.)  d_r, d_s [count][8], d_recid, d_status [count]:
+ * what mpe_gg20_sign reports per session; 811 / 812 from the claim (among duplicate indices exactly one row wins), 701 when the
+ * verify fails; zero outputs unless status 0.  d_status may be NULL. */
+int mpe_gg20_sign_online(mpe_gg20_presig_pool* pool, int count, const int32_t* d_slot, const uint32_t* d_msg, uint32_t* d_r,
+                                uint32_t* d_s, int32_t* d_recid, int32_t* d_status, void* stream);
 
 /* ---- identifiable abort: src/protocols/multi_party_ecdsa/gg_2020/blame.rs ---------------------------------------- */
 /* Every signer has opened the values the failing phase used; the functions re-derive the public ciphertexts from the
@@ -663,6 +673,15 @@ int mpe_gg20_sign(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, const int3
 int mpe_gg20_sign_sets(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, const int32_t* d_keyset, const int32_t* d_sigset,
                        const mpe_gg20_nonces* nonces, uint32_t* d_r, uint32_t* d_s, int32_t* d_recid, uint32_t* d_R, int32_t* d_status,
                        int dedup_verify, int chunk, void* stream);
+/* The offline stage alone, as one call: chunks and runs rounds 0-6 exactly as mpe_gg20_sign_sets does and, where that function signs,
+ * deposits every chunk into `pool`; the same scratch is zeroed before the call returns.  nonces->msg is not read and may be NULL.
+ * `pool` must be over `keys`, on this context's device, with all S ordinals local, else MPE_E_ARG and nothing is touched.  Row b goes to
+ * slot d_slot[b] ([batch], device).  d_status [batch]: the session's smallest non-zero party status if the session failed — what
+ * mpe_gg20_sign would report, MPE_GG20_STATUS_BAD_SET for a set index out of range included, not the pool's blanket 803 — otherwise
+ * the deposit's 801 / 802, otherwise 0.  A row with a non-zero status leaves its slot untouched. */
+int mpe_gg20_presign_sets(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, const int32_t* d_keyset, const int32_t* d_sigset,
+                          const mpe_gg20_nonces* nonces, mpe_gg20_presig_pool* pool, const int32_t* d_slot, int32_t* d_status,
+                          int dedup_verify, int chunk, void* stream);
 
 /* ---- a stream of batches: the pipelined engine ------------------------------------------------------------------------
  * A signing service receives batch after batch of `batch` sessions (BASELINE config 4: 1 024) and one such batch alone is
@@ -693,6 +712,36 @@ int mpe_gg20_pipeline_submit(mpe_gg20_pipeline* p, const int32_t* d_keyset, cons
 int mpe_gg20_pipeline_submit_seeded(mpe_gg20_pipeline* p, const int32_t* d_keyset, const uint8_t* h_seed32, uint64_t batch_counter,
                                     const uint32_t* d_msg, uint32_t* d_r, uint32_t* d_s, int32_t* d_recid, uint32_t* d_R, int32_t* d_status,
                                     void* stream, uint64_t* ticket);
+/* ... with a signer set per session (d_sigset [batch], device, staged next to d_keyset; NULL = the two calls above): `keys` must hold the
+ * secrets of every member of every one of its sets, else MPE_E_ARG.  A group may mix batches with and without sets (without: set 0);
+ * a group in which no batch names its sets launches what mpe_gg20_sign launches.  An index out of range is that session's
+ * MPE_GG20_STATUS_BAD_SET.  The seeded form draws every value as mpe_gg20_sample_nonces_sets does. */
+int mpe_gg20_pipeline_submit_sets(mpe_gg20_pipeline* p, const int32_t* d_keyset, const int32_t* d_sigset, const mpe_gg20_nonces* nonces,
+                                  uint32_t* d_r, uint32_t* d_s, int32_t* d_recid, uint32_t* d_R, int32_t* d_status, void* stream,
+                                  uint64_t* ticket);
+int mpe_gg20_pipeline_submit_seeded_sets(mpe_gg20_pipeline* p, const int32_t* d_keyset, const int32_t* d_sigset, const uint8_t* h_seed32,
+                                         uint64_t batch_counter, const uint32_t* d_msg, uint32_t* d_r, uint32_t* d_s, int32_t* d_recid,
+                                         uint32_t* d_R, int32_t* d_status, void* stream, uint64_t* ticket);
+/* A PRESIG engine: the same object — tickets, grouping, flush / wait / query / poll, deadline, eager, latency, counters, inject_fault —
+ * whose passes end in the deposit of mpe_gg20_presign_sets into `pool` (over `keys`, same device, all S ordinals local; `keys` must hold
+ * the secrets of every member of every one of its sets) instead of rounds 7-8.
+ *   submit_presig         the caller's sampled values of ONE batch (nonces->msg is not read and may be NULL), d_keyset / d_sigset as
+ *                         above (NULL = key set 0 / set 0), d_slot [batch] the pool slots of its rows, staged like d_keyset;
+ *                         d_status [batch] is the one result array, with the statuses of mpe_gg20_presign_sets
+ *   submit_presig_seeded  the seeded form; there is no message
+ * Which slots are free stays the caller's policy.  All lanes deposit into the one pool concurrently, and other calls on the pool may
+ * run beside them: the slot's compare-and-swap makes that safe, a row that loses it reads 802 and touches nothing.
+ * Submitting the wrong kind (submit / submit_seeded to a presig engine, submit_presig* to a signing engine) is MPE_E_ARG before a
+ * slot or a ticket is taken.  Failure contract: a failed pass fills every batch's d_status with MPE_GG20_STATUS_PASS_FAILED(rc); the
+ * deposit is the last step of a pass, so no slot of that group has left EMPTY (a group of more than 65 536 sessions runs in several
+ * chunks: rows of chunks that were deposited before a later chunk failed read PASS_FAILED too and their slots are the caller's to
+ * discard).  The next group deposits.  The engine is destroyed BEFORE its pool. */
+int mpe_gg20_pipeline_create_presig(mpe_ctx* ctx, const mpe_gg20_keys* keys, mpe_gg20_presig_pool* pool, int batch, int group, int lanes,
+                                    int dedup_verify, mpe_gg20_pipeline** out);
+int mpe_gg20_pipeline_submit_presig(mpe_gg20_pipeline* p, const int32_t* d_keyset, const int32_t* d_sigset, const mpe_gg20_nonces* nonces,
+                                    const int32_t* d_slot, int32_t* d_status, void* stream, uint64_t* ticket);
+int mpe_gg20_pipeline_submit_presig_seeded(mpe_gg20_pipeline* p, const int32_t* d_keyset, const int32_t* d_sigset, const uint8_t* h_seed32,
+                                           uint64_t batch_counter, const int32_t* d_slot, int32_t* d_status, void* stream, uint64_t* ticket);
 int mpe_gg20_pipeline_flush(mpe_gg20_pipeline* p);
 int mpe_gg20_pipeline_query(mpe_gg20_pipeline* p, uint64_t ticket, int* done);
 int mpe_gg20_pipeline_wait(mpe_gg20_pipeline* p, uint64_t ticket);

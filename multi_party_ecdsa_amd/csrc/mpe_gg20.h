@@ -1605,13 +1605,26 @@ int mpe_gg20_session_result(const mpe_gg20_session* s, int32_t* d_status, uint32
   return MPE_OK;
 }
 
-int mpe_gg20_sign(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, const int32_t* d_keyset, const mpe_gg20_nonces* nonces, uint32_t* d_r,
-                  uint32_t* d_s, int32_t* d_recid, uint32_t* d_R, int32_t* d_status, int dedup_verify, int chunk, void* stream) {
-  return mpe_gg20_sign_sets(ctx, keys, batch, d_keyset, nullptr, nonces, d_r, d_s, d_recid, d_R, d_status, dedup_verify, chunk, stream);
-}
-int mpe_gg20_sign_sets(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, const int32_t* d_keyset, const int32_t* d_sigset, const mpe_gg20_nonces* nonces,
-                       uint32_t* d_r, uint32_t* d_s, int32_t* d_recid, uint32_t* d_R, int32_t* d_status, int dedup_verify, int chunk, void* stream) {
-  if (!ctx || !keys || !nonces || !d_r || !d_s || !d_recid || !d_status || batch < 0) return MPE_E_ARG;
+}  // extern "C"
+
+namespace mpe {
+namespace gg {
+
+// What the tail of a lock-step pass sees of one chunk: the session behind round 6, its rows [b0, b0 + B) of the call's batch, the free
+// message slab and the per-chunk result scratch ([S][Bc] each) behind the slabs.
+struct LockstepChunk {
+  mpe_gg20_session* s;
+  int b0, B;
+  const uint32_t* msg;             // the chunk's rows of nonces->msg (NULL when the caller gave none)
+  uint32_t* M6;
+  int32_t* pst; uint32_t *pr, *ps; int32_t* prec; uint32_t* pR;
+};
+// The lock-step composition with every signer local, rounds 0-6: chunks the batch, creates each chunk's session, runs the rounds over the
+// two alternating message slabs, hands the session to `tail(chunk, st)` — rounds 7-8 and the results for mpe_gg20_sign_sets, the deposit
+// for mpe_gg20_presign_sets (mpe_presig.h) — releases it, and wipes the slabs and the context's workspace.
+template <class Tail>
+static int lockstep_pass(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, const int32_t* d_keyset, const int32_t* d_sigset, const mpe_gg20_nonces* nonces,
+                         int dedup_verify, int chunk, void* stream, Tail tail) {
   const int S = keys->S, n = keys->n;
   for (int k = 0; k < (d_sigset ? keys->nsets : 1); ++k)
     for (int i = 0; i < S; ++i)
@@ -1662,7 +1675,8 @@ int mpe_gg20_sign_sets(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, const
     Z.mb_beta_tag += oMB * 64; Z.mb_r += oMB * 64; Z.mb_nonce_b += oMB * 8; Z.mb_nonce_bt += oMB * 8;
     Z.l += oPI * 8; Z.ped_s1 += oPI * 8; Z.ped_s2 += oPI * 8;
     Z.pdl_alpha += oPP * 24; Z.pdl_beta += oPP * 64; Z.pdl_rho += oPP * 72; Z.pdl_gamma += oPP * 88;
-    Z.heg_s1 += oPI * 8; Z.heg_s2 += oPI * 8; Z.msg += (size_t)b0 * 8;
+    Z.heg_s1 += oPI * 8; Z.heg_s2 += oPI * 8;
+    if (Z.msg) Z.msg += (size_t)b0 * 8;
     mpe_gg20_session* s = nullptr;
     int rc = mpe_gg20_session_create_sets(ctx, keys, B, S, local, d_keyset ? d_keyset + b0 : nullptr, d_sigset ? d_sigset + b0 : nullptr, 0, &Z, dedup_verify, &s, stream);
     if (rc != MPE_OK) return rc;
@@ -1674,18 +1688,37 @@ int mpe_gg20_sign_sets(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, const
     if (rc == MPE_OK) rc = mpe::gg::round4(s, M[3], nullptr, M[4], st);
     if (rc == MPE_OK) rc = mpe::gg::round5(s, M[4], nullptr, M[5], st);
     if (rc == MPE_OK) rc = mpe::gg::round6(s, M[5], nullptr, st);
-    if (rc == MPE_OK) rc = mpe::gg::round7(s, Z.msg, M[6], st);
-    if (rc == MPE_OK) rc = mpe::gg::complete(s, M[6], nullptr, st);
-    if (rc == MPE_OK) rc = mpe_gg20_session_result(s, pst, nullptr, pr, ps, prec, pR, stream);
-    if (rc == MPE_OK)
-      hipLaunchKernelGGL(mpe::gg::sign_finish_kernel, dim3(mpe::blocks_for(B, 64)), dim3(64), 0, st, B, S, b0, pst, pr, ps, prec, pR, d_r, d_s,
-                         d_recid, d_R, d_status);
+    if (rc == MPE_OK) rc = tail(LockstepChunk{s, b0, B, Z.msg, M[6], pst, pr, ps, prec, pR}, st);
     mpe::gg::session_release(s, st);
     if (rc != MPE_OK) return rc;
   }
   // the message slabs and the composite workspace held nonce-derived values of this call
   (void)hipMemsetAsync(ctx->slab_buf, 0, need, st);
   return mpe_ctx_wipe(ctx, stream);
+}
+
+}  // namespace gg
+}  // namespace mpe
+
+extern "C" {
+
+int mpe_gg20_sign(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, const int32_t* d_keyset, const mpe_gg20_nonces* nonces, uint32_t* d_r,
+                  uint32_t* d_s, int32_t* d_recid, uint32_t* d_R, int32_t* d_status, int dedup_verify, int chunk, void* stream) {
+  return mpe_gg20_sign_sets(ctx, keys, batch, d_keyset, nullptr, nonces, d_r, d_s, d_recid, d_R, d_status, dedup_verify, chunk, stream);
+}
+int mpe_gg20_sign_sets(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, const int32_t* d_keyset, const int32_t* d_sigset, const mpe_gg20_nonces* nonces,
+                       uint32_t* d_r, uint32_t* d_s, int32_t* d_recid, uint32_t* d_R, int32_t* d_status, int dedup_verify, int chunk, void* stream) {
+  if (!ctx || !keys || !nonces || !d_r || !d_s || !d_recid || !d_status || batch < 0) return MPE_E_ARG;
+  const int S = keys->S;
+  return mpe::gg::lockstep_pass(ctx, keys, batch, d_keyset, d_sigset, nonces, dedup_verify, chunk, stream, [&](const mpe::gg::LockstepChunk& c, hipStream_t st) {
+    int rc = mpe::gg::round7(c.s, c.msg, c.M6, st);
+    if (rc == MPE_OK) rc = mpe::gg::complete(c.s, c.M6, nullptr, st);
+    if (rc == MPE_OK) rc = mpe_gg20_session_result(c.s, c.pst, nullptr, c.pr, c.ps, c.prec, c.pR, stream);
+    if (rc == MPE_OK)
+      hipLaunchKernelGGL(mpe::gg::sign_finish_kernel, dim3(mpe::blocks_for(c.B, 64)), dim3(64), 0, st, c.B, S, c.b0, c.pst, c.pr, c.ps, c.prec, c.pR, d_r, d_s,
+                         d_recid, d_R, d_status);
+    return rc;
+  });
 }
 
 }  // extern "C"

@@ -29,7 +29,15 @@
 // every batch starts at once (lowest latency), under load the lanes are busy and the groups fill by themselves.  (3) and (4)
 // are evaluated inside every submit / query / poll call — the ONE host thread that drives the pipeline; there is no hidden thread.
 // A new group opens on an idle lane if there is one, otherwise on the next lane in turn.
-// Included by mpe_lib.hip after mpe_sample.h.
+//
+// Two kinds of engine share all of the above.  A SIGNING engine's pass is mpe_gg20_sign_sets (a lane stages the batches' signer-set
+// indices next to the key-set indices; a group in which no batch names its sets passes NULL and launches what mpe_gg20_sign launches).
+// A PRESIG engine's pass is mpe_gg20_presign_sets: rounds 0-6, then the deposit into the ONE pool all lanes share — the slot's
+// compare-and-swap (mpe_presig.h) is what makes concurrent deposits of several lanes, and other calls on the pool beside them, safe;
+// which slots to name stays the caller's policy.  Its batches have no message and one result array, d_status.  A failed pass fills it with
+// PASS_FAILED(rc); the deposit is the last step of a pass, so a pass that failed before it left every slot of the group EMPTY.  The engine
+// holds the pool's pointer: it is destroyed before its pool.
+// Included by mpe_lib.hip after mpe_presig.h and mpe_sample.h.
 #pragma once
 #include <chrono>
 
@@ -39,6 +47,8 @@ struct mpe_gg20_pipeline {
   static constexpr int MAX_LANES = 4, MAX_GROUP = 64, RING = 4096;
   mpe_ctx* parent = nullptr;
   const mpe_gg20_keys* K = nullptr;
+  mpe_gg20_presig_pool* pool = nullptr;       // a PRESIG engine: its passes end in the deposit into this pool (mpe_gg20_presign_sets)
+  bool every_set = false;                     // the key object holds the secrets of every member of every signer set
   int batch = 0, group = 0, lanes = 0, dedup = 0;
   int64_t deadline_us = -1;                   // < 0: no deadline
   int eager = 0;                              // launch a part-filled group as soon as its lane is idle
@@ -49,13 +59,14 @@ struct mpe_gg20_pipeline {
     mpe_ctx* ctx = nullptr;
     hipStream_t st = nullptr;
     mpe_gg20_nonce_buf* stage = nullptr;      // [group * batch] sessions, every signer local
-    int32_t* keyset = nullptr;
-    void* blob = nullptr;                     // keyset | r | s | R | recid | status | fail staging
+    int32_t *keyset = nullptr, *sigset = nullptr, *slot = nullptr;      // slot: a presig engine's pool slots
+    void* blob = nullptr;                     // keyset | sigset | slot | r | s | R | recid | status | fail staging
     size_t blob_bytes = 0;
     Out res{};
     int32_t* fail = nullptr;
     int filled = 0, seeded = 0;               // seeded: slots of the open group whose values the sampler draws (all or none)
-    bool any_keyset = false;
+    bool any_keyset = false, any_sigset = false;
+    bool with_sigset[MAX_GROUP];
     uint8_t seeds[32 * mpe::smp::MAX_SLOTS];
     uint64_t counters[mpe::smp::MAX_SLOTS];
     Out dst[MAX_GROUP];
@@ -103,12 +114,15 @@ static int launch_group(mpe_gg20_pipeline* p, int li) {
   mpe_gg20_nonces Z;
   (void)mpe_gg20_nonces_view(L.stage, &Z);
   const int32_t* ks = (p->K->K > 1 || L.any_keyset) ? L.keyset : nullptr;
+  const int32_t* ss = L.any_sigset ? L.sigset : nullptr;      // no batch of the group named its sets: the launches of mpe_gg20_sign
+  for (int g = 0; ss && g < L.filled; ++g)                    // a group may mix batches with and without sets: without = set 0
+    if (!L.with_sigset[g]) (void)hipMemsetAsync(L.sigset + (size_t)g * p->batch, 0, (size_t)p->batch * 4, L.st);
   if (mpe_gg20_pipeline::Ticket* t0 = ticket_of(p, L.ticket[0])) (void)hipEventRecord(t0->begin, L.st);
   int rc = MPE_OK;
   if (L.seeded) {                               // every value of every batch of the group: one launch of the sampler
     int32_t local[8];
     for (int i = 0; i < p->K->S; ++i) local[i] = i;
-    rc = mpe::smp::sample_gg20(L.ctx, p->K, p->batch, L.filled, p->K->S, local, ks, L.seeds, L.counters, &Z, L.fail, L.st);
+    rc = mpe::smp::sample_gg20(L.ctx, p->K, p->batch, L.filled, p->K->S, local, ks, L.seeds, L.counters, &Z, L.fail, L.st, ss);
     // the seeds derive every nonce of their batches: as sensitive as the key share, gone from host memory once the sampler is queued
     // (the kernel arguments were copied at launch)
     wipe_bytes(L.seeds, sizeof L.seeds);
@@ -120,7 +134,8 @@ static int launch_group(mpe_gg20_pipeline* p, int li) {
     mpe_set_error_msg("gg20 pipeline: injected pass failure");
   }
   if (rc == MPE_OK)
-    rc = mpe_gg20_sign(L.ctx, p->K, B, ks, &Z, L.res.r, L.res.s, L.res.recid, L.res.R, L.res.status, p->dedup, 0, L.st);
+    rc = p->pool ? mpe_gg20_presign_sets(L.ctx, p->K, B, ks, ss, &Z, p->pool, L.slot, L.res.status, p->dedup, 0, L.st)
+                 : mpe_gg20_sign_sets(L.ctx, p->K, B, ks, ss, &Z, L.res.r, L.res.s, L.res.recid, L.res.R, L.res.status, p->dedup, 0, L.st);
   if (rc == MPE_OK) {
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { mpe_set_error("gg20 pipeline launch", e); rc = MPE_E_HIP; }
@@ -130,7 +145,10 @@ static int launch_group(mpe_gg20_pipeline* p, int li) {
   for (int g = 0; g < L.filled; ++g) {
     const size_t o = (size_t)g * p->batch, nb = (size_t)p->batch;
     const mpe_gg20_pipeline::Out& d = L.dst[g];
-    if (rc == MPE_OK) {
+    if (p->pool) {                              // a presig engine's one result array
+      if (rc == MPE_OK) (void)hipMemcpyAsync(d.status, L.res.status + o, nb * 4, hipMemcpyDeviceToDevice, L.st);
+      else hipLaunchKernelGGL(fill_i32_kernel, dim3(mpe::blocks_for((int)nb, 256)), dim3(256), 0, L.st, d.status, (int)nb, (int32_t)MPE_GG20_STATUS_PASS_FAILED(rc));
+    } else if (rc == MPE_OK) {
       (void)hipMemcpyAsync(d.r, L.res.r + o * 8, nb * 32, hipMemcpyDeviceToDevice, L.st);
       (void)hipMemcpyAsync(d.s, L.res.s + o * 8, nb * 32, hipMemcpyDeviceToDevice, L.st);
       (void)hipMemcpyAsync(d.recid, L.res.recid + o, nb * 4, hipMemcpyDeviceToDevice, L.st);
@@ -147,8 +165,10 @@ static int launch_group(mpe_gg20_pipeline* p, int li) {
   // the staged sampled values (k_i, gamma_i, Paillier randomness) of this group do not wait for the next one to overwrite them,
   // nor do the lane's copies of the signatures (the owners have theirs)
   (void)hipMemsetAsync(L.stage->blob, 0, L.stage->bytes, L.st);
-  (void)hipMemsetAsync(L.res.r, 0, (size_t)B * 8 * 4, L.st);
-  (void)hipMemsetAsync(L.res.s, 0, (size_t)B * 8 * 4, L.st);
+  if (!p->pool) {
+    (void)hipMemsetAsync(L.res.r, 0, (size_t)B * 8 * 4, L.st);
+    (void)hipMemsetAsync(L.res.s, 0, (size_t)B * 8 * 4, L.st);
+  }
   mpe_gg20_pipeline::Ticket* t0 = ticket_of(p, L.ticket[0]);
   for (int g = 0; g < L.filled; ++g) {
     mpe_gg20_pipeline::Ticket* t = ticket_of(p, L.ticket[g]);
@@ -162,6 +182,7 @@ static int launch_group(mpe_gg20_pipeline* p, int li) {
   L.filled = 0;
   L.seeded = 0;
   L.any_keyset = false;
+  L.any_sigset = false;
   p->launched_groups++;
   if (rc != MPE_OK) p->failed_groups++;
   // the next group opens on an idle lane if there is one, otherwise on the next lane in turn
@@ -187,10 +208,10 @@ static int poll_open_group(mpe_gg20_pipeline* p, int* launched) {
   return launch_group(p, p->cur);
 }
 
-// common part of the two submit forms: reserves slot g of the current lane, records the ticket
+// common part of the submit forms: reserves slot g of the current lane, records the ticket (a presig engine's batch has d_status alone)
 static int open_slot(mpe_gg20_pipeline* p, uint32_t* d_r, uint32_t* d_s, int32_t* d_recid, uint32_t* d_R, int32_t* d_status, hipStream_t caller,
                      int* lane_out, int* slot_out, uint64_t* ticket_out) {
-  if (!p || !d_r || !d_s || !d_recid || !d_status || !ticket_out) return MPE_E_ARG;
+  if (!p || !d_status || !ticket_out || (!p->pool && (!d_r || !d_s || !d_recid))) return MPE_E_ARG;
   const uint64_t id = p->next_ticket;
   mpe_gg20_pipeline::Ticket* t = &p->ring[id % mpe_gg20_pipeline::RING];
   if (t->used && (!t->launched || hipEventQuery(t->done) != hipSuccess)) {
@@ -213,11 +234,15 @@ static int open_slot(mpe_gg20_pipeline* p, uint32_t* d_r, uint32_t* d_s, int32_t
   *lane_out = li; *slot_out = g; *ticket_out = id;
   return MPE_OK;
 }
-static int close_slot(mpe_gg20_pipeline* p, int li, const int32_t* d_keyset) {
+// d_sigset: the batch's signer sets, staged next to the key sets (a batch without them: zeros = set 0); d_slot: a presig engine's pool slots
+static int close_slot(mpe_gg20_pipeline* p, int li, const int32_t* d_keyset, const int32_t* d_sigset, const int32_t* d_slot) {
   mpe_gg20_pipeline::Lane& L = p->lane[li];
   const size_t o = (size_t)L.filled * p->batch;
   if (d_keyset) { (void)hipMemcpyAsync(L.keyset + o, d_keyset, (size_t)p->batch * 4, hipMemcpyDeviceToDevice, L.st); L.any_keyset = true; }
   else (void)hipMemsetAsync(L.keyset + o, 0, (size_t)p->batch * 4, L.st);
+  if (d_sigset) { (void)hipMemcpyAsync(L.sigset + o, d_sigset, (size_t)p->batch * 4, hipMemcpyDeviceToDevice, L.st); L.any_sigset = true; }
+  L.with_sigset[L.filled] = d_sigset != nullptr;      // (launch_group zeroes the rows of the others when the group names sets at all)
+  if (d_slot) (void)hipMemcpyAsync(L.slot + o, d_slot, (size_t)p->batch * 4, hipMemcpyDeviceToDevice, L.st);
   L.filled++;
   // a pass that fails is reported through the tickets of its batches (each owner learns it from wait / query and from its
   // status array), not through whichever submit happened to close the group: the submission itself succeeded
@@ -233,13 +258,23 @@ extern "C" {
 
 int mpe_gg20_pipeline_destroy(mpe_gg20_pipeline* p);
 
-int mpe_gg20_pipeline_create(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, int group, int lanes, int dedup_verify, mpe_gg20_pipeline** out) {
+}  // extern "C"
+
+namespace mpe {
+namespace pipe {
+
+// pool: NULL for a signing engine, the pool a presig engine deposits into
+static int create(mpe_ctx* ctx, const mpe_gg20_keys* keys, mpe_gg20_presig_pool* pool, int batch, int group, int lanes, int dedup_verify, mpe_gg20_pipeline** out) {
   if (!ctx || !keys || !out || batch <= 0 || group < 1 || group > mpe_gg20_pipeline::MAX_GROUP || lanes < 1 || lanes > mpe_gg20_pipeline::MAX_LANES)
     return MPE_E_ARG;
   for (int i = 0; i < keys->S; ++i) if (keys->own_slot[keys->signers[i]] < 0) { mpe_set_error_msg("gg20 pipeline: the key object must hold every signer's secrets"); return MPE_E_ARG; }
+  bool every_set = true;                      // the rule of mpe_gg20_sign_sets, asked once here and not pass by pass
+  for (int k = 0; k < keys->nsets; ++k)
+    for (int i = 0; i < keys->S; ++i) every_set = every_set && keys->own_slot[(keys->sets4[k] >> (4 * i)) & 15u] >= 0;
+  if (pool && !every_set) { mpe_set_error_msg("gg20 pipeline: the key object must hold the secrets of every member of every signer set"); return MPE_E_ARG; }
   mpe_gg20_pipeline* p = new (std::nothrow) mpe_gg20_pipeline();
   if (!p) return MPE_E_NOMEM;
-  p->parent = ctx; p->K = keys; p->batch = batch; p->group = group; p->lanes = lanes; p->dedup = dedup_verify ? 1 : 0;
+  p->parent = ctx; p->K = keys; p->pool = pool; p->every_set = every_set; p->batch = batch; p->group = group; p->lanes = lanes; p->dedup = dedup_verify ? 1 : 0;
   const size_t GB = (size_t)group * batch;
   int rc = MPE_OK;
   for (int li = 0; li < lanes && rc == MPE_OK; ++li) {
@@ -255,12 +290,12 @@ int mpe_gg20_pipeline_create(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch,
     if (hipStreamCreateWithFlags(&L.st, hipStreamNonBlocking) != hipSuccess) { mpe_set_error_msg("gg20 pipeline: hipStreamCreate"); rc = MPE_E_HIP; break; }
     rc = mpe_gg20_nonces_alloc(c, keys, (int)GB, keys->S, &L.stage);
     if (rc != MPE_OK) break;
-    const size_t words = GB * (1 + 8 + 8 + 16 + 1 + 1) + 64;
+    const size_t words = GB * (3 + 8 + 8 + 16 + 1 + 1) + 64;
     L.blob_bytes = words * 4;
     if (hipMalloc(&L.blob, L.blob_bytes) != hipSuccess) { mpe_set_error_msg("gg20 pipeline: hipMalloc(staging)"); rc = MPE_E_NOMEM; break; }
     (void)hipMemset(L.blob, 0, L.blob_bytes);
     uint32_t* w = (uint32_t*)L.blob;
-    L.keyset = (int32_t*)w; w += GB;
+    L.keyset = (int32_t*)w; w += GB; L.sigset = (int32_t*)w; w += GB; L.slot = (int32_t*)w; w += GB;
     L.res.r = w; w += GB * 8; L.res.s = w; w += GB * 8; L.res.R = w; w += GB * 16;
     L.res.recid = (int32_t*)w; w += GB; L.res.status = (int32_t*)w; w += GB;
     L.fail = (int32_t*)w;
@@ -268,6 +303,41 @@ int mpe_gg20_pipeline_create(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch,
   if (rc != MPE_OK) { mpe_gg20_pipeline_destroy(p); return rc; }
   *out = p;
   return MPE_OK;
+}
+// the refusals every submit form shares, BEFORE a slot or a ticket is taken: the engine's kind, the key sets, the signer sets
+static int submit_refused(const mpe_gg20_pipeline* p, bool presig, const int32_t* d_keyset, const int32_t* d_sigset) {
+  if ((p->pool != nullptr) != presig) { mpe_set_error_msg("gg20 pipeline: a signing engine takes submit / submit_seeded, a presig engine submit_presig / submit_presig_seeded"); return MPE_E_ARG; }
+  if (p->K->K > 1 && !d_keyset) return MPE_E_ARG;
+  if (d_sigset && !p->every_set) { mpe_set_error_msg("gg20 pipeline: signer sets need the secrets of every member of every set in the key object"); return MPE_E_ARG; }
+  return MPE_OK;
+}
+// the caller-sampled forms: the first `fields` arrays of the batch go to slot g of the lane's staging (msg is the last field)
+static int stage_nonces(mpe_gg20_pipeline* p, int li, int g, mpe_gg20_nonces* src, int fields) {
+  mpe_gg20_pipeline::Lane& L = p->lane[li];
+  for (int f = 0; f < fields; ++f) {
+    mpe_gg20_nonce_buf* sb = L.stage;
+    const size_t w = sb->per_session[f] * (size_t)p->batch;
+    const uint32_t* from = *mpe::smp::nonce_field_ptr(src, f);
+    uint32_t* to = const_cast<uint32_t*>(*mpe::smp::nonce_field_ptr(&sb->view, f)) + (size_t)g * w;
+    (void)hipMemcpyAsync(to, from, w * 4, hipMemcpyDeviceToDevice, L.st);
+  }
+  return MPE_OK;
+}
+static const char* const MIXED_FORMS = "gg20 pipeline: a group holds seeded or caller-sampled batches, not both (flush between the two forms)";
+
+}  // namespace pipe
+}  // namespace mpe
+
+extern "C" {
+
+int mpe_gg20_pipeline_create(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, int group, int lanes, int dedup_verify, mpe_gg20_pipeline** out) {
+  return mpe::pipe::create(ctx, keys, nullptr, batch, group, lanes, dedup_verify, out);
+}
+int mpe_gg20_pipeline_create_presig(mpe_ctx* ctx, const mpe_gg20_keys* keys, mpe_gg20_presig_pool* pool, int batch, int group, int lanes,
+                                    int dedup_verify, mpe_gg20_pipeline** out) {
+  if (!ctx || !keys || !pool) return MPE_E_ARG;
+  if (!mpe::psg::holds_every_signer(pool, keys, ctx)) { mpe_set_error_msg("gg20 pipeline: the pool is not over these keys with every signer local"); return MPE_E_ARG; }
+  return mpe::pipe::create(ctx, keys, pool, batch, group, lanes, dedup_verify, out);
 }
 
 int mpe_gg20_pipeline_destroy(mpe_gg20_pipeline* p) {
@@ -289,34 +359,36 @@ int mpe_gg20_pipeline_destroy(mpe_gg20_pipeline* p) {
 
 int mpe_gg20_pipeline_submit(mpe_gg20_pipeline* p, const int32_t* d_keyset, const mpe_gg20_nonces* nonces, uint32_t* d_r, uint32_t* d_s, int32_t* d_recid,
                              uint32_t* d_R, int32_t* d_status, void* stream, uint64_t* ticket) {
+  return mpe_gg20_pipeline_submit_sets(p, d_keyset, nullptr, nonces, d_r, d_s, d_recid, d_R, d_status, stream, ticket);
+}
+int mpe_gg20_pipeline_submit_sets(mpe_gg20_pipeline* p, const int32_t* d_keyset, const int32_t* d_sigset, const mpe_gg20_nonces* nonces, uint32_t* d_r,
+                                  uint32_t* d_s, int32_t* d_recid, uint32_t* d_R, int32_t* d_status, void* stream, uint64_t* ticket) {
   if (!p || !nonces) return MPE_E_ARG;
-  if (p->K->K > 1 && !d_keyset) return MPE_E_ARG;
   // every refusal comes BEFORE a slot and a ticket are taken: a refused call leaves the pipeline as it was
+  MPE_TRY(mpe::pipe::submit_refused(p, false, d_keyset, d_sigset));
   mpe_gg20_nonces src = *nonces;
   for (int f = 0; f < mpe::smp::NF; ++f)
     if (!*mpe::smp::nonce_field_ptr(&src, f)) { mpe_set_error_msg("gg20 pipeline: a nonce array is NULL"); return MPE_E_ARG; }
   (void)mpe::pipe::poll_open_group(p, nullptr);
-  if (p->lane[p->cur].seeded) { mpe_set_error_msg("gg20 pipeline: a group holds seeded or caller-sampled batches, not both (flush between the two forms)"); return MPE_E_ARG; }
+  if (p->lane[p->cur].seeded) { mpe_set_error_msg(mpe::pipe::MIXED_FORMS); return MPE_E_ARG; }
   int li = 0, g = 0;
   MPE_TRY(mpe::pipe::open_slot(p, d_r, d_s, d_recid, d_R, d_status, (hipStream_t)stream, &li, &g, ticket));
-  mpe_gg20_pipeline::Lane& L = p->lane[li];
-  for (int f = 0; f < mpe::smp::NF; ++f) {
-    mpe_gg20_nonce_buf* sb = L.stage;
-    const size_t w = sb->per_session[f] * (size_t)p->batch;
-    const uint32_t* from = *mpe::smp::nonce_field_ptr(&src, f);
-    uint32_t* to = const_cast<uint32_t*>(*mpe::smp::nonce_field_ptr(&sb->view, f)) + (size_t)g * w;
-    (void)hipMemcpyAsync(to, from, w * 4, hipMemcpyDeviceToDevice, L.st);
-  }
-  return mpe::pipe::close_slot(p, li, d_keyset);
+  (void)mpe::pipe::stage_nonces(p, li, g, &src, mpe::smp::NF);
+  return mpe::pipe::close_slot(p, li, d_keyset, d_sigset, nullptr);
 }
 
 int mpe_gg20_pipeline_submit_seeded(mpe_gg20_pipeline* p, const int32_t* d_keyset, const uint8_t* h_seed32, uint64_t batch_counter, const uint32_t* d_msg,
                                     uint32_t* d_r, uint32_t* d_s, int32_t* d_recid, uint32_t* d_R, int32_t* d_status, void* stream, uint64_t* ticket) {
+  return mpe_gg20_pipeline_submit_seeded_sets(p, d_keyset, nullptr, h_seed32, batch_counter, d_msg, d_r, d_s, d_recid, d_R, d_status, stream, ticket);
+}
+int mpe_gg20_pipeline_submit_seeded_sets(mpe_gg20_pipeline* p, const int32_t* d_keyset, const int32_t* d_sigset, const uint8_t* h_seed32, uint64_t batch_counter,
+                                         const uint32_t* d_msg, uint32_t* d_r, uint32_t* d_s, int32_t* d_recid, uint32_t* d_R, int32_t* d_status, void* stream,
+                                         uint64_t* ticket) {
   if (!p || !h_seed32 || !d_msg || (batch_counter >> 56) != 0) return MPE_E_ARG;
+  MPE_TRY(mpe::pipe::submit_refused(p, false, d_keyset, d_sigset));
   if (p->group > mpe::smp::MAX_SLOTS) { mpe_set_error_msg("gg20 pipeline: seeded submission needs group <= 16 (one sampler launch per group)"); return MPE_E_ARG; }
-  if (p->K->K > 1 && !d_keyset) return MPE_E_ARG;
   (void)mpe::pipe::poll_open_group(p, nullptr);
-  if (p->lane[p->cur].filled != p->lane[p->cur].seeded) { mpe_set_error_msg("gg20 pipeline: a group holds seeded or caller-sampled batches, not both (flush between the two forms)"); return MPE_E_ARG; }
+  if (p->lane[p->cur].filled != p->lane[p->cur].seeded) { mpe_set_error_msg(mpe::pipe::MIXED_FORMS); return MPE_E_ARG; }
   int li = 0, g = 0;
   MPE_TRY(mpe::pipe::open_slot(p, d_r, d_s, d_recid, d_R, d_status, (hipStream_t)stream, &li, &g, ticket));
   mpe_gg20_pipeline::Lane& L = p->lane[li];
@@ -324,7 +396,38 @@ int mpe_gg20_pipeline_submit_seeded(mpe_gg20_pipeline* p, const int32_t* d_keyse
   memcpy(L.seeds + 32 * g, h_seed32, 32);
   L.counters[g] = batch_counter;
   L.seeded++;
-  return mpe::pipe::close_slot(p, li, d_keyset);
+  return mpe::pipe::close_slot(p, li, d_keyset, d_sigset, nullptr);
+}
+
+// The presig engine's two forms: no message, d_slot [batch] staged like d_keyset, d_status the one result array.
+int mpe_gg20_pipeline_submit_presig(mpe_gg20_pipeline* p, const int32_t* d_keyset, const int32_t* d_sigset, const mpe_gg20_nonces* nonces, const int32_t* d_slot,
+                                    int32_t* d_status, void* stream, uint64_t* ticket) {
+  if (!p || !nonces || !d_slot) return MPE_E_ARG;
+  MPE_TRY(mpe::pipe::submit_refused(p, true, d_keyset, d_sigset));
+  mpe_gg20_nonces src = *nonces;
+  for (int f = 0; f < mpe::smp::NF - 1; ++f)          // (msg, the last field, is not read)
+    if (!*mpe::smp::nonce_field_ptr(&src, f)) { mpe_set_error_msg("gg20 pipeline: a nonce array is NULL"); return MPE_E_ARG; }
+  (void)mpe::pipe::poll_open_group(p, nullptr);
+  if (p->lane[p->cur].seeded) { mpe_set_error_msg(mpe::pipe::MIXED_FORMS); return MPE_E_ARG; }
+  int li = 0, g = 0;
+  MPE_TRY(mpe::pipe::open_slot(p, nullptr, nullptr, nullptr, nullptr, d_status, (hipStream_t)stream, &li, &g, ticket));
+  (void)mpe::pipe::stage_nonces(p, li, g, &src, mpe::smp::NF - 1);
+  return mpe::pipe::close_slot(p, li, d_keyset, d_sigset, d_slot);
+}
+int mpe_gg20_pipeline_submit_presig_seeded(mpe_gg20_pipeline* p, const int32_t* d_keyset, const int32_t* d_sigset, const uint8_t* h_seed32, uint64_t batch_counter,
+                                           const int32_t* d_slot, int32_t* d_status, void* stream, uint64_t* ticket) {
+  if (!p || !h_seed32 || !d_slot || (batch_counter >> 56) != 0) return MPE_E_ARG;
+  MPE_TRY(mpe::pipe::submit_refused(p, true, d_keyset, d_sigset));
+  if (p->group > mpe::smp::MAX_SLOTS) { mpe_set_error_msg("gg20 pipeline: seeded submission needs group <= 16 (one sampler launch per group)"); return MPE_E_ARG; }
+  (void)mpe::pipe::poll_open_group(p, nullptr);
+  if (p->lane[p->cur].filled != p->lane[p->cur].seeded) { mpe_set_error_msg(mpe::pipe::MIXED_FORMS); return MPE_E_ARG; }
+  int li = 0, g = 0;
+  MPE_TRY(mpe::pipe::open_slot(p, nullptr, nullptr, nullptr, nullptr, d_status, (hipStream_t)stream, &li, &g, ticket));
+  mpe_gg20_pipeline::Lane& L = p->lane[li];
+  memcpy(L.seeds + 32 * g, h_seed32, 32);
+  L.counters[g] = batch_counter;
+  L.seeded++;
+  return mpe::pipe::close_slot(p, li, d_keyset, d_sigset, d_slot);
 }
 
 int mpe_gg20_pipeline_flush(mpe_gg20_pipeline* p) {

@@ -161,6 +161,63 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC presig_complete_kernel(View P, 
   }
 }
 
+// the offline stage as one call (mpe_gg20_presign_sets): the sibling of sign_finish_kernel.  A row's status = its session's smallest
+// non-zero party status behind round 6 — what mpe_gg20_sign would report, 92 for a bad set index included, not the deposit's blanket
+// 803 — otherwise the deposit's 801 / 802, otherwise 0.  sess_status: the session's per-round words, which the deposit's wipe leaves.
+__global__ void presign_finish_kernel(int B, int L, int b0, const int32_t* __restrict__ sess_status, const int32_t* __restrict__ dep,
+                                      int32_t* __restrict__ status) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  int st = 0;
+  for (int li = 0; li < L; ++li) {
+    const int s = gg::resolve_status(sess_status, (size_t)B * L, b * L + li, 6, nullptr, nullptr);
+    if (s && (!st || s < st)) st = s;
+  }
+  status[(size_t)b0 + b] = st ? st : dep[b];
+}
+
+// the online step in one launch, for a pool that holds all S signers (L == S): the claim of presig_sign_kernel, every party's
+// s_i = m k_i + r sigma_i with k_i and sigma_i zeroed at once, the sum, then output_signature's low-s rule and verify ONCE, and the
+// slot back to EMPTY with the wipe.  One verify is exact: the S parties of the composed path (sign + complete) verify the same sum s
+// under the same y, and the same (m, r, R.y) when the slot's parties hold one R — the argument of dedup_verify.  A healthy offline
+// stage leaves one R; a slot whose parties hold different ones (only an import can make it) is 701 here without a verify, as at least one
+// party's verify of the composed path fails on it but for a negligible chance.  r_out, s_out [count][8], zero unless status is 0.
+__global__ void __launch_bounds__(64) MPE_EC_OCC presig_sign_online_kernel(View P, int count, const int32_t* __restrict__ d_slot,
+                                                                           const uint32_t* __restrict__ msg, const uint32_t* __restrict__ y,
+                                                                           uint32_t* __restrict__ r_out, uint32_t* __restrict__ s_out,
+                                                                           int32_t* __restrict__ recid_out, int32_t* __restrict__ status) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= count) return;
+  const int slot = d_slot[g];
+  int code = 0, recid = 0;
+  if (slot < 0 || slot >= P.cap) code = MPE_GG20_PRESIG_SIGN_RANGE;
+  else if (!claim(P.state + slot, READY)) code = MPE_GG20_PRESIG_SIGN_NOT_READY;
+  ec::U256 r = ec::u256_zero(), s = ec::u256_zero();
+  if (code == 0) {
+    const size_t p0 = (size_t)slot * P.L;
+    const ec::U256 m = ec::sc_reduce(msg + (size_t)g * 8, 8);
+    r = ec::sc_reduce(P.R + p0 * 16, 8);
+    const ec::U256 ry = ec::sc_reduce(P.R + p0 * 16 + 8, 8);
+    bool one_R = true;
+#pragma unroll 1
+    for (int li = 0; li < P.L; ++li) {
+      const size_t pl = p0 + li;
+      one_R = one_R && gg::words_eq(P.R + pl * 16, P.R + p0 * 16, 16);
+      s = ec::sc_add(s, ec::sc_add(ec::sc_mul(m, ec::u256_load(P.k + pl * 8)), ec::sc_mul(r, ec::u256_load(P.sigma + pl * 8))));
+      zero_words(P.k + pl * 8, 8); zero_words(P.sigma + pl * 8, 8);
+    }
+    if (!one_R || !gg::output_signature_check(s, recid, m, r, ry, y + (size_t)P.keyset[slot] * 16)) {
+      code = MPE_GG20_PRESIG_VERIFY_FAILED; r = ec::u256_zero(); s = ec::u256_zero(); recid = 0;
+    }
+    wipe_slot(P, slot);
+    settle(P.state + slot, EMPTY);
+  }
+  ec::u256_store(r_out + (size_t)g * 8, r);
+  ec::u256_store(s_out + (size_t)g * 8, s);
+  recid_out[g] = recid;
+  if (status) status[g] = code;
+}
+
 // export: READY -> EMPTY, the record is then the only copy.  rec [count][REC_HEAD + REC_PARTY L]; a losing row's record is zero.
 __global__ void __launch_bounds__(64) presig_export_kernel(View P, int count, const int32_t* __restrict__ d_slot, const uint32_t* __restrict__ y,
                                                            uint32_t* __restrict__ rec, int32_t* __restrict__ status) {
@@ -290,6 +347,28 @@ static int launched(const char* what) {
   if (e != hipSuccess) { mpe_set_error(what, e); return MPE_E_HIP; }
   return MPE_OK;
 }
+// The deposit for callers inside the library: the session's context may be another one ON THE SAME DEVICE (the pipelined engine's lanes
+// run on contexts of their own; the pool reads nothing from its context).  mpe_gg20_presig_deposit asks for the pool's context first.
+static int deposit_into(mpe_gg20_presig_pool* p, mpe_gg20_session* s, const int32_t* d_slot, int32_t* d_status, hipStream_t st) {
+  if (!p || !s || !d_slot) return MPE_E_ARG;
+  if (s->failed || s->next_round != 7) { mpe_set_error_msg("presig deposit: the session is not behind round 6"); return MPE_E_ARG; }
+  bool same = s->K == p->K && s->ctx->device == p->ctx->device && s->L == p->v.L && s->d.lparty < 0;      // (the pool's local parties are ordinals)
+  for (int i = 0; same && i < s->L; ++i) same = s->d.loc[i] == p->v.loc[i];
+  if (!same) { mpe_set_error_msg("presig deposit: the session's keys or local parties are not the pool's"); return MPE_E_ARG; }
+  hipLaunchKernelGGL(presig_deposit_kernel, dim3(blocks_for(s->B, 64)), dim3(64), 0, st, p->v, s->B, d_slot, s->kq, s->sigma_i,
+                     s->R, s->status, s->d.ks, s->d.ss, d_status);
+  int rc = launched("presig_deposit_kernel");
+  // deposited or not, the session's copy goes, as mpe_gg20_session_abort wipes it: the only live k_i is the pool's
+  const hipError_t em = wipe_session_after_deposit(s, st);
+  if (em != hipSuccess && rc == MPE_OK) { mpe_set_error("presig deposit (wipe)", em); rc = MPE_E_HIP; }
+  s->failed = true;
+  s->next_round = 9;
+  return rc;
+}
+// a pool over `keys` on `ctx`'s device that holds all S signers (its ordinals are then 0 .. S-1)
+static bool holds_every_signer(const mpe_gg20_presig_pool* p, const mpe_gg20_keys* keys, const mpe_ctx* ctx) {
+  return p && p->K == keys && p->v.L == keys->S && (!ctx || p->ctx->device == ctx->device);
+}
 
 }  // namespace psg
 }  // namespace mpe
@@ -334,19 +413,35 @@ int mpe_gg20_presig_record_words(const mpe_gg20_presig_pool* p) { return p ? mpe
 int mpe_gg20_presig_deposit(mpe_gg20_presig_pool* p, mpe_gg20_session* s, const int32_t* d_slot, int32_t* d_status, void* stream) {
   if (!p || !s || !d_slot) return MPE_E_ARG;
   if (s->failed || s->next_round != 7) { mpe_set_error_msg("presig deposit: the session is not behind round 6"); return MPE_E_ARG; }
-  bool same = s->K == p->K && s->ctx == p->ctx && s->L == p->v.L && s->d.lparty < 0;      // (the pool's local parties are ordinals)
-  for (int i = 0; same && i < s->L; ++i) same = s->d.loc[i] == p->v.loc[i];
-  if (!same) { mpe_set_error_msg("presig deposit: the session's keys or local parties are not the pool's"); return MPE_E_ARG; }
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(mpe::psg::presig_deposit_kernel, dim3(mpe::blocks_for(s->B, 64)), dim3(64), 0, st, p->v, s->B, d_slot, s->kq, s->sigma_i,
-                     s->R, s->status, s->d.ks, s->d.ss, d_status);
-  int rc = mpe::psg::launched("presig_deposit_kernel");
-  // deposited or not, the session's copy goes, as mpe_gg20_session_abort wipes it: the only live k_i is the pool's
-  const hipError_t em = mpe::psg::wipe_session_after_deposit(s, st);
-  if (em != hipSuccess && rc == MPE_OK) { mpe_set_error("presig deposit (wipe)", em); rc = MPE_E_HIP; }
-  s->failed = true;
-  s->next_round = 9;
-  return rc;
+  if (s->ctx != p->ctx) { mpe_set_error_msg("presig deposit: the session's keys or local parties are not the pool's"); return MPE_E_ARG; }
+  return mpe::psg::deposit_into(p, s, d_slot, d_status, (hipStream_t)stream);
+}
+
+int mpe_gg20_presign_sets(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, const int32_t* d_keyset, const int32_t* d_sigset,
+                          const mpe_gg20_nonces* nonces, mpe_gg20_presig_pool* pool, const int32_t* d_slot, int32_t* d_status, int dedup_verify,
+                          int chunk, void* stream) {
+  if (!ctx || !keys || !nonces || !pool || !d_slot || !d_status || batch < 0) return MPE_E_ARG;
+  if (!mpe::psg::holds_every_signer(pool, keys, ctx)) { mpe_set_error_msg("mpe_gg20_presign_sets: the pool is not over these keys with every signer local"); return MPE_E_ARG; }
+  const int S = keys->S;
+  return mpe::gg::lockstep_pass(ctx, keys, batch, d_keyset, d_sigset, nonces, dedup_verify, chunk, stream, [&](const mpe::gg::LockstepChunk& c, hipStream_t st) {
+    // the chunk's deposit codes go to the result scratch behind the slabs ([S][Bc] words, B of them used)
+    int rc = mpe::psg::deposit_into(pool, c.s, d_slot + c.b0, c.pst, st);
+    if (rc == MPE_OK) {
+      hipLaunchKernelGGL(mpe::psg::presign_finish_kernel, dim3(mpe::blocks_for(c.B, 64)), dim3(64), 0, st, c.B, S, c.b0, c.s->status, c.pst, d_status);
+      rc = mpe::psg::launched("presign_finish_kernel");
+    }
+    return rc;
+  });
+}
+
+int mpe_gg20_sign_online(mpe_gg20_presig_pool* p, int count, const int32_t* d_slot, const uint32_t* d_msg, uint32_t* d_r, uint32_t* d_s,
+                                int32_t* d_recid, int32_t* d_status, void* stream) {
+  if (!p || count < 0 || (count && (!d_slot || !d_msg || !d_r || !d_s || !d_recid))) return MPE_E_ARG;
+  if (p->v.L != p->v.S) { mpe_set_error_msg("mpe_gg20_sign_online: the pool does not hold every signer"); return MPE_E_ARG; }
+  if (!count) return MPE_OK;
+  hipLaunchKernelGGL(mpe::psg::presig_sign_online_kernel, dim3(mpe::blocks_for(count, 64)), dim3(64), 0, (hipStream_t)stream, p->v, count, d_slot,
+                     d_msg, p->K->y, d_r, d_s, d_recid, d_status);
+  return mpe::psg::launched("presig_sign_online_kernel");
 }
 
 int mpe_gg20_presig_sign(mpe_gg20_presig_pool* p, int count, const int32_t* d_slot, const uint32_t* d_msg, uint32_t* d_s_i, int32_t* d_status,

@@ -741,6 +741,18 @@ class PresigPool:
         self._pending.append((d_slot, o["status"]))          # 0 and 701 emptied the slot, 821 / 822 did not
         return o
 
+    def sign_online(self, slots, msg):
+        """The online step in one launch (mpe_gg20_sign_online; the pool holds every signer): what gg20_sign_online returns —
+        r, s [count, 8], recid, status [count] (811 / 812 from the claim, 701 when the one verify fails; zero outputs unless 0)."""
+        d_slot = self._slots(slots)
+        count, dv = d_slot.numel(), self.ctx.device
+        r, s = torch.empty((count, 8), dtype=torch.int32, device=dv), torch.empty((count, 8), dtype=torch.int32, device=dv)
+        recid, status = torch.empty((count,), dtype=torch.int32, device=dv), torch.empty((count,), dtype=torch.int32, device=dv)
+        N_.check(N_.lib.mpe_gg20_sign_online(self.h, count, _ptr(d_slot), _ptr(msg), _ptr(r), _ptr(s), _ptr(recid), _ptr(status),
+                                                    self.ctx.stream()), "mpe_gg20_sign_online")
+        self._pending.append((d_slot, status))              # 0 and 701 emptied the slot, 811 / 812 did not
+        return r, s, recid, status
+
     def export(self, slots):
         """READY slots -> (records [count, record_words], status [count]); the slots are EMPTY afterwards, the records the only copy"""
         d_slot = self._slots(slots)
@@ -799,6 +811,34 @@ def gg20_presign(ctx, keys, nonces, B, pool, keyset=None, dedup_verify=False, si
     finally:
         sess.close()
         ctx.wipe()                                           # the composites' workspace held nonce-derived values, as after mpe_gg20_sign
+
+
+def _no_msg(ctx, nonces):
+    """the nonce struct of a call that reads no message: `msg` may be missing from the dict"""
+    return nonces if "msg" in nonces else dict(nonces, msg=torch.zeros((0,), dtype=torch.int32, device=ctx.device))
+
+
+def gg20_presign_fused(ctx, keys, nonces, B, pool, slots=None, keyset=None, dedup_verify=False, sigset=None, chunk=0):
+    """gg20_presign as ONE C call (mpe_gg20_presign_sets): rounds 0-6 chunked as gg20_sign chunks them, every chunk deposited into
+    `pool` (free slots, or `slots`, one per session).  Returns the usable slots [B] (numpy int32; -1 where the row failed);
+    pool.last_status holds the row statuses: the session's own status, else the deposit's 801 / 802, else 0."""
+    mine = slots is None
+    if mine:
+        slots = pool._take(B)
+        pool._used.update(slots)
+    d_slot = pool._slots(slots)
+    if d_slot.numel() != B:
+        raise ValueError("gg20_presign_fused: one slot per session")
+    d_status = torch.full((B,), -1, dtype=torch.int32, device=ctx.device)
+    nn = _struct(N_.Gg20Nonces, _no_msg(ctx, nonces))
+    try:
+        N_.check(N_.lib.mpe_gg20_presign_sets(ctx.h, keys.h, B, _ptr(keyset), _ptr(sigset), C.byref(nn), pool.h, _ptr(d_slot), _ptr(d_status),
+                                              int(bool(dedup_verify)), int(chunk), ctx.stream()), "mpe_gg20_presign_sets")
+    except N_.MpeError:
+        if mine:
+            pool._used.difference_update(slots)
+        raise
+    return pool._filled(d_slot.cpu().numpy(), d_status.cpu().numpy(), not mine)
 
 
 def gg20_sign_online(pool, slots, msg):
@@ -881,12 +921,17 @@ def shard_in_off(placement, S, world, batch, block):
 class Gg20Pipeline:
     """mpe_gg20_pipeline_*: a stream of `batch`-session batches, `group` of them coalesced per pass, `lanes` passes in flight on one
     stream each (include/mpecdsa_hip.h).  submit / submit_seeded return a ticket; the result tensors of a ticket are valid after
-    wait(ticket) (or after stream_wait on the consuming stream)."""
+    wait(ticket) (or after stream_wait on the consuming stream).  With `pool=` (a PresigPool over all S signers of `keys`) the object is
+    a PRESIG engine: submit_presig / submit_presig_seeded run the offline stage and deposit into the pool; close it before the pool."""
 
-    def __init__(self, ctx, keys, batch, group=4, lanes=2, dedup_verify=False):
-        self.ctx, self.keys, self.batch, self.group, self.lanes = ctx, keys, batch, group, lanes
+    def __init__(self, ctx, keys, batch, group=4, lanes=2, dedup_verify=False, pool=None):
+        self.ctx, self.keys, self.batch, self.group, self.lanes, self.pool = ctx, keys, batch, group, lanes, pool
         h = C.c_void_p()
-        N_.check(N_.lib.mpe_gg20_pipeline_create(ctx.h, keys.h, batch, group, lanes, int(bool(dedup_verify)), C.byref(h)), "mpe_gg20_pipeline_create")
+        if pool is None:
+            N_.check(N_.lib.mpe_gg20_pipeline_create(ctx.h, keys.h, batch, group, lanes, int(bool(dedup_verify)), C.byref(h)), "mpe_gg20_pipeline_create")
+        else:
+            N_.check(N_.lib.mpe_gg20_pipeline_create_presig(ctx.h, keys.h, pool.h, batch, group, lanes, int(bool(dedup_verify)), C.byref(h)),
+                     "mpe_gg20_pipeline_create_presig")
         self.h = h
         self._keep = {}                       # ticket -> the tensors the device still reads / writes
 
@@ -898,21 +943,74 @@ class Gg20Pipeline:
         R = _new(self.ctx, B, 16) if want_R else None
         return r, s, recid, status, R
 
-    def submit(self, nonces, keyset=None, want_R=False):
+    def submit(self, nonces, keyset=None, want_R=False, sigset=None):
+        """sigset: device int32 [batch], the signer set of every session (mpe_gg20_pipeline_submit_sets)"""
         r, s, recid, status, R = self._outs(want_R)
         nn = _struct(N_.Gg20Nonces, nonces)
         t = C.c_uint64(0)
-        N_.check(N_.lib.mpe_gg20_pipeline_submit(self.h, _ptr(keyset), C.byref(nn), _ptr(r), _ptr(s), _ptr(recid), _ptr(R), _ptr(status), self.ctx.stream(),
-                                                 C.byref(t)), "mpe_gg20_pipeline_submit")
-        self._keep[t.value] = (nonces, keyset, r, s, recid, status, R)
+        if sigset is None:
+            N_.check(N_.lib.mpe_gg20_pipeline_submit(self.h, _ptr(keyset), C.byref(nn), _ptr(r), _ptr(s), _ptr(recid), _ptr(R), _ptr(status),
+                                                     self.ctx.stream(), C.byref(t)), "mpe_gg20_pipeline_submit")
+        else:
+            N_.check(N_.lib.mpe_gg20_pipeline_submit_sets(self.h, _ptr(keyset), _ptr(sigset), C.byref(nn), _ptr(r), _ptr(s), _ptr(recid), _ptr(R),
+                                                          _ptr(status), self.ctx.stream(), C.byref(t)), "mpe_gg20_pipeline_submit_sets")
+        self._keep[t.value] = ((nonces, sigset), keyset, r, s, recid, status, R)
         return t.value
 
-    def submit_seeded(self, seed, batch_counter, msg, keyset=None, want_R=False):
+    def submit_seeded(self, seed, batch_counter, msg, keyset=None, want_R=False, sigset=None):
         r, s, recid, status, R = self._outs(want_R)
         t = C.c_uint64(0)
-        N_.check(N_.lib.mpe_gg20_pipeline_submit_seeded(self.h, _ptr(keyset), _seed(seed), int(batch_counter), _ptr(msg), _ptr(r), _ptr(s), _ptr(recid),
-                                                        _ptr(R), _ptr(status), self.ctx.stream(), C.byref(t)), "mpe_gg20_pipeline_submit_seeded")
-        self._keep[t.value] = (msg, keyset, r, s, recid, status, R)
+        if sigset is None:
+            N_.check(N_.lib.mpe_gg20_pipeline_submit_seeded(self.h, _ptr(keyset), _seed(seed), int(batch_counter), _ptr(msg), _ptr(r), _ptr(s),
+                                                            _ptr(recid), _ptr(R), _ptr(status), self.ctx.stream(), C.byref(t)),
+                     "mpe_gg20_pipeline_submit_seeded")
+        else:
+            N_.check(N_.lib.mpe_gg20_pipeline_submit_seeded_sets(self.h, _ptr(keyset), _ptr(sigset), _seed(seed), int(batch_counter), _ptr(msg), _ptr(r),
+                                                                 _ptr(s), _ptr(recid), _ptr(R), _ptr(status), self.ctx.stream(), C.byref(t)),
+                     "mpe_gg20_pipeline_submit_seeded_sets")
+        self._keep[t.value] = ((msg, sigset), keyset, r, s, recid, status, R)
+        return t.value
+
+    # ---- the presig engine: slots come from the pool's free list (or the caller names them) and are marked used at submit; wait()
+    # gives back the rows whose status is non-zero
+    def _presig_slots(self, slots):
+        if self.pool is None:
+            raise N_.MpeError("Gg20Pipeline: submit_presig needs an engine made with pool=")
+        mine = slots is None
+        if mine:
+            slots = self.pool._take(self.batch)
+        d_slot = self.pool._slots(slots)
+        if d_slot.numel() != self.batch:
+            raise ValueError("submit_presig: one slot per session")
+        h_slot = d_slot.cpu().numpy()
+        fresh = [int(x) for x in h_slot if 0 <= x < self.pool.capacity and int(x) not in self.pool._used]     # what a failed row hands back
+        self.pool._used.update(fresh)
+        return d_slot, h_slot, fresh, torch.full((self.batch,), -1, dtype=torch.int32, device=self.ctx.device)
+
+    def submit_presig(self, nonces, slots=None, keyset=None, sigset=None):
+        """the offline stage of one batch into `slots` (default: free slots of the pool); wait(ticket) -> (usable slots, status)"""
+        d_slot, h_slot, fresh, status = self._presig_slots(slots)
+        nn = _struct(N_.Gg20Nonces, _no_msg(self.ctx, nonces))
+        t = C.c_uint64(0)
+        try:
+            N_.check(N_.lib.mpe_gg20_pipeline_submit_presig(self.h, _ptr(keyset), _ptr(sigset), C.byref(nn), _ptr(d_slot), _ptr(status),
+                                                            self.ctx.stream(), C.byref(t)), "mpe_gg20_pipeline_submit_presig")
+        except N_.MpeError:
+            self.pool._used.difference_update(fresh)
+            raise
+        self._keep[t.value] = ((nonces, sigset, d_slot), keyset, h_slot, fresh, None, status, None)
+        return t.value
+
+    def submit_presig_seeded(self, seed, batch_counter, slots=None, keyset=None, sigset=None):
+        d_slot, h_slot, fresh, status = self._presig_slots(slots)
+        t = C.c_uint64(0)
+        try:
+            N_.check(N_.lib.mpe_gg20_pipeline_submit_presig_seeded(self.h, _ptr(keyset), _ptr(sigset), _seed(seed), int(batch_counter), _ptr(d_slot),
+                                                                   _ptr(status), self.ctx.stream(), C.byref(t)), "mpe_gg20_pipeline_submit_presig_seeded")
+        except N_.MpeError:
+            self.pool._used.difference_update(fresh)
+            raise
+        self._keep[t.value] = ((sigset, d_slot), keyset, h_slot, fresh, None, status, None)
         return t.value
 
     def flush(self):
@@ -934,11 +1032,19 @@ class Gg20Pipeline:
     def wait(self, ticket, want_R=False, check=True):
         """blocks until the batch is complete; returns (r, s, recid, status[, R]) and forgets the ticket's tensors.  A batch whose PASS
         failed raises MpeError (check=True) or returns its arrays — status = MPE_GG20_STATUS_PASS_FAILED(rc), no signature — with
-        check=False"""
+        check=False.  A presig engine returns (usable slots [batch] numpy int32, -1 where the row's status is non-zero; status) and
+        hands the slots of those rows back to the pool's free list, also when it raises."""
         rc = N_.lib.mpe_gg20_pipeline_wait(self.h, ticket)
         if ticket not in self._keep:
             N_.check(rc if rc != N_.MPE_OK else N_.MPE_E_ARG, "mpe_gg20_pipeline_wait (unknown ticket)")
         _, _, r, s, recid, status, R = self._keep.pop(ticket)
+        if self.pool is not None:             # a presig ticket: r = the slots as submitted, s = those the submit marked used
+            h_slot, fresh, st = r, set(s), status.cpu().numpy()
+            self.pool._used.difference_update(int(x) for x in h_slot[st != 0] if int(x) in fresh)
+            self.pool.last_status = st
+            if check:
+                N_.check(rc, "mpe_gg20_pipeline_wait")
+            return np.where(st == 0, h_slot, -1).astype(np.int32), status
         if check:
             N_.check(rc, "mpe_gg20_pipeline_wait")
         return (r, s, recid, status, R) if want_R else (r, s, recid, status)
