@@ -385,6 +385,7 @@ typedef struct {
  * rules are curv's (recalled): sample(bits) = from_bytes_be(ceil(bits/8) bytes) >> (8 ceil(bits/8) - bits);
  * sample_below(u) = repeat sample(bit_length(u)) until < u (every attempt takes fresh bytes).
  * A (seed, stream_id) pair must never be used twice.  h_seed32: HOST pointer to 32 bytes.
+ * (The sealed records below have the same kind of contract: a (wrapping key, nonce_hi) pair must never be used twice.)
  *   mpe_sample_bits    d_out [batch][out_words] = BigInt::sample(bits)
  *   mpe_sample_below   d_out = sample_below(bound row d_bound_idx[i] of d_bound [nbounds][bound_words]; NULL index: row 0 when
  *                      nbounds == 1, else row i); flags: MPE_SAMPLE_NONZERO rejects 0, MPE_SAMPLE_PLUS_ONE returns 1 + the draw
@@ -566,6 +567,9 @@ int mpe_gg20_session_fault_inject(mpe_gg20_session* sess, int step, uint32_t par
  *       | [11] key-set index | [12..27] y (x[8] | y[8]) | then per local party k_i [8] | sigma_i [8] | R [16]
  *     This layout is this library's own: the reference derives no `Serialize` for `CompletedOfflineStage`, there is no byte parity to
  *     claim.  A record holds k_i in the clear: importing one record twice, or into two pools, is the nonce reuse the slots prevent.
+ *     Sealing a record (mpe_gg20_sealed_presig_export / _import below) closes DISCLOSURE and FORGERY: k_i leaves the device
+ *     encrypted, and an edited record, or one sealed under another wallet's wrapping key, is refused.  It does not close REPLAY: a
+ *     sealed record imports as often as it is presented, and keeping it from being presented twice stays the caller's duty.
  * mpe_gg20_presig_discard   READY, SIGNED or EMPTY -> EMPTY with the wipe (a slot that a running call on another stream holds BUSY is
  *     left to that call).
  * A slot remembers the signer set its session signed with (mpe_gg20_session_create_sets; set 0 otherwise) beside the key set: export
@@ -612,6 +616,66 @@ int mpe_gg20_presig_pool_audit(mpe_gg20_presig_pool* pool, int64_t* h_out, void*
  * verify fails; zero outputs unless status 0.  d_status may be NULL. */
 int mpe_gg20_sign_online(mpe_gg20_presig_pool* pool, int count, const int32_t* d_slot, const uint32_t* d_msg, uint32_t* d_r,
                                 uint32_t* d_s, int32_t* d_recid, int32_t* d_status, void* stream);
+
+/* ---- sealed records: presignatures and key shares leave the device encrypted ------------------------------------------------
+ * ChaCha20-Poly1305 exactly as RFC 8439 §2.8 defines it, on the device, under a WRAPPING KEY: 32 bytes from the operator's KMS or
+ * HSM — the one secret the host handles.  mpe_wrap_key_create copies them (h_key32: HOST pointer) into device memory the object owns;
+ * _destroy zeroes that memory before it frees it (and waits for the device: calls on any stream may still read the key).
+ *     The SEALED ROW (this library's own layout, little-endian 32-bit words taken as their byte image): words + 10 words for a
+ *     payload of `words` words, 1 <= words <= MPE_SEAL_MAX_WORDS:
+ *       [0] MPE_SEAL_MAGIC (bytes "MPS1") | [1] kind | [2] words | [3..5] nonce = (row index within the call, low 32 bits of nonce_hi,
+ *       high 32 bits) — ChaCha20's state[13..15] | [6 .. 6+words) ciphertext | [6+words .. 10+words) Poly1305 tag
+ *     AAD = words [0..2] as 12 bytes, so kind and length are authenticated; the one-time Poly1305 key is the first 32 bytes of block 0,
+ *     the payload is XORed with blocks 1, 2, ...  Kinds: MPE_SEAL_KIND_PRESIG (1) a presignature record, MPE_SEAL_KIND_KEYSHARE (2) a
+ *     GG20 key share, >= MPE_SEAL_KIND_USER (16) the caller's own rows.
+ * nonce_hi: a (wrapping key, nonce_hi) pair must NEVER be used twice — the caller's contract, like the sampler's (seed, stream_id):
+ *     two calls that seal under the same pair encrypt their rows with the same keystream and MAC them with the same one-time keys.
+ *     64 random bits per call, or a counter kept with the key, both do.
+ * mpe_seal      d_plain [count][words] -> d_sealed [count][words + 10].
+ * mpe_unseal    d_sealed -> d_plain [count][words], d_status [count] (may be NULL): 0, or MPE_SEAL_REFUSED (841) for a row whose magic,
+ *     kind, length or tag does not match.  A row is authenticated before it is decrypted; the tag is compared without an early exit; a
+ *     refused row's plaintext row is all zero — unauthenticated plaintext is never written.
+ *     The generic pair takes kinds >= MPE_SEAL_KIND_USER only: kinds 1 and 2 are MPE_E_ARG, so that a sealed presignature or key share
+ *     is not turned back into clear words through it.
+ * mpe_poly1305  the one-time-key MAC on its own: d_key [count][8] (r [4] | s [4]), d_msg [count][msg_bytes] bytes, d_tag [count][4].
+ * mpe_gg20_sealed_presig_export / _import: mpe_gg20_presig_export / _import with the record (kind 1) sealed, rows of
+ *     mpe_gg20_sealed_presig_words(pool) = record words + 10; the same state transitions and row statuses.  A row that exports nothing
+ *     (831, 833) gets an all-zero sealed row.  Import AUTHENTICATES BEFORE IT CLAIMS: a row that fails authentication reports 841 and
+ *     its slot stays EMPTY and untouched; an authenticated record is then judged by import's own rules (832, 834).  The clear records
+ *     exist only in a stage inside the pool's context's workspace (counted by mpe_ctx_scratch_audit), which the same call zeroes in
+ *     stream order: after the call no device buffer outside the pool holds a clear record.  What sealing closes and what it does not:
+ *     see mpe_gg20_presig_import above.
+ * mpe_gg20_keyshare_seal: rows x [8] | p [32] | q [32] = MPE_GG20_KEYSHARE_WORDS (72) payload words, kind 2, gathered from d_x
+ *     [count][8], d_p, d_q [count][32] -> d_sealed [count][82]: key generation seals its shares before anything is copied out.
+ * mpe_gg20_keys_create_sealed: mpe_gg20_keys_create_sets with d_x, d_p, d_q replaced by the wrapping key and d_sealed_shares
+ *     [nkeysets][n_own][82]: unseals into device memory of its own, builds the object through the existing path and zeroes the clear
+ *     rows.  Any refused row fails the call (MPE_E_ARG) and creates no object.  Synchronises the stream. */
+#define MPE_SEAL_MAGIC ((uint32_t)0x3153504du)
+#define MPE_SEAL_REFUSED ((int)841)
+#define MPE_SEAL_MAX_WORDS ((int)4096)
+#define MPE_SEAL_KIND_PRESIG ((uint32_t)1)
+#define MPE_SEAL_KIND_KEYSHARE ((uint32_t)2)
+#define MPE_SEAL_KIND_USER ((uint32_t)16)
+#define MPE_GG20_KEYSHARE_WORDS ((int)72)
+typedef struct mpe_wrap_key mpe_wrap_key;
+int mpe_wrap_key_create(mpe_ctx* ctx, const uint8_t* h_key32, mpe_wrap_key** out);
+int mpe_wrap_key_destroy(mpe_wrap_key* key);
+int mpe_seal(mpe_ctx* ctx, const mpe_wrap_key* key, uint32_t kind, int count, int words, const uint32_t* d_plain, uint64_t nonce_hi,
+             uint32_t* d_sealed, void* stream);
+int mpe_unseal(mpe_ctx* ctx, const mpe_wrap_key* key, uint32_t kind, int count, int words, const uint32_t* d_sealed, uint32_t* d_plain,
+               int32_t* d_status, void* stream);
+int mpe_poly1305(mpe_ctx* ctx, int count, const uint32_t* d_key, const uint8_t* d_msg, size_t msg_bytes, uint32_t* d_tag, void* stream);
+int mpe_gg20_sealed_presig_words(const mpe_gg20_presig_pool* pool);
+int mpe_gg20_sealed_presig_export(mpe_gg20_presig_pool* pool, const mpe_wrap_key* key, int count, const int32_t* d_slot, uint64_t nonce_hi,
+                                  uint32_t* d_sealed, int32_t* d_status, void* stream);
+int mpe_gg20_sealed_presig_import(mpe_gg20_presig_pool* pool, const mpe_wrap_key* key, int count, const int32_t* d_slot,
+                                  const uint32_t* d_sealed, int32_t* d_status, void* stream);
+int mpe_gg20_keyshare_seal(mpe_ctx* ctx, const mpe_wrap_key* key, int count, const uint32_t* d_x, const uint32_t* d_p, const uint32_t* d_q,
+                           uint64_t nonce_hi, uint32_t* d_sealed, void* stream);
+int mpe_gg20_keys_create_sealed(mpe_ctx* ctx, int t, int n, int n_signers, int n_sets, const int32_t* h_sets, int nkeysets, int n_own,
+                                const int32_t* h_own, const mpe_wrap_key* key, const uint32_t* d_sealed_shares, const uint32_t* d_N,
+                                const uint32_t* d_Nt, const uint32_t* d_h1, const uint32_t* d_h2, const uint32_t* d_y, const uint32_t* d_X,
+                                mpe_gg20_keys** out, void* stream);
 
 /* ---- identifiable abort: src/protocols/multi_party_ecdsa/gg_2020/blame.rs ---------------------------------------- */
 /* Every signer has opened the values the failing phase used; the functions re-derive the public ciphertexts from the

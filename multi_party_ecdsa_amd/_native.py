@@ -30,6 +30,13 @@ def gg20_status_pass_failed(rc):              # MPE_GG20_STATUS_PASS_FAILED(rc),
     return 9000 - rc
 
 
+# The sealed records' constants are TYPED macros in the header (`((uint32_t)16)`), which the generator's integer-constant rule
+# does not take; they are restated here and tests/test_seal_abi_cpu.py compares them with what a C compiler prints.
+SEAL_MAGIC, SEAL_REFUSED, SEAL_MAX_WORDS = 0x3153504D, 841, 4096
+SEAL_KIND_PRESIG, SEAL_KIND_KEYSHARE, SEAL_KIND_USER = 1, 2, 16
+GG20_KEYSHARE_WORDS = 72
+
+
 class MpeError(RuntimeError):
     pass
 

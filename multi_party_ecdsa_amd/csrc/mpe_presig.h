@@ -249,15 +249,18 @@ __global__ void __launch_bounds__(64) presig_export_kernel(View P, int count, co
 
 // import: EMPTY -> READY for a record that is this pool's (version, one of the key object's signer sets, local parties), names one of its key sets with that key
 // set's y, and holds values a healthy offline stage leaves: every R on the curve, 0 < k_i < q, sigma_i < q.  The record is judged before
-// the slot is claimed: a refused record leaves the slot as it was.
+// the slot is claimed: a refused record leaves the slot as it was.  refused (null for clear records): the sealed import's verdict on the
+// row's authentication (mpe_seal.h) — a non-zero word is the row's status, and the row goes no further.
 __global__ void __launch_bounds__(64) presig_import_kernel(View P, int count, const int32_t* __restrict__ d_slot, const uint32_t* __restrict__ y,
-                                                           const uint32_t* __restrict__ rec, int32_t* __restrict__ status) {
+                                                           const uint32_t* __restrict__ rec, int32_t* __restrict__ status,
+                                                           const int32_t* __restrict__ refused) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= count) return;
   const int slot = d_slot[g], W = REC_HEAD + REC_PARTY * P.L;
   const uint32_t* o = rec + (size_t)g * W;
   int code = 0, sigset = 0;
   if (slot < 0 || slot >= P.cap) code = MPE_GG20_PRESIG_RECORD_RANGE;
+  else if (refused && refused[g]) code = refused[g];
   else {
     int set = -1;
     for (int k = 0; k < P.nsets; ++k) if (P.masks[k] == o[1]) set = k;
@@ -477,7 +480,7 @@ int mpe_gg20_presig_import(mpe_gg20_presig_pool* p, int count, const int32_t* d_
   if (!p || count < 0 || (count && (!d_slot || !d_rec))) return MPE_E_ARG;
   if (!count) return MPE_OK;
   hipLaunchKernelGGL(mpe::psg::presig_import_kernel, dim3(mpe::blocks_for(count, 64)), dim3(64), 0, (hipStream_t)stream, p->v, count, d_slot,
-                     p->K->y, d_rec, d_status);
+                     p->K->y, d_rec, d_status, (const int32_t*)nullptr);
   return mpe::psg::launched("presig_import_kernel");
 }
 

@@ -461,9 +461,14 @@ class Gg20Keys:
     y [K,16], X [K*n,16] (and optionally N [K*n,64], else p*q).  own: the party indices whose SECRETS (x, p, q) this
     object gets (default: all — the Simulation harness); the other parties' rows of x, p, q never leave the host.
     signer_sets=[[...], ...] (instead of `signers`): one object that signs for several quorums of the wallet
-    (mpe_gg20_keys_create_sets); a session names its set by its index in this list (`sigset=`), set 0 where none is named."""
+    (mpe_gg20_keys_create_sets); a session names its set by its index in this list (`sigset=`), set 0 where none is named.
+    sealed_shares, wrap: the secrets as sealed key shares [K*n, 82] (numpy uint32 or device int32, what gg20_keygen(..., wrap=) returns)
+    under the WrapKey `wrap`, instead of x, p, q in `arrays` (which then needs N): they are unsealed on the device
+    (mpe_gg20_keys_create_sealed) and no clear secret passes through the host."""
 
-    def __init__(self, ctx, t, n, signers, arrays, own=None, nkeysets=1, signer_sets=None):
+    def __init__(self, ctx, t, n, signers, arrays, own=None, nkeysets=1, signer_sets=None, sealed_shares=None, wrap=None):
+        if (sealed_shares is None) != (wrap is None):
+            raise ValueError("Gg20Keys: sealed_shares and wrap go together")
         if signer_sets is None:
             signer_sets = [list(signers)]
         elif signers is not None and [int(x) for x in signers] != [int(x) for x in signer_sets[0]]:
@@ -473,21 +478,35 @@ class Gg20Keys:
         self.ctx, self.t, self.n, self.S, self.K = ctx, t, n, len(signers), nkeysets
         own = list(range(n)) if own is None else sorted(int(a) for a in own)
         self.own = own
-        a = {f: np.ascontiguousarray(arrays[f]) for f in ("x", "p", "q", "Nt", "h1", "h2", "y", "X")}
+        sealed = sealed_shares is not None
+        a = {f: np.ascontiguousarray(arrays[f]) for f in (() if sealed else ("x", "p", "q")) + ("Nt", "h1", "h2", "y", "X")}
         if "N" in arrays and arrays["N"] is not None:
             a["N"] = np.ascontiguousarray(arrays["N"])
+        elif sealed:
+            raise ValueError("Gg20Keys: sealed shares need arrays['N']")
         else:
             ps, qs = words_to_ints(a["p"]), words_to_ints(a["q"])
             a["N"] = ints_to_words([p_ * q_ for p_, q_ in zip(ps, qs)], 64)
         rows = [kk * n + o for kk in range(nkeysets) for o in own]
         h = {f: a[f] for f in ("N", "Nt", "h1", "h2", "y", "X")}
-        for f in ("x", "p", "q"):
+        for f in (() if sealed else ("x", "p", "q")):
             h[f] = np.ascontiguousarray(a[f][rows])
         self.d = {f: torch.from_numpy(h[f].view(np.int32)).to(ctx.device) for f in h}
+        if sealed:
+            sh = sealed_shares if torch.is_tensor(sealed_shares) else torch.from_numpy(np.ascontiguousarray(sealed_shares).view(np.int32))
+            self.d["sealed"] = sh.to(ctx.device)[torch.tensor(rows, device=ctx.device)].contiguous()
         ow = (C.c_int32 * len(own))(*own)
         hd = C.c_void_p()
-        dev = [_ptr(self.d[f]) for f in ("x", "p", "q", "N", "Nt", "h1", "h2", "y", "X")]
-        if len(self.signer_sets) == 1:
+        pub = [_ptr(self.d[f]) for f in ("N", "Nt", "h1", "h2", "y", "X")]
+        dev = ([wrap.h, _ptr(self.d["sealed"])] if sealed else [_ptr(self.d[f]) for f in ("x", "p", "q")]) + pub
+        if sealed:
+            flat = [x for s in self.signer_sets for x in s]
+            sg = (C.c_int32 * len(flat))(*flat)
+            if len(flat) != len(self.signer_sets) * self.S:
+                raise ValueError("every signer set of a key object has the same number of signers")
+            N_.check(N_.lib.mpe_gg20_keys_create_sealed(ctx.h, t, n, self.S, len(self.signer_sets), sg, nkeysets, len(own), ow, *dev, C.byref(hd),
+                                                        ctx.stream()), "mpe_gg20_keys_create_sealed")
+        elif len(self.signer_sets) == 1:
             sg = (C.c_int32 * len(signers))(*signers)
             N_.check(N_.lib.mpe_gg20_keys_create(ctx.h, t, n, len(signers), sg, nkeysets, len(own), ow, *dev, C.byref(hd), ctx.stream()),
                      "mpe_gg20_keys_create")
@@ -644,6 +663,75 @@ def gg20_sign(ctx, keys, nonces, B, dedup_verify=False, chunk=0, want_R=False, k
     return (r, s, recid, status, R) if want_R else (r, s, recid, status)
 
 
+class WrapKey:
+    """A wrapping key for sealed records (`mpe_wrap_key`): 32 bytes from the operator's KMS or HSM, copied into device memory the
+    object owns and zeroed there when it is closed.  Every sealing call needs a `nonce_hi` that is never used twice with this key:
+    unless one is given, 64 fresh random bits (`secrets.randbits`) per call."""
+
+    def __init__(self, ctx, key_bytes):
+        key_bytes = bytes(key_bytes)
+        if len(key_bytes) != 32:
+            raise ValueError("WrapKey: 32 bytes")
+        self.ctx = ctx
+        h = C.c_void_p()
+        N_.check(N_.lib.mpe_wrap_key_create(ctx.h, key_bytes, C.byref(h)), "mpe_wrap_key_create")
+        self.h = h
+
+    @staticmethod
+    def nonce(nonce_hi=None):
+        import secrets
+        return C.c_uint64(secrets.randbits(64) if nonce_hi is None else int(nonce_hi))
+
+    def close(self):
+        if self.h:
+            N_.lib.mpe_wrap_key_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def seal(ctx, wrap, kind, d_plain, nonce_hi=None):
+    """caller rows (kind >= 16): d_plain [count, words] device int32 -> sealed rows [count, words + 10] (mpe_seal)"""
+    d_plain = d_plain.contiguous()
+    count, words = d_plain.shape
+    out = torch.empty((count, words + 10), dtype=torch.int32, device=ctx.device)
+    N_.check(N_.lib.mpe_seal(ctx.h, wrap.h, int(kind), count, words, _ptr(d_plain), WrapKey.nonce(nonce_hi), _ptr(out), ctx.stream()), "mpe_seal")
+    return out
+
+
+def unseal(ctx, wrap, kind, d_sealed):
+    """sealed rows [count, words + 10] -> (plain [count, words], status [count]): 841 and an all-zero row where a row is refused"""
+    d_sealed = d_sealed.contiguous()
+    count, words = d_sealed.shape[0], d_sealed.shape[1] - 10
+    plain = torch.empty((count, words), dtype=torch.int32, device=ctx.device)
+    status = torch.empty((count,), dtype=torch.int32, device=ctx.device)
+    N_.check(N_.lib.mpe_unseal(ctx.h, wrap.h, int(kind), count, words, _ptr(d_sealed), _ptr(plain), _ptr(status), ctx.stream()), "mpe_unseal")
+    return plain, status
+
+
+def poly1305(ctx, d_key, d_msg):
+    """the one-time-key MAC on its own: d_key [count, 8] int32 (r | s), d_msg [count, bytes] uint8 -> tags [count, 4] int32"""
+    d_key, d_msg = d_key.contiguous(), d_msg.contiguous()
+    count = d_key.shape[0]
+    tag = torch.empty((count, 4), dtype=torch.int32, device=ctx.device)
+    N_.check(N_.lib.mpe_poly1305(ctx.h, count, _ptr(d_key), _ptr(d_msg), d_msg.shape[1], _ptr(tag), ctx.stream()), "mpe_poly1305")
+    return tag
+
+
+def keyshare_seal(ctx, wrap, d_x, d_p, d_q, nonce_hi=None):
+    """x [count, 8], p, q [count, 32] (device int32) -> sealed key shares [count, 82] (mpe_gg20_keyshare_seal)"""
+    count = d_x.shape[0]
+    d_x, d_p, d_q = d_x.contiguous(), d_p.contiguous(), d_q.contiguous()        # (held until the call is queued)
+    out = torch.empty((count, N_.GG20_KEYSHARE_WORDS + 10), dtype=torch.int32, device=ctx.device)
+    N_.check(N_.lib.mpe_gg20_keyshare_seal(ctx.h, wrap.h, count, _ptr(d_x), _ptr(d_p), _ptr(d_q), WrapKey.nonce(nonce_hi), _ptr(out), ctx.stream()),
+             "mpe_gg20_keyshare_seal")
+    return out
+
+
 class PresigPool:
     """Device-resident presignatures in single-use slots (`mpe_gg20_presig_*`): `CompletedOfflineStage` of `capacity` sessions for the
     local parties `local` (signer ordinals), kept until the message arrives.  The C-ABI is mechanism only; this object owns the POLICY:
@@ -660,6 +748,7 @@ class PresigPool:
         self.h = h
         self.capacity = N_.lib.mpe_gg20_presig_pool_capacity(h)
         self.record_words = N_.lib.mpe_gg20_presig_record_words(h)
+        self.sealed_words = N_.lib.mpe_gg20_sealed_presig_words(h)
         self._used = set()                       # slots the free list has handed out (or the caller named) and not got back
         self._pending = []                       # (slots, device status, rows-per-slot) of calls whose freed slots are not yet counted
         self.last_status = None                  # numpy row statuses of the last deposit / import_
@@ -753,18 +842,24 @@ class PresigPool:
         self._pending.append((d_slot, status))              # 0 and 701 emptied the slot, 811 / 812 did not
         return r, s, recid, status
 
-    def export(self, slots):
-        """READY slots -> (records [count, record_words], status [count]); the slots are EMPTY afterwards, the records the only copy"""
+    def export(self, slots, wrap=None, nonce_hi=None):
+        """READY slots -> (records [count, record_words], status [count]); the slots are EMPTY afterwards, the records the only copy.
+        wrap (a WrapKey): the records leave sealed, [count, sealed_words] (mpe_gg20_sealed_presig_export)"""
         d_slot = self._slots(slots)
         count = d_slot.numel()
-        rec = torch.empty((count, self.record_words), dtype=torch.int32, device=self.ctx.device)
+        rec = torch.empty((count, self.record_words if wrap is None else self.sealed_words), dtype=torch.int32, device=self.ctx.device)
         status = torch.empty((count,), dtype=torch.int32, device=self.ctx.device)
-        N_.check(N_.lib.mpe_gg20_presig_export(self.h, count, _ptr(d_slot), _ptr(rec), _ptr(status), self.ctx.stream()), "mpe_gg20_presig_export")
+        if wrap is None:
+            N_.check(N_.lib.mpe_gg20_presig_export(self.h, count, _ptr(d_slot), _ptr(rec), _ptr(status), self.ctx.stream()), "mpe_gg20_presig_export")
+        else:
+            N_.check(N_.lib.mpe_gg20_sealed_presig_export(self.h, wrap.h, count, _ptr(d_slot), WrapKey.nonce(nonce_hi), _ptr(rec), _ptr(status),
+                                                          self.ctx.stream()), "mpe_gg20_sealed_presig_export")
         self._pending.append((d_slot, status))
         return rec, status
 
-    def import_(self, records, slots=None):
-        """records [count, record_words] (device int32) -> free slots (or `slots`); returns the usable slots, -1 where refused"""
+    def import_(self, records, slots=None, wrap=None):
+        """records [count, record_words] (device int32) -> free slots (or `slots`); returns the usable slots, -1 where refused.
+        wrap (a WrapKey): the records are sealed rows [count, sealed_words]; a row that fails authentication is 841"""
         count = records.shape[0]
         mine = slots is None
         if mine:
@@ -772,8 +867,12 @@ class PresigPool:
             self._used.update(slots)
         d_slot = self._slots(slots)
         status = torch.empty((count,), dtype=torch.int32, device=self.ctx.device)
-        N_.check(N_.lib.mpe_gg20_presig_import(self.h, count, _ptr(d_slot), _ptr(records.contiguous()), _ptr(status), self.ctx.stream()),
-                 "mpe_gg20_presig_import")
+        if wrap is None:
+            N_.check(N_.lib.mpe_gg20_presig_import(self.h, count, _ptr(d_slot), _ptr(records.contiguous()), _ptr(status), self.ctx.stream()),
+                     "mpe_gg20_presig_import")
+        else:
+            N_.check(N_.lib.mpe_gg20_sealed_presig_import(self.h, wrap.h, count, _ptr(d_slot), _ptr(records.contiguous()), _ptr(status),
+                                                          self.ctx.stream()), "mpe_gg20_sealed_presig_import")
         return self._filled(d_slot.cpu().numpy(), status.cpu().numpy(), not mine)
 
     def discard(self, slots):
@@ -1319,7 +1418,7 @@ def keygen_verify_round3(ctx, n_parties, d_commits, d_pk, d_R, d_z, want_xi=Fals
 KEYGEN_MATERIAL_FIELDS = ("p", "q", "pt", "qt", "h1", "xi")        # rows [B*n, 32] x 4, [B*n, 64] x 2
 
 
-def gg20_keygen(ctx, t, n, B, seed, counter=0, material=None, _fault=None, safe_primes=False, safe_ntilde=False):
+def gg20_keygen(ctx, t, n, B, seed, counter=0, material=None, _fault=None, safe_primes=False, safe_ntilde=False, wrap=None, nonce_hi=None):
     """`Keygen` (gg_2020/state_machine/keygen/rounds.rs) for B wallets in lock step with all n parties local, the counterpart of gg20_sign:
     a chain of C-ABI calls, rows = (wallet, party).
       material: None = mint the Paillier / N~ material on the device (streams counter | 0..5 << 56 of `seed`); or a dict of uint32
@@ -1333,7 +1432,9 @@ def gg20_keygen(ctx, t, n, B, seed, counter=0, material=None, _fault=None, safe_
                 before round 2, as Gg20Session.fault_inject does for signing (tests/test_keygen_deal_gpu.py walks the blame path with it).
     Returns a dict: ok [B] uint8 (all three verdicts of every party), bad1 [B] (provers of round 1), bad2 [B, n] (per receiving party,
     the dealers round 2 blames), bad3 [B] (round 3), commits [B n, t+1, 16], xi_commit [B n, 16], failures (sampler / prime search
-    give-ups) and `arrays`, the layout Gg20Keys takes with nkeysets = B."""
+    give-ups) and `arrays`, the layout Gg20Keys takes with nkeysets = B.
+      wrap:     a WrapKey: every party's x_i, p, q are sealed on the device (mpe_gg20_keyshare_seal) before anything is copied out;
+                `arrays` then has no x, p, q and the dict carries `sealed_shares` [B n, 82] (numpy uint32) for Gg20Keys(sealed_shares=)."""
     P, t1 = B * n, t + 1
     if counter >> 56:
         raise ValueError("counter < 2^56")
@@ -1392,10 +1493,18 @@ def gg20_keygen(ctx, t, n, B, seed, counter=0, material=None, _fault=None, safe_
     ok3, bad3, xi = keygen_verify_round3(ctx, n, commits, pk, R, z, want_xi=True)
     ok = ok1.reshape(B, n).bool().all(1) & ok2.reshape(B, n * n).bool().all(1) & ok3.reshape(B, n).bool().all(1)
     ctx.sync()
-    arrays = {f: _to_np_u32(v) for f, v in dict(x=x, p=p, q=q, N=N, Nt=Nt, h1=h1, h2=h2, X=pk).items()}
+    secret = dict(x=x, p=p, q=q)
+    sealed_shares = None
+    if wrap is not None:
+        sealed_shares = _to_np_u32(keyshare_seal(ctx, wrap, x, p, q, nonce_hi))
+        secret = {}
+    arrays = {f: _to_np_u32(v) for f, v in dict(secret, N=N, Nt=Nt, h1=h1, h2=h2, X=pk).items()}
     arrays["y"] = np.ascontiguousarray(_to_np_u32(ysum).reshape(B, n, 16)[:, 0])
-    return dict(ok=ok.to(torch.uint8), bad1=bad1, bad2=bad2.reshape(B, n), bad3=bad3, commits=commits, xi_commit=xi,
-                failures=int(sum(int(f.item()) for f in fails)), arrays=arrays)
+    out = dict(ok=ok.to(torch.uint8), bad1=bad1, bad2=bad2.reshape(B, n), bad3=bad3, commits=commits, xi_commit=xi,
+               failures=int(sum(int(f.item()) for f in fails)), arrays=arrays)
+    if wrap is not None:
+        out["sealed_shares"] = sealed_shares
+    return out
 
 
 # ---- identifiable abort (gg_2020/blame.rs) ----
