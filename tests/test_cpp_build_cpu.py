@@ -1,11 +1,13 @@
 """Without a GPU, without a compiler: tests/cpp_build.py — when a prebuilt C++ test program is handed back (temporary files), and the
-g++ arguments and dependencies of the three programs (written out: those of the three builders the helper replaced)."""
+g++ arguments and dependencies of the three programs (written out: those of the three builders the helper replaced); and the same for
+tests/hip_build.py, the recipe of the test-only device library tests/hip/libec_dev.so."""
 import os
 from collections import Counter
 
 import pytest
 
 import cpp_build
+import hip_build
 
 
 @pytest.mark.parametrize("case, want", [("prebuilt newest", True), ("same age", True), ("dependency newer", False), ("dependency missing", False),
@@ -42,3 +44,17 @@ def test_gxx_arguments_and_dependencies_are_those_of_the_replaced_builders(name,
         want_deps = [src, j("include", "mpecdsa.hpp"), j("include", "mpecdsa_hip.h"), lib]
     deps, cmd = cpp_build.recipe(name, exe)
     assert Counter(cmd) == Counter(want) and cmd[0] == "g++" and deps == want_deps
+
+
+def test_device_test_library_is_compiled_with_the_flags_of_the_product(tmp_path, monkeypatch):
+    import __graft_entry__ as entry
+    j = lambda *parts: os.path.join(hip_build.ROOT, *parts)
+    out, src = str(tmp_path / "libec_dev.so"), j("tests", "hip", "ec_dev.hip")
+    deps, cmd = hip_build.recipe(out)
+    assert cmd == ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", src, "-o", out]
+    assert deps == [src] + [j("multi_party_ecdsa_amd", "csrc", h) for h in ("mpe_fe.h", "mpe_sc.h", "mpe_jac.h", "mpe_ec.h", "mpe_small.h")] + [j("include", "mpecdsa_hip.h")]
+    assert all(os.path.exists(d) for d in deps)
+    monkeypatch.setattr(entry, "HIPCC_FLAGS", ["--offload-arch=gfx950", "-O1"])        # taken from __graft_entry__, not restated
+    assert hip_build.recipe(out)[1] == ["hipcc", "--offload-arch=gfx950", "-O1", "-shared", src, "-o", out]
+    # the library stays out of build/, which does not travel with the tree, and out of git
+    assert os.path.dirname(src) == j("tests", "hip") and hip_build.NAME.endswith(".so")

@@ -1,19 +1,35 @@
-"""The device field / point code (csrc/mpe_fe.h, csrc/mpe_jac.h) compiled for the HOST and fuzzed against Python
-integers and tests/pyref.py: the 10 x 26-bit lazy-reduction limb algorithms are checked at every magnitude the point
-formulas use, at the worst-case limb patterns, and through whole scalar multiplications (variable base, comb table,
-exceptional additions).  No GPU involved: the same header text is what hipcc compiles for gfx950."""
+"""The device field / scalar / point code (csrc/mpe_fe.h, mpe_sc.h, mpe_jac.h) compiled for the HOST and run over the case tables of
+tests/fe_cases.py against Python integers and tests/pyref.py: the 10 x 26-bit lazy-reduction limb algorithms at every magnitude the
+point formulas use and at the worst-case limb patterns, the scalar field at every ending of its reduction, and whole scalar
+multiplications (variable base, comb table, exceptional additions, negation, projective equality).  No GPU involved: this is the same
+header text hipcc compiles for gfx950, NOT the same code — tests/test_fe_gpu.py runs the same tables and the same checks on the device."""
 import ctypes
 import os
-import random
 import subprocess
 
 import pytest
 
+import fe_cases as T
 import pyref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P = R.P
-M26 = (1 << 26) - 1
+LAMBDA, BETA = T.LAMBDA, T.BETA
+
+# how fe_host.cpp takes each operation of fe_cases.OPS: i<n> an input column (pointer), v<n> an input column of one word by value,
+# o<n> an output column (pointer), r the int it returns (the only output column), n the call's arg (sch_reduce's width), t the comb table
+HOST_CALLS = {
+    "feh_mul": "i0 i1 o0 o1", "feh_sqr": "i0 o0 o1", "feh_weak": "i0 o0", "feh_normalize": "i0 o0", "feh_is_zero": "i0 r",
+    "feh_neg": "i0 v1 o0", "feh_from_words": "i0 o0", "feh_inv": "i0 o0", "feh_add": "i0 i1 o0", "feh_sub": "i0 i1 v2 o0",
+    "feh_mul_int": "i0 v1 o0", "feh_eq": "i0 i1 v2 r", "ech_mul": "i0 i1 o0", "ech_mul_w4": "i0 i1 o0", "ech_add": "i0 i1 o0",
+    "ech_add_jac": "i0 i1 i2 i3 o0", "ech_eq": "i0 i1 i2 r", "ech_eq_jac": "i0 i1 i2 i3 v4 r", "ech_on_curve": "i0 r",
+    "ech_neg": "i0 i1 v2 o0 o1", "ech_mul_comb": "i0 t o0", "sch_split": "i0 o0 o1 o2", "sch_reduce": "i0 n o0", "sch_mul": "i0 i1 o0",
+    "sch_inv": "i0 o0", "sch_add": "i0 i1 o0", "sch_sub": "i0 i1 o0", "sch_neg": "i0 o0",
+}
+
+
+def arr(vals, n):
+    return (ctypes.c_uint32 * n)(*vals)
 
 
 @pytest.fixture(scope="module")
@@ -28,194 +44,89 @@ def lib():
     return ctypes.CDLL(out)
 
 
-def arr(vals, n):
-    return (ctypes.c_uint32 * n)(*vals)
-
-
-def limbs_value(l):
-    return sum(int(v) << (26 * i) for i, v in enumerate(l))
-
-
-def words_value(w):
-    return sum(int(v) << (32 * i) for i, v in enumerate(w))
-
-
-def to_words(x, n=8):
-    return [(x >> (32 * i)) & 0xFFFFFFFF for i in range(n)]
-
-
-def rand_limbs(rng, m, mode):
-    """limbs of an element of magnitude m: n[0..8] <= 2 m (2^26 - 1), n[9] <= 2 m (2^22 - 1)"""
-    hi = [2 * m * M26] * 9 + [2 * m * ((1 << 22) - 1)]
-    if mode == "max":
-        return hi
-    if mode == "edge":
-        return [rng.choice([0, 1, h - 1, h, h // 2]) for h in hi]
-    return [rng.randrange(h + 1) for h in hi]
-
-
-def test_mul_sqr_all_magnitudes(lib):
-    rng = random.Random(1)
-    out, ol = arr([0] * 8, 8), arr([0] * 10, 10)
-    pairs = [(1, 1), (1, 3), (3, 3), (3, 6), (2, 6), (5, 5), (5, 3), (1, 32), (4, 8), (2, 16), (3, 2)]
-    for m1, m2 in pairs:
-        for mode in ["max", "edge", "rand", "rand", "rand", "edge", "rand"] * 6:
-            a, b = rand_limbs(rng, m1, mode), rand_limbs(rng, m2, mode if mode != "edge" else "rand")
-            lib.feh_mul(arr(a, 10), arr(b, 10), out, ol)
-            assert words_value(out) == limbs_value(a) * limbs_value(b) % P, (m1, m2, mode)
-            # the raw result is of magnitude 1 and congruent
-            assert all(v <= 2 * M26 for v in ol[:9]) and ol[9] <= 2 * ((1 << 22) - 1)
-            assert limbs_value(ol) % P == words_value(out)
-    for m in [1, 2, 3, 5]:
-        for mode in ["max", "edge", "rand", "rand", "edge", "rand"] * 8:
-            a = rand_limbs(rng, m, mode)
-            lib.feh_sqr(arr(a, 10), out, ol)
-            assert words_value(out) == limbs_value(a) ** 2 % P, (m, mode)
-            assert all(v <= 2 * M26 for v in ol[:9]) and ol[9] <= 2 * ((1 << 22) - 1)
-
-
-def test_normalize_weak_zero_neg(lib):
-    rng = random.Random(2)
-    out, ol = arr([0] * 8, 8), arr([0] * 10, 10)
-    specials = [0, 1, P - 1, P, P + 1, 2 * P, 2 * P - 1, (1 << 256) - 1, 1 << 256, (1 << 256) + (1 << 32) + 976, 3 * P, 31 * P]
-    for v in specials:
-        # the value spread over limbs in a few ways (canonical split, and with a heavy top limb)
-        l0 = [(v >> (26 * i)) & M26 for i in range(9)] + [v >> 234]
-        for l in [l0]:
-            if max(l) >= 1 << 32:
-                continue
-            lib.feh_normalize(arr(l, 10), out)
-            assert words_value(out) == v % P, hex(v)
-            assert lib.feh_is_zero(arr(l, 10)) == (1 if v % P == 0 else 0), hex(v)
-    for m in [1, 2, 3, 6, 10, 17, 31]:
-        for mode in ["max", "edge", "rand", "rand", "rand"] * 10:
-            a = rand_limbs(rng, m, mode)
-            lib.feh_normalize(arr(a, 10), out)
-            assert words_value(out) == limbs_value(a) % P
-            lib.feh_weak(arr(a, 10), ol)
-            assert limbs_value(ol) % P == limbs_value(a) % P
-            assert all(v <= M26 for v in ol[:9]) and ol[9] <= (1 << 22) + 63
-            assert lib.feh_is_zero(arr(a, 10)) == (1 if limbs_value(a) % P == 0 else 0)
-            if m < 31:
-                lib.feh_neg(arr(a, 10), m, ol)
-                assert (limbs_value(ol) + limbs_value(a)) % P == 0
-                hi = [2 * (m + 1) * M26] * 9 + [2 * (m + 1) * ((1 << 22) - 1)]
-                assert all(0 <= v <= h for v, h in zip(ol, hi))
-    # multiples of p at every magnitude are recognised as zero
-    for k in range(0, 60):
-        v = k * P
-        l = [(v >> (26 * i)) & M26 for i in range(9)] + [v >> 234]
-        assert lib.feh_is_zero(arr(l, 10)) == 1
-
-
-def test_words_roundtrip_and_inverse(lib):
-    rng = random.Random(3)
-    out, ol = arr([0] * 8, 8), arr([0] * 10, 10)
-    for v in [0, 1, P - 1, (1 << 255) + 12345, 0xDEADBEEF << 200] + [rng.randrange(P) for _ in range(50)]:
-        lib.feh_from_words(arr(to_words(v), 8), ol)
-        assert limbs_value(ol) == v and all(x <= M26 for x in ol)
-        lib.feh_normalize(ol, out)
-        assert words_value(out) == v
-        if v:
-            for k in [1, 2, 5]:
-                lk = [x * k for x in ol]
-                lib.feh_inv(arr(lk, 10), out)
-                assert words_value(out) * v * k % P == 1
-
-
-def pt_words(pt):
-    return [0] * 16 if pt is None else to_words(pt[0]) + to_words(pt[1])
-
-
-def words_pt(w):
-    x, y = words_value(w[:8]), words_value(w[8:])
-    return None if x == 0 and y == 0 else (x, y)
-
-
-def test_scalar_multiplication_and_additions(lib):
-    rng = random.Random(4)
-    out = arr([0] * 16, 16)
-    pts = [R.G, R.H2] + [R.ec_mul(rng.randrange(1, R.Q), R.G) for _ in range(6)]
-    ks = [0, 1, 2, 3, 15, 16, 17, R.Q - 1, R.Q - 2, (1 << 255), (1 << 256) - 1 - (1 << 256) % 1, 0x1111111111111111111111111111111111111111111111111111111111111111,
-          0xF0F0F0F0F0F0F0F0F0F0F0F0F0F0F0F0F0F0F0F0F0F0F0F0F0F0F0F0F0F0F0F0 % R.Q] + [rng.randrange(R.Q) for _ in range(12)]
-    for pt in pts[:4]:
-        for k in ks:
-            k %= R.Q
-            lib.ech_mul(arr(to_words(k), 8), arr(pt_words(pt), 16), out)
-            assert words_pt(out) == R.ec_mul(k, pt), hex(k)
-    # mixed additions incl. the exceptional cases: P + P, P + (-P), P + inf, inf + P
-    for a in pts[:4]:
-        for b in [a, R.ec_neg(a), None, pts[5], R.ec_mul(2, a)]:
-            lib.ech_add(arr(pt_words(a), 16), arr(pt_words(b), 16), out)
-            assert words_pt(out) == R.ec_add(a, b)
-            lib.ech_add(arr(pt_words(None), 16), arr(pt_words(b), 16), out)
-            assert words_pt(out) == b
-    # general Jacobian addition of two computed points, incl. equal, opposite and infinite operands
-    cases = [(3, pts[2], 5, pts[3]), (7, R.G, 7, R.G), (7, R.G, R.Q - 7, R.G), (0, R.G, 9, pts[4]), (9, pts[4], 0, R.G),
-             (0, R.G, 0, R.G), (2, R.G, 1, R.ec_mul(2, R.G))] + [(rng.randrange(R.Q), pts[2], rng.randrange(R.Q), pts[6]) for _ in range(6)]
-    for ka, pa, kb, pb in cases:
-        lib.ech_add_jac(arr(to_words(ka), 8), arr(pt_words(pa), 16), arr(to_words(kb), 8), arr(pt_words(pb), 16), out)
-        assert words_pt(out) == R.ec_add(R.ec_mul(ka, pa), R.ec_mul(kb, pb))
-    # projective equality
-    for k in [1, 2, 5, rng.randrange(R.Q)]:
-        q = R.ec_mul(k, pts[3])
-        assert lib.ech_eq(arr(to_words(k), 8), arr(pt_words(pts[3]), 16), arr(pt_words(q), 16)) == 3
-        assert lib.ech_eq(arr(to_words(k), 8), arr(pt_words(pts[3]), 16), arr(pt_words(R.ec_neg(q)), 16)) == 0
-        assert lib.ech_eq(arr(to_words(k), 8), arr(pt_words(pts[3]), 16), arr(pt_words(pts[4]), 16)) == 0
-    assert lib.ech_eq(arr(to_words(0), 8), arr(pt_words(R.G), 16), arr(pt_words(None), 16)) == 3
-    # curve membership
-    for pt in pts:
-        assert lib.ech_on_curve(arr(pt_words(pt), 16)) == 1
-        assert lib.ech_on_curve(arr(pt_words((pt[0], (pt[1] + 1) % P)), 16)) == 0
-        assert lib.ech_on_curve(arr(pt_words(((pt[0] + 1) % P, pt[1])), 16)) == 0
-
-
-def test_comb_tables(lib):
-    rng = random.Random(5)
-    out = arr([0] * 16, 16)
-    for base in [R.G, R.H2]:
+@pytest.fixture(scope="module")
+def comb(lib):
+    """the comb tables of G and base_point2, built by the host twin of ec_comb_build_kernel"""
+    tabs = []
+    for base in (R.G, R.H2):
         tab = (ctypes.c_uint32 * (64 * 15 * 20))()
-        lib.ech_comb_build(arr(pt_words(base), 16), tab)
-        # spot-check entries, then multiply
-        for w, d in [(0, 1), (0, 15), (1, 1), (63, 15), (31, 7)]:
-            e = tab[(w * 15 + d - 1) * 20:(w * 15 + d) * 20]
-            assert (limbs_value(e[:10]), limbs_value(e[10:])) == R.ec_mul(d * 16 ** w, base)
-        for k in [0, 1, 15, 16, R.Q - 1, 1 << 255 % R.Q, 0x0F0F0F0F0F0F0F0F0F0F0F0F0F0F0F0F0F0F0F0F0F0F0F0F0F0F0F0F0F0F0F0F] + [rng.randrange(R.Q) for _ in range(10)]:
-            k %= R.Q
-            lib.ech_mul_comb(arr(to_words(k), 8), tab, out)
-            assert words_pt(out) == R.ec_mul(k, base), hex(k)
+        lib.ech_comb_build(arr(T.pt_words(base), 16), tab)
+        tabs.append(tab)
+    return tabs
 
 
-def test_scalar_field(lib):
-    rng = random.Random(6)
-    Q = R.Q
-    out = arr([0] * 8, 8)
-    edge = [0, 1, 2, Q - 1, Q, Q + 1, (1 << 256) - 1, (1 << 255), (1 << 128) - 1, 1 << 128, Q >> 1]
-    # reductions of every width the kernels use (8 .. 90 words), incl. all-ones inputs and multiples of q
-    for n in [1, 5, 8, 9, 16, 24, 25, 64, 72, 88, 89, 90]:
-        vals = [0, (1 << (32 * n)) - 1, (Q * ((1 << (32 * n)) // Q)) if n >= 8 else 0, ((1 << (32 * n)) // Q) * Q - 1 if n >= 8 else 1]
-        vals += [rng.randrange(1 << (32 * n)) for _ in range(12)]
-        for v in vals:
-            lib.sch_reduce(arr(to_words(v, n), n), n, out)
-            assert words_value(out) == v % Q, (n, hex(v))
-    for a in edge:
-        for b in edge + [rng.randrange(1 << 256) for _ in range(3)]:
-            lib.sch_mul(arr(to_words(a % (1 << 256)), 8), arr(to_words(b % (1 << 256)), 8), out)
-            assert words_value(out) == (a % (1 << 256)) * (b % (1 << 256)) % Q
-    for _ in range(300):
-        a, b = rng.randrange(1 << 256), rng.randrange(1 << 256)
-        lib.sch_mul(arr(to_words(a), 8), arr(to_words(b), 8), out)
-        assert words_value(out) == a * b % Q
-    for a in [1, 2, Q - 1, Q - 2] + [rng.randrange(1, Q) for _ in range(20)]:
-        lib.sch_inv(arr(to_words(a), 8), out)
-        assert words_value(out) * a % Q == 1
+@pytest.fixture(scope="module")
+def run(lib, comb):
+    assert set(HOST_CALLS) == set(T.OPS)
+
+    def run(op, rows, arg=0):
+        wi, wo = T.OPS[op]
+        fn, spec, res = getattr(lib, op), HOST_CALLS[op].split(), []
+        for row in rows:
+            outs = [arr([0] * w, w) for w in wo]
+            args = []
+            for s in spec:
+                k = int(s[1:]) if len(s) > 1 else 0
+                if s[0] == "i":
+                    args.append(arr(row[k], len(row[k])))
+                    assert len(row[k]) == (wi[k] if wi[k] is not None else arg)
+                elif s[0] == "v":
+                    args.append(ctypes.c_uint32(row[k][0]))
+                elif s[0] == "o":
+                    args.append(outs[k])
+                elif s[0] == "n":
+                    args.append(ctypes.c_int(arg))
+                elif s[0] == "t":
+                    args.append(comb[arg])
+            ret = fn(*args)
+            res.append(([ret],) if "r" in spec else tuple(list(o) for o in outs))
+        return res
+    return run
 
 
-LAMBDA = 0x5363AD4CC05C30E0A5261C028812645A122E22EA20816678DF02967C1B23BD72
-BETA = 0x7AE96A2B657C07106E64479EAC3434E99CF0497512F58995C1396C28719501EE
+def test_mul_sqr_all_magnitudes(run):
+    T.check_mul_sqr(run)
 
 
-def test_glv_constants_and_split(lib):
+def test_normalize_weak_zero_neg(run):
+    T.check_normalize_weak_zero_neg(run)
+
+
+def test_words_roundtrip_and_inverse(run):
+    T.check_words_roundtrip_and_inverse(run)
+
+
+def test_add_sub_mul_int_eq_at_the_magnitudes_of_the_point_formulas(run):
+    T.check_fe_helpers(run)
+
+
+def test_scalar_multiplication_and_additions(run):
+    T.check_scalar_multiplication_and_additions(run)
+
+
+def test_negation_and_projective_equality(run):
+    T.check_neg_and_eq(run)
+
+
+def test_comb_tables(run, comb):
+    for g in (0, 1):
+        T.check_comb_entries(list(comb[g]), g)
+    T.check_comb_mul(run)
+
+
+def test_fold_model_reaches_every_ending_of_sc_reduce512():
+    T.check_fold_model()
+
+
+def test_scalar_field(run):
+    T.check_scalar_field(run)
+
+
+def test_scalar_add_sub_neg(run):
+    T.check_scalar_add_sub_neg(run)
+
+
+def test_glv_constants_and_split(run):
     """the endomorphism constants are re-derived here from the lattice basis; the device split is exact and 128-bit"""
     n, p = R.Q, R.P
     assert pow(LAMBDA, 3, n) == 1 and LAMBDA != 1 and pow(BETA, 3, p) == 1 and BETA != 1
@@ -228,30 +139,20 @@ def test_glv_constants_and_split(lib):
 
     def const(name):
         body = src[src.index(name + "[8] = {") + len(name) + 7:]
-        return words_value([int(t.strip().rstrip("u"), 16) for t in body[:body.index("}")].split(",")])
+        return T.words_value([int(t.strip().rstrip("u"), 16) for t in body[:body.index("}")].split(",")])
     assert const("GLV_LAMBDA") == LAMBDA and const("GLV_BETA") == BETA
     assert const("GLV_G1") == g1 and const("GLV_G2") == g2
     assert const("GLV_MB1") == (-b1) % n and const("GLV_MB2") == (-b2) % n
-    rng = random.Random(7)
-    r1, r2, neg = arr([0] * 8, 8), arr([0] * 8, 8), (ctypes.c_int * 2)()
-    ks = [0, 1, 2, n - 1, n - 2, n // 2, n // 2 + 1, LAMBDA, n - LAMBDA, LAMBDA + 1, (1 << 128), (1 << 128) - 1, (1 << 255)] + [rng.randrange(n) for _ in range(3000)]
-    for k in ks:
-        lib.sch_split(arr(to_words(k), 8), r1, r2, neg)
-        v1, v2 = words_value(r1), words_value(r2)
-        assert v1 < 1 << 128 and v2 < 1 << 128
-        assert ((-v1 if neg[0] else v1) + (-v2 if neg[1] else v2) * LAMBDA) % n == k
+    T.check_glv_split(run)
 
 
-def test_glv_ladder_matches_plain_ladder(lib):
-    rng = random.Random(8)
-    out, out2 = arr([0] * 16, 16), arr([0] * 16, 16)
-    n = R.Q
-    pts = [R.G, R.H2, R.ec_mul(rng.randrange(1, n), R.G)]
-    ks = [0, 1, 2, 15, 16, 17, 31, 32, 33, n - 1, n - 2, LAMBDA, n - LAMBDA, LAMBDA - 1, LAMBDA + 1, (LAMBDA * 16) % n, (LAMBDA * 17 + 16) % n,
-          (1 << 128) - 1, 1 << 128, 0x10842108421084210842108421084210 % n] + [rng.randrange(n) for _ in range(60)]
-    for pt in pts:
-        for k in ks:
-            lib.ech_mul(arr(to_words(k), 8), arr(pt_words(pt), 16), out)
-            lib.ech_mul_w4(arr(to_words(k), 8), arr(pt_words(pt), 16), out2)
-            assert list(out) == list(out2), hex(k)
-            assert words_pt(out) == R.ec_mul(k, pt), hex(k)
+def test_glv_ladder_matches_plain_ladder(run):
+    T.check_glv_ladder_matches_plain_ladder(run)
+
+
+def test_exceptional_kinds_one_call_each(run):
+    T.check_uniform(run, rows=1)                                  # (the device launches each as a whole wave of identical rows)
+
+
+def test_sha_rows_cover_every_length_and_field_shape():
+    T.check_sha_bigint_rows_cover_every_length()
