@@ -6,4 +6,8 @@ set -e
 cd "$(dirname "$0")"
 python -c 'import sys, __graft_entry__ as g; g.build_library(extra=sys.argv[1:], report=True)' "$@" || { echo "BUILD FAILED"; exit 1; }
 cp multi_party_ecdsa_amd/libmpecdsa_hip.so build/libmpecdsa_hip.so
-grep -E "Function Name|VGPRs:|Occupancy|VGPRs Spill" build/resource_usage.txt | sed 's/remark: [^ ]* *//' | paste - - - - | sed 's/\[-Rpass-analysis=kernel-resource-usage\]//g' | awk '{print $3, $5, $6, $9, $10, $13,$14,$15}'
+# one line per kernel: registers, scratch bytes per lane, waves per SIMD and what was spilled
+sed 's/remark: [^ ]* *//; s/ *\[-Rpass-analysis=kernel-resource-usage\]//' build/resource_usage.txt | awk '
+  /^Function Name:/ { name = $3 }  /^TotalSGPRs:/ { sgpr = $2 }  /^VGPRs:/ { vgpr = $2 }  /^ScratchSize/ { scratch = $3 }
+  /^Occupancy/ { occ = $3 }  /^SGPRs Spill:/ { sspill = $3 }
+  /^VGPRs Spill:/ { print name, "VGPRs:", vgpr, "SGPRs:", sgpr, "scratch:", scratch, "occupancy:", occ, "spills(SGPR/VGPR):", sspill "/" $3 }'

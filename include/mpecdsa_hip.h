@@ -467,6 +467,9 @@ int mpe_gg20_msg_words(int n_signers, int n, int round);
  *   92 (MPE_GG20_STATUS_BAD_SET, round 0) the session names no quorum this party signs in: d_sigset[b] is outside [0, n_sets), or the
  *      local party given by index is not a member of the session's set.  Checked on the device (the host never reads d_sigset); the
  *      party emits zero records and never signs
+ *   93 (MPE_GG20_STATUS_BAD_TWEAK, round 0) the session's tweak (mpe_gg20_session_create_tweaks) is not canonical (t >= q — the all-ones
+ *      tweak of a failed mpe_bip32_derive row is), or the child key y + t G is the point at infinity; the party emits zero records and
+ *      never signs, the other sessions of the batch are unaffected
  * with `bad_actors` (a bit mask over signer ordinals, the reference's `ErrorType::bad_actors`, gg_2020/mod.rs:23-27) set
  * for 401 (the peers whose decommitment is bad), 501 (the first failing prover) and 601 (every failing prover).
  * mpe_gg20_session_result: d_status, d_bad_actors, d_recid [n_local][batch]; d_r, d_s [n_local][batch][8] (after
@@ -474,6 +477,7 @@ int mpe_gg20_msg_words(int n_signers, int n, int round);
  * Destroying a session zeroes its state (k_i, gamma_i, w_i, sigma_i, ...). */
 #define MPE_GG20_STATUS_BAD_NONCE 91
 #define MPE_GG20_STATUS_BAD_SET 92
+#define MPE_GG20_STATUS_BAD_TWEAK ((int)93)
 typedef struct mpe_gg20_session mpe_gg20_session;
 int mpe_gg20_session_create(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, int n_local, const int32_t* h_local,
                             const int32_t* d_keyset, const mpe_gg20_nonces* nonces, int dedup_verify, mpe_gg20_session** out,
@@ -491,6 +495,24 @@ int mpe_gg20_session_create(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, 
 int mpe_gg20_session_create_sets(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, int n_local, const int32_t* h_local,
                                  const int32_t* d_keyset, const int32_t* d_sigset, int local_by_party, const mpe_gg20_nonces* nonces,
                                  int dedup_verify, mpe_gg20_session** out, void* stream);
+/* Sessions that sign for CHILD KEYS of their key set (non-hardened BIP32 derivation, mpe_bip32_derive): d_tweak [batch][8] (device,
+ * little-endian words, PUBLIC) = the tweak t_b of session b; the session signs for x + t_b, public key y + t_b G.  Adding t to every
+ * Shamir share moves the polynomial's constant term by t and nothing else, so x_i' = x_i + t, X_i' = X_i + t G, and of a signing
+ * session only w_i = lambda_i (x_i + t), g_w_vec[j] = g_w[j] + (lambda_j t) G and y change: Paillier keys, N~ statements, sampler bounds
+ * and every ladder stay.  The session copies the tweaks and owns two tables, y_b [batch][16] and g_w_b [batch][S][16], filled by one
+ * kernel here and at every re-arm ((S + 1) comb multiplications per session); d_tweak need not outlive the call.  NULL = no tweak:
+ * exactly mpe_gg20_session_create_sets, no table, the same launches.  A tweak that is not canonical, or whose child key is the point
+ * at infinity, stops the session's parties at round 0 with MPE_GG20_STATUS_BAD_TWEAK.  The tweak is bound at round 0 (sigma_i contains
+ * w_i'): a presignature made here belongs to its child key.
+ * NOT supported for a session with tweaks, each MPE_E_ARG with a mpe_last_error text: mpe_gg20_presig_deposit (the record keeps its
+ * layout; MPE_GG20_PRESIG_RECORD_VERSION stays 1) and mpe_gg20_session_blame6_state (the blame entry points take a key object and know
+ * no tweak).  The pipelined engines, mpe_gg20_presign_sets and the sharded exchange have no form that takes tweaks. */
+int mpe_gg20_session_create_tweaks(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, int n_local, const int32_t* h_local,
+                                   const int32_t* d_keyset, const int32_t* d_sigset, int local_by_party, const uint32_t* d_tweak,
+                                   const mpe_gg20_nonces* nonces, int dedup_verify, mpe_gg20_session** out, void* stream);
+/* d_y [batch][16]: the public key every session of the running batch signs for — its child key (zero where the tweak was refused), or
+ * its key set's y in a batch without tweaks. */
+int mpe_gg20_session_child_keys(const mpe_gg20_session* sess, uint32_t* d_y, void* stream);
 int mpe_gg20_session_destroy(mpe_gg20_session* sess, void* stream);
 /* The next batch of the same shape on the same object (a party process signs batch after batch: `SignManual::new` again
  * with fresh `SignKeys`, sign.rs:540-569): new sampled values (and key-set choice), state of the previous batch zeroed, rounds
@@ -504,6 +526,10 @@ int mpe_gg20_session_rearm(mpe_gg20_session* sess, const int32_t* d_keyset, cons
  * local parties' secrets were then checked against set 0 alone).  NULL = set 0 for all; mpe_gg20_session_rearm is that case. */
 int mpe_gg20_session_rearm_sets(mpe_gg20_session* sess, const int32_t* d_keyset, const int32_t* d_sigset, const mpe_gg20_nonces* nonces,
                                 void* stream);
+/* ... with the next batch's tweaks, for a session made by mpe_gg20_session_create_tweaks with a d_tweak (MPE_E_ARG otherwise: the
+ * session owns no tables).  NULL = no tweak for the next batch; mpe_gg20_session_rearm_sets is that case. */
+int mpe_gg20_session_rearm_tweaks(mpe_gg20_session* sess, const int32_t* d_keyset, const int32_t* d_sigset, const uint32_t* d_tweak,
+                                  const mpe_gg20_nonces* nonces, void* stream);
 /* Gives the running batch up (a peer vanished, a round call returned an error): the
  * nonce-derived state is wiped at once, every round entry point refuses, and mpe_gg20_session_rearm starts the next batch.  (A caller
  * that stops after the offline stage to sign later does not abort: mpe_gg20_presig_deposit moves the presignatures into a pool.)  A
@@ -722,6 +748,35 @@ int mpe_ecddh_prove(mpe_ctx* ctx, int batch, const uint32_t* d_x, const uint32_t
 int mpe_ecddh_verify(mpe_ctx* ctx, int batch, const mpe_ecddh_statement* statement, const mpe_ecddh_proof* proof, uint8_t* d_ok,
                      void* stream);
 
+/* ---- SHA-512, HMAC-SHA512 and BIP32 public derivation -----------------------------------------------------------------------------
+ * One item per lane.  Byte arrays are device uint8_t rows of a length fixed per call.
+ * mpe_sha512       d_msg [batch][msg_bytes] -> d_out [batch][64], 0 <= msg_bytes <= MPE_SHA512_MAX_MSG_BYTES (65 536).
+ * mpe_hmac_sha512  d_key [batch][key_bytes], 0 <= key_bytes <= 128 (a longer key is MPE_E_ARG: RFC 2104's hash-the-key branch is not
+ *                  built), d_msg as above -> d_out [batch][64].
+ * mpe_bip32_derive CKDpub along a path of non-hardened indices, one row per lane.  Parents: d_parent_pub [n_parents][16] (x [8] | y [8]
+ *                  little-endian words, as every point here), d_parent_cc [n_parents][32] bytes; row b starts from parent
+ *                  d_parent_idx[b] (NULL = parent 0) and walks d_path[b][0 .. d_depth[b]) (d_path [batch][max_depth], 1 <= max_depth <=
+ *                  MPE_BIP32_MAX_DEPTH).  Per level I = HMAC-SHA512(cc, serP(K) | ser32(i)); tweak += I_L mod q; K += I_L G; cc = I_R.
+ *                  Outputs: d_tweak [batch][8] (the sum of the I_L: child private key = parent private key + tweak mod q — what
+ *                  mpe_gg20_session_create_tweaks takes), d_child_pub [batch][16], d_child_cc [batch][32], d_status [batch]:
+ *                    0 ok (depth 0: tweak 0, the parent's key and chain code)
+ *                    MPE_BIP32_STATUS_HARDENED  an index >= 2^31 on the path (hardened derivation needs the private key)
+ *                    MPE_BIP32_STATUS_INVALID   I_L >= q or a child at infinity at some level (BIP32: take the next index — the
+ *                                               caller's choice), or a parent that is not a valid point
+ *                    MPE_BIP32_STATUS_DEPTH     d_depth[b] outside [0, max_depth] or d_parent_idx[b] outside [0, n_parents)
+ *                  A FAILED ROW NEVER READS AS "TWEAK 0" (which would sign for the parent): its tweak is 0xFFFFFFFF x 8 (>= q: a session
+ *                  refuses it with MPE_GG20_STATUS_BAD_TWEAK), its child key and chain code are zero. */
+#define MPE_SHA512_MAX_MSG_BYTES ((int)65536)
+#define MPE_BIP32_MAX_DEPTH ((int)16)
+#define MPE_BIP32_STATUS_HARDENED ((int)1)
+#define MPE_BIP32_STATUS_INVALID ((int)2)
+#define MPE_BIP32_STATUS_DEPTH ((int)3)
+int mpe_sha512(mpe_ctx* ctx, int batch, const uint8_t* d_msg, int msg_bytes, uint8_t* d_out, void* stream);
+int mpe_hmac_sha512(mpe_ctx* ctx, int batch, const uint8_t* d_key, int key_bytes, const uint8_t* d_msg, int msg_bytes, uint8_t* d_out,
+                    void* stream);
+int mpe_bip32_derive(mpe_ctx* ctx, int batch, int n_parents, const uint32_t* d_parent_pub, const uint8_t* d_parent_cc,
+                     const int32_t* d_parent_idx, const uint32_t* d_path, const int32_t* d_depth, int max_depth, uint32_t* d_tweak,
+                     uint32_t* d_child_pub, uint8_t* d_child_cc, int32_t* d_status, void* stream);
 /* The lock-step composition of the rounds above with every signer local (needs every signer's secrets in `keys`):
  * OfflineStage Round0..Round6 and SignManual for `batch` sessions on this GPU — what `round_based::dev::Simulation`
  * does for one session (state_machine/sign.rs:667-763).  nonces: [batch][S] layout.  Outputs per session: d_r, d_s
@@ -737,6 +792,11 @@ int mpe_gg20_sign(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, const int3
 int mpe_gg20_sign_sets(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, const int32_t* d_keyset, const int32_t* d_sigset,
                        const mpe_gg20_nonces* nonces, uint32_t* d_r, uint32_t* d_s, int32_t* d_recid, uint32_t* d_R, int32_t* d_status,
                        int dedup_verify, int chunk, void* stream);
+/* ... with a tweak per session (d_tweak [batch][8], device; NULL = mpe_gg20_sign_sets): session b signs for the child key y + t_b G
+ * (mpe_gg20_session_create_tweaks).  A session whose tweak is refused ends with status MPE_GG20_STATUS_BAD_TWEAK and zero outputs. */
+int mpe_gg20_sign_tweaks(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, const int32_t* d_keyset, const int32_t* d_sigset,
+                         const uint32_t* d_tweak, const mpe_gg20_nonces* nonces, uint32_t* d_r, uint32_t* d_s, int32_t* d_recid,
+                         uint32_t* d_R, int32_t* d_status, int dedup_verify, int chunk, void* stream);
 /* The offline stage alone, as one call: chunks and runs rounds 0-6 exactly as mpe_gg20_sign_sets does and, where that function signs,
  * deposits every chunk into `pool`; the same scratch is zeroed before the call returns.  nonces->msg is not read and may be NULL.
  * `pool` must be over `keys`, on this context's device, with all S ordinals local, else MPE_E_ARG and nothing is touched.  Row b goes to

@@ -35,6 +35,10 @@ def gg20_status_pass_failed(rc):              # MPE_GG20_STATUS_PASS_FAILED(rc),
 SEAL_MAGIC, SEAL_REFUSED, SEAL_MAX_WORDS = 0x3153504D, 841, 4096
 SEAL_KIND_PRESIG, SEAL_KIND_KEYSHARE, SEAL_KIND_USER = 1, 2, 16
 GG20_KEYSHARE_WORDS = 72
+# ... as are those of the child-key sessions and of SHA-512 / BIP32 derivation (tests/test_bip32_cpu.py compares them the same way)
+GG20_STATUS_BAD_TWEAK = 93
+SHA512_MAX_MSG_BYTES, BIP32_MAX_DEPTH = 65536, 16
+BIP32_STATUS_HARDENED, BIP32_STATUS_INVALID, BIP32_STATUS_DEPTH = 1, 2, 3
 
 
 class MpeError(RuntimeError):

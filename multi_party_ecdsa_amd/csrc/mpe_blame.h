@@ -400,6 +400,8 @@ int mpe_ecddh_verify(mpe_ctx* ctx, int batch, const mpe_ecddh_statement* stateme
 int mpe_gg20_session_blame6_state(const mpe_gg20_session* s, const uint32_t* d_nonce, uint32_t* d_miu, uint32_t* d_a1, uint32_t* d_a2,
                                   uint32_t* d_z, void* stream) {
   if (!s || !d_nonce || !d_miu || !d_a1 || !d_a2 || !d_z) return MPE_E_ARG;
+  // the blame entry points take a key object and know no tweak: openings of a child key's session would be judged against the parent's g_w
+  if (s->d.tw) { mpe_set_error_msg("gg20: blame does not support sessions with tweaks (mpe_gg20_session_create_tweaks)"); return MPE_E_ARG; }
   if (s->next_round < 6) { mpe_set_error_msg("gg20: the phase-6 openings exist after round 5"); return MPE_E_ARG; }
   hipStream_t st = (hipStream_t)stream;
   const mpe::gg::Counts c = mpe::gg::counts_of(s->d);

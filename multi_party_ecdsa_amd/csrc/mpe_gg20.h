@@ -87,6 +87,10 @@ struct Dim {
   uint32_t sg4;          // sg in that form
   int nsets;             // sets of the key object (the gw table is [K][nsets][S][16])
   int lparty;            // >= 0: the ONE local party, by party index: its ordinal in session b is its rank in that session's set; -1: loc
+  // per-session tweaks (mpe_gg20_*_tweaks): session b signs for the child key x + tw[b]; all three null: no tweak, the key object's tables
+  const uint32_t* tw;    // [B][8]     the tweak t_b
+  const uint32_t* ty;    // [B][16]    y + t_b G (zero: t_b is not canonical, or the child key is the point at infinity)
+  const uint32_t* tgw;   // [B][S][16] g_w of the session's set + (lambda_j t_b) G
 };
 __device__ __forceinline__ int ind_of(int i, int jj) { return jj < i ? jj : jj + 1; }
 __device__ __forceinline__ int jme_of(int i, int ind) { return i < ind ? i : i - 1; }
@@ -112,8 +116,14 @@ __device__ __forceinline__ int kpub(const Dim& d, int b, int i) { return ks_of(d
 // (i is a LOCAL party's ordinal)
 __device__ __forceinline__ int kown(const Dim& d, int b, int i) { return ks_of(d, b) * d.n_own + d.oslot[d.lparty >= 0 ? d.lparty : sg_of(d, b, i)]; }
 // g_w of signer ordinal `ind` in session b
+// (a session with tweaks: its own table, tweak_kernel; `gw` is the key object's)
 __device__ __forceinline__ const uint32_t* gw_of(const Dim& d, const uint32_t* gw, int b, int ind) {
+  if (d.tgw) return d.tgw + ((size_t)b * d.S + ind) * 16;
   return gw + (((size_t)ks_of(d, b) * d.nsets + ss_of(d, b)) * d.S + ind) * 16;
+}
+// the public key session b signs for: the key set's y (`y` is the key object's [K][16]), or the session's child key
+__device__ __forceinline__ const uint32_t* y_of(const Dim& d, const uint32_t* y, int b) {
+  return d.ty ? d.ty + (size_t)b * 16 : y + (size_t)ks_of(d, b) * 16;
 }
 
 // incoming message slab: sender j's [B][W] block starts at record off[j]
@@ -264,6 +274,24 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC gw_kernel(Dim d, const uint32_t
   ec::aff_store(gw + (size_t)g * 16, ec::mul_aff(lagrange0(set4, d.S, j), ec::aff_load(Xs + ((size_t)kk * d.n + ((set4 >> (4 * j)) & 15u)) * 16)));
 }
 
+// The tables of a session with tweaks, at create and at every re-arm (d.tgw / d.ty still null here: gw_of / y_of read the key object):
+// lane (b, j < S): tgw[b][j] = g_w[set of b][j] + (lambda_j t_b) G;  lane (b, S): ty[b] = y + t_b G.  Both from the comb tables.
+// A tweak that is not canonical (t_b >= q) leaves zero rows, as does a child key at infinity: r0_kernel stops on a zero ty[b].
+__global__ void __launch_bounds__(64) MPE_EC_OCC tweak_kernel(Dim d, const uint32_t* __restrict__ tw, const uint32_t* __restrict__ gw,
+                          const uint32_t* __restrict__ y, uint32_t* __restrict__ tgw, uint32_t* __restrict__ ty) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= d.B * (d.S + 1)) return;
+  const int b = g / (d.S + 1), j = g % (d.S + 1);
+  uint32_t* out = j < d.S ? tgw + ((size_t)b * d.S + j) * 16 : ty + (size_t)b * 16;
+  const ec::U256 t = ec::u256_load(tw + (size_t)b * 8);
+  ec::Aff r; r.inf = true;
+  if (!ec::u256_ge(t, ec::FQ)) {
+    const ec::U256 k = j < d.S ? ec::sc_mul(lagrange0(set4_of(d, b), d.S, j), t) : t;
+    r = ec::jac_to_aff(ec::jac_add(ec::jac_mul_gen(k), ec::jac_from_aff(ec::aff_load(j < d.S ? gw_of(d, gw, b, j) : y_of(d, y, b)))));
+  }
+  if (r.inf) { for (int w = 0; w < 16; ++w) out[w] = 0u; } else ec::aff_store(out, r);
+}
+
 // ---- Round 0: SignKeys::create + phase1_broadcast (party_i.rs:546-589) ----------------------------
 __global__ void __launch_bounds__(64) MPE_EC_OCC r0_kernel(Dim d, const uint32_t* __restrict__ xs, const uint32_t* __restrict__ k_in,
                           const uint32_t* __restrict__ gamma_in, const uint32_t* __restrict__ blind, uint32_t* __restrict__ kq,
@@ -281,7 +309,16 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r0_kernel(Dim d, const uint32_t
   const bool k_ok = ec::sc_is_canonical_nonzero(k_in + (size_t)pi * 8), g_ok = ec::sc_is_canonical_nonzero(gamma_in + (size_t)pi * 8);
   if (!k_ok || !g_ok) fail(status, bad, pi, MPE_GG20_STATUS_BAD_NONCE, 0);
   const ec::U256 k = ec::sc_reduce(k_in + (size_t)pi * 8, 8), g = ec::sc_reduce(gamma_in + (size_t)pi * 8, 8);
-  const ec::U256 wi = ec::sc_mul(lagrange0(set4_of(d, b), d.S, i), ec::sc_reduce(xs + (size_t)kown(d, b, i) * 8, 8));
+  ec::U256 xi = ec::sc_reduce(xs + (size_t)kown(d, b, i) * 8, 8);
+  if (d.tw) {
+    // the child key's share x_i + t_b.  A tweak that is not canonical, or a child key at infinity (tweak_kernel left ty[b] zero), is no
+    // key to sign for: the party stops here with MPE_GG20_STATUS_BAD_TWEAK, no message leaves it
+    const ec::U256 t = ec::u256_load(d.tw + (size_t)b * 8);
+    const ec::Aff yb = ec::aff_load(d.ty + (size_t)b * 16);
+    if (ec::u256_ge(t, ec::FQ) || yb.inf) fail(status, bad, pi, MPE_GG20_STATUS_BAD_TWEAK, 0);
+    else xi = ec::sc_add(xi, t);
+  }
+  const ec::U256 wi = ec::sc_mul(lagrange0(set4_of(d, b), d.S, i), xi);
   ec::u256_store(kq + (size_t)pi * 8, k);
   ec::u256_store(gq + (size_t)pi * 8, g);
   ec::u256_store(w + (size_t)pi * 8, wi);
@@ -549,7 +586,7 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r6_kernel(Dim d, Slab in5, cons
     acc = ec::jac_add_aff(acc, E);
   }
   if (mask) fail(status, bad, pi, 601, mask);
-  if (!ec::jac_eq_aff(acc, ec::aff_load(y + (size_t)ks_of(d, b) * 16))) fail(status, bad, pi, 602, 0);
+  if (!ec::jac_eq_aff(acc, ec::aff_load(y_of(d, y, b)))) fail(status, bad, pi, 602, 0);
 }
 
 // ---- small batches: the same checks with a group of adjacent lanes per item ---------------------------
@@ -663,7 +700,7 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC r6_group_kernel(Dim d, int G, S
     acc = ec::jac_add_aff(acc, E);
   }
   if (mask) fail(status, bad, pi, 601, mask);
-  if (!ec::jac_eq_aff(acc, ec::aff_load(y + (size_t)ks_of(d, b) * 16))) fail(status, bad, pi, 602, 0);
+  if (!ec::jac_eq_aff(acc, ec::aff_load(y_of(d, y, b)))) fail(status, bad, pi, 602, 0);
 }
 
 // ---- Round 7: phase7_local_sig -> PartialSignature (party_i.rs:850-871) -------------------------------------------------
@@ -713,7 +750,7 @@ __global__ void __launch_bounds__(64) MPE_EC_OCC complete_kernel(Dim d, Slab in6
   const ec::U256 m = ec::u256_load(mq + (size_t)pi * 8), r = ec::u256_load(rq + (size_t)pi * 8);
   const ec::U256 ry = ec::sc_reduce(R + (size_t)pi * 16 + 8, 8);
   int recid;
-  const bool okv = output_signature_check(s, recid, m, r, ry, y + (size_t)ks_of(d, b) * 16);
+  const bool okv = output_signature_check(s, recid, m, r, ry, y_of(d, y, b));
   const size_t nPI = (size_t)d.B * d.L;
   if (!okv) fail(status + 8 * nPI, bad + 8 * nPI, pi, 701, 0);
   const bool good = resolve_status(status, nPI, pi, NR - 1, nullptr, nullptr) == 0;
@@ -733,6 +770,13 @@ __global__ void result_kernel(Dim d, const int32_t* __restrict__ status, const u
   if (st_out) st_out[o] = stv;
   if (bad_out) bad_out[o] = bm;
   if (R_out) for (int j = 0; j < 16; ++j) R_out[o * 16 + j] = R[(size_t)pi * 16 + j];
+}
+// the public key every session of the batch signs for, [B][16]: its child key, or its key set's y without tweaks; a session whose tweak
+// was refused (MPE_GG20_STATUS_BAD_TWEAK) reads zero
+__global__ void child_keys_kernel(Dim d, const uint32_t* __restrict__ y, uint32_t* __restrict__ out) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= d.B * 16) return;
+  out[g] = y_of(d, y, g / 16)[g % 16];
 }
 // the lock-step composition: a session's status = the smallest non-zero party status; the signature is party 0's
 __global__ void sign_finish_kernel(int B, int L, int b0, const int32_t* __restrict__ pst, const uint32_t* __restrict__ pr,
@@ -775,7 +819,9 @@ struct mpe_gg20_session {
   mpe_ctx* ctx = nullptr;
   const mpe_gg20_keys* K = nullptr;
   int B = 0, L = 0, dedup = 0, next_round = 0;
+  bool tweaked = false;            // created with d_tweak: owns tw / ty / tgw (a re-arm may still pass no tweaks)
   bool any_set = false;            // created with d_sigset: the local parties' secrets were checked against every set of the key object
+  uint32_t *tw = nullptr, *ty = nullptr, *tgw = nullptr;   // created with d_tweak: the batch's tweaks [B][8] and the tables of tweak_kernel (public, not wiped)
   bool failed = false;             // a round call returned an error (MPE_E_NOMEM, a HIP failure): the batch cannot go on; rearm / abort start afresh
   mpe::gg::Dim d{};
   mpe_gg20_nonces Z{};
@@ -860,6 +906,7 @@ static size_t layout(mpe_gg20_session* s, char* base) {
   x.ca_mb = m.i(c.nMB); x.kpub_mb = m.i(c.nMB); x.kown_mb = m.i(c.nMB);
   x.pi_pp = m.i(c.nPP); x.kown_pp = m.i(c.nPP); x.st_pp = m.i(c.nPP);
   x.ca_pv = m.i(c.nPV); x.pi_pv = m.i(c.nPV); x.kpub_pv = m.i(c.nPV); x.st_pv = m.i(c.nPV);
+  if (s->tweaked) { s->tw = m.w((size_t)d.B * 8); s->ty = m.w((size_t)d.B * 16); s->tgw = m.w((size_t)d.B * d.S * 16); }
   s->kq = m.w(c.nPI * 8); s->gq = m.w(c.nPI * 8); s->w = m.w(c.nPI * 8); s->k64 = m.w(c.nPI * 64);
   s->g_gamma = m.w(c.nPI * 16); s->com = m.w(c.nPI * 8); s->c_a = m.w(c.nPI * 128); s->beta = m.w(c.nMB * 8);
   s->ca_all = m.w(c.SB * 128); s->com_all = m.w(c.SB * 8); s->bpk_in = m.w(c.nPP * 16);
@@ -1354,6 +1401,15 @@ static void launch_idx(mpe_gg20_session* s, hipStream_t st) {
   for (const size_t v : {c.nVI, c.nMB, c.nAP, c.nPV, c.nPI}) if (v > total) total = v;
   hipLaunchKernelGGL(idx_kernel, dim3(blocks_for((int)total, 64)), dim3(64), 0, st, s->d, s->ix, (int)total);
 }
+// a batch's tweaks (null: none): the session's copy and its two tables, or back to the key object's
+static void launch_tweaks(mpe_gg20_session* s, const uint32_t* d_tweak, hipStream_t st) {
+  Dim& d = s->d;
+  d.tw = d.ty = d.tgw = nullptr;
+  if (!d_tweak) return;
+  (void)hipMemcpyAsync(s->tw, d_tweak, (size_t)d.B * 32, hipMemcpyDeviceToDevice, st);
+  hipLaunchKernelGGL(tweak_kernel, dim3(blocks_for(d.B * (d.S + 1), 64)), dim3(64), 0, st, d, s->tw, s->K->gw, s->K->y, s->tgw, s->ty);
+  d.tw = s->tw; d.ty = s->ty; d.tgw = s->tgw;
+}
 // the state region after the index tables, everything nonce-derived: secrets of a batch do not outlive it
 static hipError_t wipe_batch_state(mpe_gg20_session* s, hipStream_t st) {
   ahead_drain(s, st);
@@ -1476,6 +1532,11 @@ int mpe_gg20_session_create(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, 
 int mpe_gg20_session_create_sets(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, int n_local, const int32_t* h_local, const int32_t* d_keyset,
                                  const int32_t* d_sigset, int local_by_party, const mpe_gg20_nonces* nonces, int dedup_verify,
                                  mpe_gg20_session** out, void* stream) {
+  return mpe_gg20_session_create_tweaks(ctx, keys, batch, n_local, h_local, d_keyset, d_sigset, local_by_party, nullptr, nonces, dedup_verify, out, stream);
+}
+int mpe_gg20_session_create_tweaks(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, int n_local, const int32_t* h_local, const int32_t* d_keyset,
+                                   const int32_t* d_sigset, int local_by_party, const uint32_t* d_tweak, const mpe_gg20_nonces* nonces,
+                                   int dedup_verify, mpe_gg20_session** out, void* stream) {
   if (!ctx || !keys || !nonces || !out || batch <= 0 || n_local < 1 || n_local > keys->S || !h_local) return MPE_E_ARG;
   mpe::gg::Dim d0{};
   mpe::gg::dim_of_keys(d0, keys, d_keyset, d_sigset);
@@ -1485,6 +1546,7 @@ int mpe_gg20_session_create_sets(mpe_ctx* ctx, const mpe_gg20_keys* keys, int ba
   mpe_gg20_session* s = new (std::nothrow) mpe_gg20_session();
   if (!s) return MPE_E_NOMEM;
   s->ctx = ctx; s->K = keys; s->B = batch; s->L = n_local; s->dedup = dedup_verify ? 1 : 0; s->Z = *nonces; s->any_set = d_sigset != nullptr;
+  s->tweaked = d_tweak != nullptr;
   mpe::gg::Dim& d = s->d;
   d = d0;
   d.B = batch; d.V = dedup_verify ? 1 : 2; d.PV = dedup_verify ? 1 : n_local; d.enc = ctx->enc;
@@ -1507,6 +1569,7 @@ int mpe_gg20_session_create_sets(mpe_ctx* ctx, const mpe_gg20_keys* keys, int ba
   (void)hipMemsetAsync(s->status, 0, c.nPI * mpe::gg::NR * 4, st);
   (void)hipMemsetAsync(s->bad, 0, c.nPI * mpe::gg::NR * 4, st);
   mpe::gg::launch_idx(s, st);
+  mpe::gg::launch_tweaks(s, d_tweak, st);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) { mpe_set_error("gg20 idx_kernel", e); mpe::gg::session_release(s, st); return MPE_E_HIP; }
   *out = s;
@@ -1523,11 +1586,17 @@ int mpe_gg20_session_rearm(mpe_gg20_session* s, const int32_t* d_keyset, const m
 }
 // (a session made without d_sigset checked its local parties' secrets against set 0 alone: it re-arms without one; null here means set 0 again)
 int mpe_gg20_session_rearm_sets(mpe_gg20_session* s, const int32_t* d_keyset, const int32_t* d_sigset, const mpe_gg20_nonces* nonces, void* stream) {
+  return mpe_gg20_session_rearm_tweaks(s, d_keyset, d_sigset, nullptr, nonces, stream);
+}
+// (likewise a session made without d_tweak owns no tables: it re-arms without tweaks; null here means no tweak for the next batch)
+int mpe_gg20_session_rearm_tweaks(mpe_gg20_session* s, const int32_t* d_keyset, const int32_t* d_sigset, const uint32_t* d_tweak,
+                                  const mpe_gg20_nonces* nonces, void* stream) {
   // a long-lived party process signs batch after batch with the same (keys, batch, local parties) shape: the state arrays and
   // the index tables stay, everything nonce-derived is zeroed and the round counter starts again
   if (!s || !nonces) return MPE_E_ARG;
   if (s->K->K > 1 && !d_keyset) return MPE_E_ARG;
   if (d_sigset && !s->any_set) { mpe_set_error_msg("gg20 session rearm: the session was created without per-session signer sets"); return MPE_E_ARG; }
+  if (d_tweak && !s->tweaked) { mpe_set_error_msg("gg20 session rearm: the session was created without per-session tweaks"); return MPE_E_ARG; }
   // a batch that is half-way through the protocol is not silently thrown away: finish it (round 8 = complete) or destroy it
   // — unless a round call FAILED (MPE_E_NOMEM, a HIP error: the batch cannot go on) or the caller abandoned it (mpe_gg20_session_abort)
   if (s->next_round != 0 && s->next_round <= 8 && !s->failed) { mpe_set_error_msg("gg20 session rearm: the previous batch has not completed (finish it, or mpe_gg20_session_abort)"); return MPE_E_ARG; }
@@ -1538,6 +1607,7 @@ int mpe_gg20_session_rearm_sets(mpe_gg20_session* s, const int32_t* d_keyset, co
   if (em != hipSuccess) { mpe_set_error("gg20 session rearm (wipe)", em); return MPE_E_HIP; }
   s->Z = *nonces; s->d.ks = d_keyset; s->d.ss = d_sigset; s->next_round = 0; s->failed = false; s->fault_step = 0; s->fault_mask = 0;
   mpe::gg::launch_idx(s, st);           // the key indices follow the (possibly different) key-set choice
+  mpe::gg::launch_tweaks(s, d_tweak, st);     // (behind d.ks / d.ss: the tables follow the key set and the signer set too)
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) { mpe_set_error("gg20 session rearm", e); return MPE_E_HIP; }
   return MPE_OK;
@@ -1605,6 +1675,14 @@ int mpe_gg20_session_result(const mpe_gg20_session* s, int32_t* d_status, uint32
   return MPE_OK;
 }
 
+int mpe_gg20_session_child_keys(const mpe_gg20_session* s, uint32_t* d_y, void* stream) {
+  if (!s || !d_y) return MPE_E_ARG;
+  hipLaunchKernelGGL(mpe::gg::child_keys_kernel, dim3(mpe::blocks_for(s->B * 16, 64)), dim3(64), 0, (hipStream_t)stream, s->d, s->K->y, d_y);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { mpe_set_error("gg20 child keys", e); return MPE_E_HIP; }
+  return MPE_OK;
+}
+
 }  // extern "C"
 
 namespace mpe {
@@ -1623,8 +1701,8 @@ struct LockstepChunk {
 // two alternating message slabs, hands the session to `tail(chunk, st)` — rounds 7-8 and the results for mpe_gg20_sign_sets, the deposit
 // for mpe_gg20_presign_sets (mpe_presig.h) — releases it, and wipes the slabs and the context's workspace.
 template <class Tail>
-static int lockstep_pass(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, const int32_t* d_keyset, const int32_t* d_sigset, const mpe_gg20_nonces* nonces,
-                         int dedup_verify, int chunk, void* stream, Tail tail) {
+static int lockstep_pass(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, const int32_t* d_keyset, const int32_t* d_sigset, const uint32_t* d_tweak,
+                         const mpe_gg20_nonces* nonces, int dedup_verify, int chunk, void* stream, Tail tail) {
   const int S = keys->S, n = keys->n;
   for (int k = 0; k < (d_sigset ? keys->nsets : 1); ++k)
     for (int i = 0; i < S; ++i)
@@ -1678,7 +1756,8 @@ static int lockstep_pass(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, con
     Z.heg_s1 += oPI * 8; Z.heg_s2 += oPI * 8;
     if (Z.msg) Z.msg += (size_t)b0 * 8;
     mpe_gg20_session* s = nullptr;
-    int rc = mpe_gg20_session_create_sets(ctx, keys, B, S, local, d_keyset ? d_keyset + b0 : nullptr, d_sigset ? d_sigset + b0 : nullptr, 0, &Z, dedup_verify, &s, stream);
+    int rc = mpe_gg20_session_create_tweaks(ctx, keys, B, S, local, d_keyset ? d_keyset + b0 : nullptr, d_sigset ? d_sigset + b0 : nullptr, 0,
+                                            d_tweak ? d_tweak + (size_t)b0 * 8 : nullptr, &Z, dedup_verify, &s, stream);
     if (rc != MPE_OK) return rc;
     s->ahead.lockstep = true;                       // the message slabs never leave the library between two rounds
     rc = mpe::gg::round0(s, M[0], st);
@@ -1708,9 +1787,14 @@ int mpe_gg20_sign(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, const int3
 }
 int mpe_gg20_sign_sets(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, const int32_t* d_keyset, const int32_t* d_sigset, const mpe_gg20_nonces* nonces,
                        uint32_t* d_r, uint32_t* d_s, int32_t* d_recid, uint32_t* d_R, int32_t* d_status, int dedup_verify, int chunk, void* stream) {
+  return mpe_gg20_sign_tweaks(ctx, keys, batch, d_keyset, d_sigset, nullptr, nonces, d_r, d_s, d_recid, d_R, d_status, dedup_verify, chunk, stream);
+}
+int mpe_gg20_sign_tweaks(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, const int32_t* d_keyset, const int32_t* d_sigset, const uint32_t* d_tweak,
+                         const mpe_gg20_nonces* nonces, uint32_t* d_r, uint32_t* d_s, int32_t* d_recid, uint32_t* d_R, int32_t* d_status,
+                         int dedup_verify, int chunk, void* stream) {
   if (!ctx || !keys || !nonces || !d_r || !d_s || !d_recid || !d_status || batch < 0) return MPE_E_ARG;
   const int S = keys->S;
-  return mpe::gg::lockstep_pass(ctx, keys, batch, d_keyset, d_sigset, nonces, dedup_verify, chunk, stream, [&](const mpe::gg::LockstepChunk& c, hipStream_t st) {
+  return mpe::gg::lockstep_pass(ctx, keys, batch, d_keyset, d_sigset, d_tweak, nonces, dedup_verify, chunk, stream, [&](const mpe::gg::LockstepChunk& c, hipStream_t st) {
     int rc = mpe::gg::round7(c.s, c.msg, c.M6, st);
     if (rc == MPE_OK) rc = mpe::gg::complete(c.s, c.M6, nullptr, st);
     if (rc == MPE_OK) rc = mpe_gg20_session_result(c.s, c.pst, nullptr, c.pr, c.ps, c.prec, c.pR, stream);

@@ -267,6 +267,8 @@ static int launch_pair_modexp(mpe_ctx* ctx, const mpe_pairset* ps, int batch, Ro
 #include "mpe_presig.h"
 #include "mpe_sample.h"
 #include "mpe_seal.h"
+#include "mpe_sha512.h"
+#include "mpe_bip32.h"
 #include "mpe_pipeline.h"
 #include "mpe_comm.h"
 #include "mpe_sigma.h"

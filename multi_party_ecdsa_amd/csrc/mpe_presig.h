@@ -355,6 +355,8 @@ static int launched(const char* what) {
 static int deposit_into(mpe_gg20_presig_pool* p, mpe_gg20_session* s, const int32_t* d_slot, int32_t* d_status, hipStream_t st) {
   if (!p || !s || !d_slot) return MPE_E_ARG;
   if (s->failed || s->next_round != 7) { mpe_set_error_msg("presig deposit: the session is not behind round 6"); return MPE_E_ARG; }
+  // a record has no field for a tweak (MPE_GG20_PRESIG_RECORD_VERSION stays 1) and the pool signs and checks under the key object's y
+  if (s->d.tw) { mpe_set_error_msg("presig deposit: a session with tweaks (mpe_gg20_session_create_tweaks) cannot be deposited"); return MPE_E_ARG; }
   bool same = s->K == p->K && s->ctx->device == p->ctx->device && s->L == p->v.L && s->d.lparty < 0;      // (the pool's local parties are ordinals)
   for (int i = 0; same && i < s->L; ++i) same = s->d.loc[i] == p->v.loc[i];
   if (!same) { mpe_set_error_msg("presig deposit: the session's keys or local parties are not the pool's"); return MPE_E_ARG; }
@@ -426,7 +428,7 @@ int mpe_gg20_presign_sets(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, co
   if (!ctx || !keys || !nonces || !pool || !d_slot || !d_status || batch < 0) return MPE_E_ARG;
   if (!mpe::psg::holds_every_signer(pool, keys, ctx)) { mpe_set_error_msg("mpe_gg20_presign_sets: the pool is not over these keys with every signer local"); return MPE_E_ARG; }
   const int S = keys->S;
-  return mpe::gg::lockstep_pass(ctx, keys, batch, d_keyset, d_sigset, nonces, dedup_verify, chunk, stream, [&](const mpe::gg::LockstepChunk& c, hipStream_t st) {
+  return mpe::gg::lockstep_pass(ctx, keys, batch, d_keyset, d_sigset, nullptr, nonces, dedup_verify, chunk, stream, [&](const mpe::gg::LockstepChunk& c, hipStream_t st) {
     // the chunk's deposit codes go to the result scratch behind the slabs ([S][Bc] words, B of them used)
     int rc = mpe::psg::deposit_into(pool, c.s, d_slot + c.b0, c.pst, st);
     if (rc == MPE_OK) {

@@ -539,9 +539,11 @@ class Gg20Session:
     tensors with leading dimensions [B][len(local)] (fields _native.GG20_NONCE_FIELDS; `msg` optional).
     sigset: device int32 [B], the signer set (index into keys.signer_sets) of every session; ordinals are then positions in each
     session's own set.  local_party=p (instead of `local`): the one local party by its party INDEX, its ordinal in a session is its
-    rank in that session's set (mpe_gg20_session_create_sets)."""
+    rank in that session's set (mpe_gg20_session_create_sets).
+    tweaks: device int32 [B, 8], the public tweak of every session (E.bip32_derive): session b signs for the child key x + t_b
+    (mpe_gg20_session_create_tweaks); child_keys() gives the public keys."""
 
-    def __init__(self, ctx, keys, B, local, nonces, keyset=None, dedup_verify=False, sigset=None, local_party=None):
+    def __init__(self, ctx, keys, B, local, nonces, keyset=None, dedup_verify=False, sigset=None, local_party=None, tweaks=None):
         by_party = local_party is not None
         if by_party:
             local = [int(local_party)] if local is None else list(local)
@@ -555,7 +557,12 @@ class Gg20Session:
         nn = _struct(N_.Gg20Nonces, self._nonces)
         lc = (C.c_int32 * self.L)(*self.local)
         h = C.c_void_p()
-        if sigset is None and not by_party:
+        if tweaks is not None:
+            tweaks = tweaks.contiguous()
+            N_.check(N_.lib.mpe_gg20_session_create_tweaks(ctx.h, keys.h, B, self.L, lc, _ptr(keyset), _ptr(sigset), int(by_party), _ptr(tweaks),
+                                                           C.byref(nn), int(bool(dedup_verify)), C.byref(h), ctx.stream()),
+                     "mpe_gg20_session_create_tweaks")
+        elif sigset is None and not by_party:
             N_.check(N_.lib.mpe_gg20_session_create(ctx.h, keys.h, B, self.L, lc, _ptr(keyset), C.byref(nn), int(bool(dedup_verify)),
                                                     C.byref(h), ctx.stream()), "mpe_gg20_session_create")
         else:
@@ -566,18 +573,27 @@ class Gg20Session:
     def _off(self, in_off):
         return None if in_off is None else (C.c_int64 * self.S)(*[int(x) for x in in_off])
 
-    def rearm(self, nonces, keyset=None, sigset=None):
-        """the next batch of the same shape on this object (mpe_gg20_session_rearm[_sets]): fresh sampled values, rounds from 0"""
+    def rearm(self, nonces, keyset=None, sigset=None, tweaks=None):
+        """the next batch of the same shape on this object (mpe_gg20_session_rearm[_sets | _tweaks]): fresh sampled values, rounds from 0"""
         self._nonces = dict(nonces)
         if "msg" not in self._nonces:
             self._nonces["msg"] = torch.zeros((self.B, 8), dtype=torch.int32, device=self.ctx.device)
         self._keyset = keyset
         nn = _struct(N_.Gg20Nonces, self._nonces)
         self._sigset = sigset
-        if sigset is None:
+        if tweaks is not None:
+            N_.check(N_.lib.mpe_gg20_session_rearm_tweaks(self.h, _ptr(keyset), _ptr(sigset), _ptr(tweaks.contiguous()), C.byref(nn), self.ctx.stream()),
+                     "mpe_gg20_session_rearm_tweaks")
+        elif sigset is None:
             N_.check(N_.lib.mpe_gg20_session_rearm(self.h, _ptr(keyset), C.byref(nn), self.ctx.stream()), "mpe_gg20_session_rearm")
         else:
             N_.check(N_.lib.mpe_gg20_session_rearm_sets(self.h, _ptr(keyset), _ptr(sigset), C.byref(nn), self.ctx.stream()), "mpe_gg20_session_rearm_sets")
+
+    def child_keys(self):
+        """[B, 16] device int32: the public key every session of the batch signs for (mpe_gg20_session_child_keys)"""
+        y = torch.empty((self.B, 16), dtype=torch.int32, device=self.ctx.device)
+        N_.check(N_.lib.mpe_gg20_session_child_keys(self.h, _ptr(y), self.ctx.stream()), "mpe_gg20_session_child_keys")
+        return y
 
     def abort(self):
         """mpe_gg20_session_abort: give the running batch up (state wiped now); rearm() starts the next one"""
@@ -645,16 +661,20 @@ class Gg20Session:
             pass
 
 
-def gg20_sign(ctx, keys, nonces, B, dedup_verify=False, chunk=0, want_R=False, keyset=None, sigset=None):
+def gg20_sign(ctx, keys, nonces, B, dedup_verify=False, chunk=0, want_R=False, keyset=None, sigset=None, tweaks=None):
     """nonces: dict of device int32 tensors (fields _native.GG20_NONCE_FIELDS, [B][S] layout).  Returns device tensors
     r [B,8], s [B,8], recid [B], status [B] (0 = signed and verified) and optionally R [B,16].  sigset: device int32 [B], the signer
-    set of every session (mpe_gg20_sign_sets)."""
+    set of every session (mpe_gg20_sign_sets).  tweaks: device int32 [B, 8], session b signs for the child key x + t_b
+    (mpe_gg20_sign_tweaks)."""
     r, s = _new(ctx, B, 8), _new(ctx, B, 8)
     recid = torch.empty((B,), dtype=torch.int32, device=ctx.device)
     status = torch.full((B,), -1, dtype=torch.int32, device=ctx.device)
     R = _new(ctx, B, 16) if want_R else None
     nn = _struct(N_.Gg20Nonces, nonces)
-    if sigset is None:
+    if tweaks is not None:
+        N_.check(N_.lib.mpe_gg20_sign_tweaks(ctx.h, keys.h, B, _ptr(keyset), _ptr(sigset), _ptr(tweaks.contiguous()), C.byref(nn), _ptr(r), _ptr(s),
+                                             _ptr(recid), _ptr(R), _ptr(status), int(bool(dedup_verify)), int(chunk), ctx.stream()), "mpe_gg20_sign_tweaks")
+    elif sigset is None:
         N_.check(N_.lib.mpe_gg20_sign(ctx.h, keys.h, B, _ptr(keyset), C.byref(nn), _ptr(r), _ptr(s), _ptr(recid), _ptr(R), _ptr(status),
                                       int(bool(dedup_verify)), int(chunk), ctx.stream()), "mpe_gg20_sign")
     else:
@@ -720,6 +740,65 @@ def poly1305(ctx, d_key, d_msg):
     tag = torch.empty((count, 4), dtype=torch.int32, device=ctx.device)
     N_.check(N_.lib.mpe_poly1305(ctx.h, count, _ptr(d_key), _ptr(d_msg), d_msg.shape[1], _ptr(tag), ctx.stream()), "mpe_poly1305")
     return tag
+
+
+def _bytes_rows(ctx, rows, name):
+    """device uint8 [count, bytes] of a tensor, or of a list of equally long bytes objects"""
+    if isinstance(rows, torch.Tensor):
+        if rows.dtype != torch.uint8 or rows.dim() != 2:
+            raise ValueError(f"{name}: a uint8 [count, bytes] tensor")
+        return rows.to(ctx.device).contiguous()
+    rows = [bytes(r) for r in rows]
+    if len({len(r) for r in rows}) > 1:
+        raise ValueError(f"{name}: rows of one length")
+    return torch.tensor([list(r) for r in rows], dtype=torch.uint8, device=ctx.device).reshape(len(rows), len(rows[0]) if rows else 0)
+
+
+def sha512(ctx, msg):
+    """msg: uint8 [count, bytes] (device tensor, or a list of bytes of one length, at most _native.SHA512_MAX_MSG_BYTES)
+    -> digests, device uint8 [count, 64] (mpe_sha512)"""
+    d_msg = _bytes_rows(ctx, msg, "sha512")
+    out = torch.empty((d_msg.shape[0], 64), dtype=torch.uint8, device=ctx.device)
+    N_.check(N_.lib.mpe_sha512(ctx.h, d_msg.shape[0], _ptr(d_msg), d_msg.shape[1], _ptr(out), ctx.stream()), "mpe_sha512")
+    return out
+
+
+def hmac_sha512(ctx, key, msg):
+    """key: uint8 [count, 0..128], msg: uint8 [count, bytes] -> device uint8 [count, 64] (mpe_hmac_sha512)"""
+    d_key, d_msg = _bytes_rows(ctx, key, "hmac_sha512 key"), _bytes_rows(ctx, msg, "hmac_sha512 msg")
+    if d_key.shape[0] != d_msg.shape[0]:
+        raise ValueError("hmac_sha512: one key per message")
+    out = torch.empty((d_msg.shape[0], 64), dtype=torch.uint8, device=ctx.device)
+    N_.check(N_.lib.mpe_hmac_sha512(ctx.h, d_msg.shape[0], _ptr(d_key), d_key.shape[1], _ptr(d_msg), d_msg.shape[1], _ptr(out), ctx.stream()),
+             "mpe_hmac_sha512")
+    return out
+
+
+def bip32_derive(ctx, d_pub, cc, paths, depth=None, parent_idx=None):
+    """BIP32 CKDpub along non-hardened paths (mpe_bip32_derive).  d_pub: parents' public keys, device int32 [n_parents, 16] (or [16]);
+    cc: their chain codes, uint8 [n_parents, 32] (tensor or list of bytes); paths: [B, max_depth] indices (tensor or nested list, values
+    below 2^32); depth: [B] levels used of each row (default: all max_depth); parent_idx: [B] (default: parent 0).
+    Returns device tensors (tweak int32 [B, 8], child_pub int32 [B, 16], child_cc uint8 [B, 32], status int32 [B]); a row whose status
+    is not 0 has the all-ones tweak, which a session refuses."""
+    dv = ctx.device
+    d_pub = d_pub.reshape(-1, 16).contiguous()
+    d_cc = _bytes_rows(ctx, [cc] if isinstance(cc, (bytes, bytearray)) else cc, "bip32_derive cc")
+    if d_cc.shape != (d_pub.shape[0], 32):
+        raise ValueError("bip32_derive: one 32-byte chain code per parent")
+    if isinstance(paths, torch.Tensor):
+        d_path = paths.to(dv).to(torch.int32).contiguous()
+    else:
+        d_path = torch.from_numpy(np.ascontiguousarray(np.array(paths, dtype=np.uint32).reshape(len(paths), -1)).view(np.int32)).to(dv)
+    B, max_depth = d_path.shape
+    i32 = lambda v, fill: (torch.full((B,), fill, dtype=torch.int32, device=dv) if v is None else
+                           (v.to(dv).to(torch.int32).contiguous() if isinstance(v, torch.Tensor) else torch.tensor(list(v), dtype=torch.int32, device=dv)))
+    d_depth = i32(depth, max_depth)
+    d_pidx = None if parent_idx is None else i32(parent_idx, 0)
+    tweak, child = torch.empty((B, 8), dtype=torch.int32, device=dv), torch.empty((B, 16), dtype=torch.int32, device=dv)
+    ccs, status = torch.empty((B, 32), dtype=torch.uint8, device=dv), torch.empty((B,), dtype=torch.int32, device=dv)
+    N_.check(N_.lib.mpe_bip32_derive(ctx.h, B, d_pub.shape[0], _ptr(d_pub), _ptr(d_cc), _ptr(d_pidx), _ptr(d_path), _ptr(d_depth), max_depth,
+                                     _ptr(tweak), _ptr(child), _ptr(ccs), _ptr(status), ctx.stream()), "mpe_bip32_derive")
+    return tweak, child, ccs, status
 
 
 def keyshare_seal(ctx, wrap, d_x, d_p, d_q, nonce_hi=None):
