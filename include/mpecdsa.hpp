@@ -32,6 +32,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <array>
 #include <cstdint>
 #include <cstring>
 #include <map>
@@ -623,6 +624,25 @@ struct SignNonces {
       pdl_beta, pdl_rho, pdl_gamma, heg_s1, heg_s2;
 };
 
+namespace detail {
+// the arrays of a SignNonces in the order of the members of mpe_gg20_nonces (every member but msg, the last)
+constexpr size_t SIGN_NONCE_ARRAYS = sizeof(mpe_gg20_nonces) / sizeof(void*) - 1;
+static_assert(sizeof(SignNonces) == SIGN_NONCE_ARRAYS * sizeof(Batch), "SignNonces: one Batch per array of mpe_gg20_nonces but msg");
+inline std::array<const Batch*, SIGN_NONCE_ARRAYS> sign_nonce_arrays(const SignNonces& z) {
+  return {&z.k, &z.gamma, &z.blind, &z.r_a, &z.al_alpha, &z.al_beta, &z.al_gamma, &z.al_rho, &z.mb_beta_tag, &z.mb_r, &z.mb_nonce_b, &z.mb_nonce_bt,
+          &z.l, &z.ped_s1, &z.ped_s2, &z.pdl_alpha, &z.pdl_beta, &z.pdl_rho, &z.pdl_gamma, &z.heg_s1, &z.heg_s2};
+}
+// uploads them into `keep` (wiped when released): the C-ABI's view of the device arrays, msg NULL
+inline mpe_gg20_nonces upload_sign_nonces(const SignNonces& z, std::vector<std::unique_ptr<Dev<uint32_t>>>& keep) {
+  const uint32_t* d[SIGN_NONCE_ARRAYS + 1] = {};
+  size_t q = 0;
+  for (const Batch* b : sign_nonce_arrays(z)) d[q++] = keep.emplace_back(new Dev<uint32_t>(b->w, true))->get();
+  mpe_gg20_nonces nn;
+  std::memcpy(&nn, d, sizeof nn);                  // (the struct is SIGN_NONCE_ARRAYS + 1 pointers)
+  return nn;
+}
+}  // namespace detail
+
 namespace state_machine {
 namespace sign {
 
@@ -710,13 +730,7 @@ class OfflineStage {
                                  h1.get(), h2.get(), y.get(), X.get(), &P.keys, nullptr), "mpe_gg20_keys_create");
       ctx.sync();
     }
-    const Batch* f[] = {&sampled.k, &sampled.gamma, &sampled.blind, &sampled.r_a, &sampled.al_alpha, &sampled.al_beta, &sampled.al_gamma, &sampled.al_rho,
-                        &sampled.mb_beta_tag, &sampled.mb_r, &sampled.mb_nonce_b, &sampled.mb_nonce_bt, &sampled.l, &sampled.ped_s1, &sampled.ped_s2,
-                        &sampled.pdl_alpha, &sampled.pdl_beta, &sampled.pdl_rho, &sampled.pdl_gamma, &sampled.heg_s1, &sampled.heg_s2};
-    for (const Batch* b : f) P.sampled.emplace_back(new Dev<uint32_t>(b->w, true));       // wiped when released (after round 5 / with the party)
-    auto d = [&](int k) { return (const uint32_t*)P.sampled[(size_t)k]->get(); };
-    const mpe_gg20_nonces nn{d(0), d(1), d(2), d(3), d(4), d(5), d(6), d(7), d(8), d(9), d(10), d(11), d(12), d(13), d(14), d(15), d(16), d(17), d(18),
-                             d(19), d(20), nullptr};
+    const mpe_gg20_nonces nn = gg_2020::detail::upload_sign_nonces(sampled, P.sampled);       // released after round 5 / with the party
     check(mpe_gg20_session_create(ctx.get(), P.keys, batch, 1, &local, nullptr, &nn, 0, &P.sess, nullptr), "mpe_gg20_session_create");
   }
 
@@ -930,13 +944,7 @@ class PartySharded {
                                    y.get(), X.get(), &P->keys, nullptr), "mpe_gg20_keys_create");
         ctx.sync();
       }
-      const SignNonces& z = h.sampled;
-      const Batch* f[] = {&z.k, &z.gamma, &z.blind, &z.r_a, &z.al_alpha, &z.al_beta, &z.al_gamma, &z.al_rho, &z.mb_beta_tag, &z.mb_r, &z.mb_nonce_b,
-                          &z.mb_nonce_bt, &z.l, &z.ped_s1, &z.ped_s2, &z.pdl_alpha, &z.pdl_beta, &z.pdl_rho, &z.pdl_gamma, &z.heg_s1, &z.heg_s2};
-      for (const Batch* b : f) P->sampled.emplace_back(new Dev<uint32_t>(b->w, true));
-      auto d = [&](int q) { return (const uint32_t*)P->sampled[(size_t)q]->get(); };
-      const mpe_gg20_nonces nn{d(0), d(1), d(2), d(3), d(4), d(5), d(6), d(7), d(8), d(9), d(10), d(11), d(12), d(13), d(14), d(15), d(16), d(17), d(18),
-                               d(19), d(20), nullptr};
+      const mpe_gg20_nonces nn = gg_2020::detail::upload_sign_nonces(h.sampled, P->sampled);
       check(mpe_gg20_session_create(ctx.get(), P->keys, batch, 1, &local, nullptr, &nn, 0, &P->sess, nullptr), "mpe_gg20_session_create");
       check(mpe_gg20_shard_in_off(placement, S_, world, batch, h.block, P->in_off), "mpe_gg20_shard_in_off");
       pairs_.push_back(std::move(P));

@@ -22,6 +22,7 @@
 #include <cstdlib>
 
 #include "mpe_gg20_msg.h"
+#include "mpe_gg20_nonces.h"
 #include "mpe_proofs.h"
 
 namespace mpe {
@@ -1746,15 +1747,7 @@ static int lockstep_pass(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, con
   uint32_t* pR = (uint32_t*)(prec + (size_t)S * Bc);
   for (int b0 = 0; b0 < batch; b0 += chunk) {
     const int B = batch - b0 < chunk ? batch - b0 : chunk;
-    const size_t oPI = (size_t)b0 * S, oAP = oPI * n, oPP = oPI * (S - 1), oMB = oPP * 2;
-    mpe_gg20_nonces Z = *nonces;
-    Z.k += oPI * 8; Z.gamma += oPI * 8; Z.blind += oPI * 8; Z.r_a += oPI * 64;
-    Z.al_alpha += oAP * 24; Z.al_beta += oAP * 64; Z.al_gamma += oAP * 88; Z.al_rho += oAP * 72;
-    Z.mb_beta_tag += oMB * 64; Z.mb_r += oMB * 64; Z.mb_nonce_b += oMB * 8; Z.mb_nonce_bt += oMB * 8;
-    Z.l += oPI * 8; Z.ped_s1 += oPI * 8; Z.ped_s2 += oPI * 8;
-    Z.pdl_alpha += oPP * 24; Z.pdl_beta += oPP * 64; Z.pdl_rho += oPP * 72; Z.pdl_gamma += oPP * 88;
-    Z.heg_s1 += oPI * 8; Z.heg_s2 += oPI * 8;
-    if (Z.msg) Z.msg += (size_t)b0 * 8;
+    const mpe_gg20_nonces Z = nonces_from_session(*nonces, S, n, S, b0);          // the chunk's rows, every signer local
     mpe_gg20_session* s = nullptr;
     int rc = mpe_gg20_session_create_tweaks(ctx, keys, B, S, local, d_keyset ? d_keyset + b0 : nullptr, d_sigset ? d_sigset + b0 : nullptr, 0,
                                             d_tweak ? d_tweak + (size_t)b0 * 8 : nullptr, &Z, dedup_verify, &s, stream);

@@ -312,14 +312,13 @@ static int submit_refused(const mpe_gg20_pipeline* p, bool presig, const int32_t
   return MPE_OK;
 }
 // the caller-sampled forms: the first `fields` arrays of the batch go to slot g of the lane's staging (msg is the last field)
-static int stage_nonces(mpe_gg20_pipeline* p, int li, int g, mpe_gg20_nonces* src, int fields) {
+static int stage_nonces(mpe_gg20_pipeline* p, int li, int g, const mpe_gg20_nonces* src, int fields) {
   mpe_gg20_pipeline::Lane& L = p->lane[li];
+  const mpe_gg20_nonce_buf* sb = L.stage;
   for (int f = 0; f < fields; ++f) {
-    mpe_gg20_nonce_buf* sb = L.stage;
-    const size_t w = sb->per_session[f] * (size_t)p->batch;
-    const uint32_t* from = *mpe::smp::nonce_field_ptr(src, f);
-    uint32_t* to = const_cast<uint32_t*>(*mpe::smp::nonce_field_ptr(&sb->view, f)) + (size_t)g * w;
-    (void)hipMemcpyAsync(to, from, w * 4, hipMemcpyDeviceToDevice, L.st);
+    const gg::NonceField& F = gg::NONCE_FIELDS[f];
+    const size_t w = gg::nonce_words(F, sb->S, sb->n, sb->L, p->batch);
+    (void)hipMemcpyAsync(const_cast<uint32_t*>(sb->view.*F.ptr) + (size_t)g * w, src->*F.ptr, w * 4, hipMemcpyDeviceToDevice, L.st);
   }
   return MPE_OK;
 }
@@ -366,14 +365,12 @@ int mpe_gg20_pipeline_submit_sets(mpe_gg20_pipeline* p, const int32_t* d_keyset,
   if (!p || !nonces) return MPE_E_ARG;
   // every refusal comes BEFORE a slot and a ticket are taken: a refused call leaves the pipeline as it was
   MPE_TRY(mpe::pipe::submit_refused(p, false, d_keyset, d_sigset));
-  mpe_gg20_nonces src = *nonces;
-  for (int f = 0; f < mpe::smp::NF; ++f)
-    if (!*mpe::smp::nonce_field_ptr(&src, f)) { mpe_set_error_msg("gg20 pipeline: a nonce array is NULL"); return MPE_E_ARG; }
+  if (mpe::gg::nonces_missing(*nonces, mpe::gg::NF)) { mpe_set_error_msg("gg20 pipeline: a nonce array is NULL"); return MPE_E_ARG; }
   (void)mpe::pipe::poll_open_group(p, nullptr);
   if (p->lane[p->cur].seeded) { mpe_set_error_msg(mpe::pipe::MIXED_FORMS); return MPE_E_ARG; }
   int li = 0, g = 0;
   MPE_TRY(mpe::pipe::open_slot(p, d_r, d_s, d_recid, d_R, d_status, (hipStream_t)stream, &li, &g, ticket));
-  (void)mpe::pipe::stage_nonces(p, li, g, &src, mpe::smp::NF);
+  (void)mpe::pipe::stage_nonces(p, li, g, nonces, mpe::gg::NF);
   return mpe::pipe::close_slot(p, li, d_keyset, d_sigset, nullptr);
 }
 
@@ -404,14 +401,13 @@ int mpe_gg20_pipeline_submit_presig(mpe_gg20_pipeline* p, const int32_t* d_keyse
                                     int32_t* d_status, void* stream, uint64_t* ticket) {
   if (!p || !nonces || !d_slot) return MPE_E_ARG;
   MPE_TRY(mpe::pipe::submit_refused(p, true, d_keyset, d_sigset));
-  mpe_gg20_nonces src = *nonces;
-  for (int f = 0; f < mpe::smp::NF - 1; ++f)          // (msg, the last field, is not read)
-    if (!*mpe::smp::nonce_field_ptr(&src, f)) { mpe_set_error_msg("gg20 pipeline: a nonce array is NULL"); return MPE_E_ARG; }
+  const int fields = mpe::gg::NF - 1;                  // (msg, the last field, is not read)
+  if (mpe::gg::nonces_missing(*nonces, fields)) { mpe_set_error_msg("gg20 pipeline: a nonce array is NULL"); return MPE_E_ARG; }
   (void)mpe::pipe::poll_open_group(p, nullptr);
   if (p->lane[p->cur].seeded) { mpe_set_error_msg(mpe::pipe::MIXED_FORMS); return MPE_E_ARG; }
   int li = 0, g = 0;
   MPE_TRY(mpe::pipe::open_slot(p, nullptr, nullptr, nullptr, nullptr, d_status, (hipStream_t)stream, &li, &g, ticket));
-  (void)mpe::pipe::stage_nonces(p, li, g, &src, mpe::smp::NF - 1);
+  (void)mpe::pipe::stage_nonces(p, li, g, nonces, fields);
   return mpe::pipe::close_slot(p, li, d_keyset, d_sigset, d_slot);
 }
 int mpe_gg20_pipeline_submit_presig_seeded(mpe_gg20_pipeline* p, const int32_t* d_keyset, const int32_t* d_sigset, const uint8_t* h_seed32, uint64_t batch_counter,

@@ -37,7 +37,7 @@ namespace smp {
 // signs on zeroed values, whether or not the caller reads *fail.
 constexpr int DEFAULT_MAX_ATTEMPTS = 128;
 constexpr int F_NONZERO = 1, F_PLUS_ONE = 2, F_COPRIME = 4;
-constexpr int NF = 22;                 // fields of mpe_gg20_nonces, msg last
+using gg::NF;                          // fields of mpe_gg20_nonces, msg last (mpe_gg20_nonces.h)
 
 struct Seed { uint32_t k[8]; };
 
@@ -247,19 +247,6 @@ __global__ void sidx_kernel(gg::Dim d, SIdx x, int total) {
   }
 }
 
-// words per session-party of every field of mpe_gg20_nonces, in declaration order (msg last: per session)
-static void nonce_field_words(int S, int n, int L, size_t per_session[NF]) {
-  const size_t P1 = (size_t)S - 1, l = (size_t)L;
-  const size_t w[NF] = {l * 8, l * 8, l * 8, l * 64, l * n * 24, l * n * 64, l * n * 88, l * n * 72, l * P1 * 2 * 64, l * P1 * 2 * 64, l * P1 * 2 * 8, l * P1 * 2 * 8,
-                        l * 8, l * 8, l * 8, l * P1 * 24, l * P1 * 64, l * P1 * 72, l * P1 * 88, l * 8, l * 8, 8};
-  for (int f = 0; f < NF; ++f) per_session[f] = w[f];
-}
-static const uint32_t** nonce_field_ptr(mpe_gg20_nonces* z, int f) {
-  const uint32_t** p[NF] = {&z->k, &z->gamma, &z->blind, &z->r_a, &z->al_alpha, &z->al_beta, &z->al_gamma, &z->al_rho, &z->mb_beta_tag, &z->mb_r, &z->mb_nonce_b,
-                            &z->mb_nonce_bt, &z->l, &z->ped_s1, &z->ped_s2, &z->pdl_alpha, &z->pdl_beta, &z->pdl_rho, &z->pdl_gamma, &z->heg_s1, &z->heg_s2, &z->msg};
-  return p[f];
-}
-
 }  // namespace smp
 }  // namespace mpe
 
@@ -269,7 +256,6 @@ struct mpe_gg20_nonce_buf {
   size_t bytes = 0;
   int S = 0, n = 0, L = 0, batch = 0;
   mpe_gg20_nonces view{};
-  size_t per_session[mpe::smp::NF] = {0};
 };
 
 namespace mpe {
@@ -295,7 +281,8 @@ static int sample_gg20(mpe_ctx* ctx, const mpe_gg20_keys* K, int per_batch, int 
     for (int i = 0; i < n_local; ++i) if (h_local[i] < 0 || h_local[i] >= K->S || (i && h_local[i] <= h_local[i - 1])) return MPE_E_ARG;
     for (int i = 0; i < 8; ++i) d.loc[i] = i < n_local ? h_local[i] : 0;
   }
-  const size_t P1 = (size_t)K->S - 1, nPI = (size_t)batch * n_local, nAP = nPI * K->n, nPP = nPI * P1, nMB = nPP * 2;
+  const gg::Counts c = gg::counts_of(batch, K->S, K->n, n_local, 0, 0);
+  const size_t nPI = c.nPI, nAP = c.nAP, nPP = c.nPP, nMB = c.nMB;
   // workspace: the bound-row index of every item + the batched coprimality verdict of from_modulo
   const mpe_modset* msn = K->pub->ms_n;
   const size_t idx_words = 2 * nPI + 2 * nAP + nMB + 2 * nPP + (size_t)batch + 128;
@@ -322,34 +309,39 @@ static int sample_gg20(mpe_ctx* ctx, const mpe_gg20_keys* K, int per_batch, int 
   t.n = 0; t.start[0] = 0; t.max_attempts = ctx->sampler_max_attempts; t.owner_bad = owner_bad;
   t.L = n_local; t.S = K->S; t.loc_packed = 0; t.ord = x.ord;
   for (int i = 0; i < n_local && !local_by_party; ++i) t.loc_packed |= (uint32_t)h_local[i] << (4 * i);
-  auto add = [&](int f, const uint32_t* dst, size_t items, const uint32_t* bound, int bw, const int32_t* idx, int ow, int flags, int bits = 0) {
-    t.f[t.n] = FieldDesc{U(dst), bound, idx, (unsigned)(items / nslots), (unsigned)(items / nPI), bw, ow, bits, flags, f};
+  // destination, row count and width of field f: the table (mpe_gg20_nonces.h); the sampler's own knowledge is the bound and the flags
+  size_t items_total = 0;
+  auto add = [&](int f, const uint32_t* bound, int bw, const int32_t* idx, int flags, int bits = 0) {
+    const gg::NonceField& F = gg::NONCE_FIELDS[f];
+    const size_t items = gg::nonce_rows(F.dom, K->S, K->n, n_local, batch);
+    t.f[t.n] = FieldDesc{U(out->*F.ptr), bound, idx, (unsigned)(items / nslots), (unsigned)(items / nPI), bw, F.words, bits, flags, f};
     t.start[t.n + 1] = t.start[t.n] + (unsigned)items;
     t.n++;
+    items_total += items;
   };
-  auto scalar = [&](int f, const uint32_t* dst, size_t items) { add(f, dst, items, b.q, 8, nullptr, 8, F_NONZERO); };      // Scalar::random()
-  scalar(0, out->k, nPI);                                                                      // party_i.rs:563 k_i
-  scalar(1, out->gamma, nPI);                                                                  // :561 gamma_i
-  add(2, out->blind, nPI, nullptr, 0, nullptr, 8, 0, 256);                                     // :574 BigInt::sample(SECURITY)
-  add(3, out->r_a, nPI, N, 64, x.own_pi, 64, 0);                                               // mta/mod.rs:57 sample_below(&alice_ek.n)
-  add(4, out->al_alpha, nAP, b.q3, 24, nullptr, 24, 0);                                        // range_proofs.rs:48 sample_below(q^3)
-  add(5, out->al_beta, nAP, N, 64, x.own_ap, 64, 0);                                           // :49 from_paillier_key -> from_modulo (:544-552)
-  add(6, out->al_gamma, nAP, b.q3Nt, 88, x.st_ap, 88, 0);                                      // :50 sample_below(q^3 N~)
-  add(7, out->al_rho, nAP, b.qNt, 72, x.st_ap, 72, 0);                                         // :51 sample_below(q N~)
-  add(8, out->mb_beta_tag, nMB, N, 64, x.peer_mb, 64, 0);                                      // mta/mod.rs:97 sample_below(&alice_ek.n)
-  add(9, out->mb_r, nMB, N, 64, x.peer_mb, 64, 0);                                             // :98
-  scalar(10, out->mb_nonce_b, nMB);                                                            // :147 DLogProof::prove(b)
-  scalar(11, out->mb_nonce_bt, nMB);                                                           // :148
-  scalar(12, out->l, nPI);                                                                     // party_i.rs:628 l
-  scalar(13, out->ped_s1, nPI);                                                                // PedersenProof::prove (:620-634)
-  scalar(14, out->ped_s2, nPI);
-  add(15, out->pdl_alpha, nPP, b.q3, 24, nullptr, 24, 0);                                      // zk_pdl_with_slack/mod.rs:73
-  add(16, out->pdl_beta, nPP, b.Nm2, 64, x.own_pp, 64, F_PLUS_ONE);                            // :75 sample_range(1, N - 1)
-  add(17, out->pdl_rho, nPP, b.qNt, 72, x.st_pp, 72, 0);                                       // :76
-  add(18, out->pdl_gamma, nPP, b.q3Nt, 88, x.st_pp, 88, 0);                                    // :77
-  scalar(19, out->heg_s1, nPI);                                                                // HomoELGamalProof::prove (:778-799)
-  scalar(20, out->heg_s2, nPI);
-  if ((size_t)t.start[t.n] != 9 * nPI + 4 * nAP + 4 * nMB + 4 * nPP) { mpe_set_error_msg("gg20 sampler: more than 2^32 items in one batch"); return MPE_E_ARG; }          // a batch beyond 2^32 items
+  auto scalar = [&](int f) { add(f, b.q, 8, nullptr, F_NONZERO); };      // Scalar::random()
+  scalar(0);                                                     // party_i.rs:563 k_i
+  scalar(1);                                                     // :561 gamma_i
+  add(2, nullptr, 0, nullptr, 0, 256);                           // :574 BigInt::sample(SECURITY)
+  add(3, N, 64, x.own_pi, 0);                                    // mta/mod.rs:57 sample_below(&alice_ek.n)
+  add(4, b.q3, 24, nullptr, 0);                                  // range_proofs.rs:48 sample_below(q^3)
+  add(5, N, 64, x.own_ap, 0);                                    // :49 from_paillier_key -> from_modulo (:544-552)
+  add(6, b.q3Nt, 88, x.st_ap, 0);                                // :50 sample_below(q^3 N~)
+  add(7, b.qNt, 72, x.st_ap, 0);                                 // :51 sample_below(q N~)
+  add(8, N, 64, x.peer_mb, 0);                                   // mta/mod.rs:97 sample_below(&alice_ek.n)
+  add(9, N, 64, x.peer_mb, 0);                                   // :98
+  scalar(10);                                                    // :147 DLogProof::prove(b)
+  scalar(11);                                                    // :148
+  scalar(12);                                                    // party_i.rs:628 l
+  scalar(13);                                                    // PedersenProof::prove (:620-634)
+  scalar(14);
+  add(15, b.q3, 24, nullptr, 0);                                 // zk_pdl_with_slack/mod.rs:73
+  add(16, b.Nm2, 64, x.own_pp, F_PLUS_ONE);                      // :75 sample_range(1, N - 1)
+  add(17, b.qNt, 72, x.st_pp, 0);                                // :76
+  add(18, b.q3Nt, 88, x.st_pp, 0);                               // :77
+  scalar(19);                                                    // HomoELGamalProof::prove (:778-799)
+  scalar(20);
+  if ((size_t)t.start[t.n] != items_total) { mpe_set_error_msg("gg20 sampler: more than 2^32 items in one batch"); return MPE_E_ARG; }
   SlotTable sl{};
   for (int k = 0; k < nslots; ++k) { sl.key[k] = seed_of(h_seeds + 32 * k); sl.ctr_lo[k] = (uint32_t)h_counters[k]; sl.ctr_hi[k] = (uint32_t)(h_counters[k] >> 32); }
   hipLaunchKernelGGL(sample_fields_kernel, dim3((t.start[t.n] + 63) / 64), dim3(64), 0, st, t, sl, d_fail);
@@ -402,14 +394,11 @@ int mpe_gg20_nonces_alloc(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, in
   mpe_gg20_nonce_buf* nb = new (std::nothrow) mpe_gg20_nonce_buf();
   if (!nb) return MPE_E_NOMEM;
   nb->S = keys->S; nb->n = keys->n; nb->L = n_local; nb->batch = batch;
-  mpe::smp::nonce_field_words(keys->S, keys->n, n_local, nb->per_session);
-  size_t words = 0;
-  for (int f = 0; f < mpe::smp::NF; ++f) words += ((nb->per_session[f] * batch + 63) & ~(size_t)63);
-  nb->bytes = words * 4;
+  const mpe::gg::NonceBlob layout = mpe::gg::nonce_blob(keys->S, keys->n, n_local, batch);
+  nb->bytes = layout.words * 4;
   const hipError_t e = hipMalloc(&nb->blob, nb->bytes);
   if (e != hipSuccess) { delete nb; mpe_set_error("hipMalloc(gg20 nonces)", e); return MPE_E_NOMEM; }
-  uint32_t* p = (uint32_t*)nb->blob;
-  for (int f = 0; f < mpe::smp::NF; ++f) { *mpe::smp::nonce_field_ptr(&nb->view, f) = p; p += ((nb->per_session[f] * batch + 63) & ~(size_t)63); }
+  for (int f = 0; f < mpe::gg::NF; ++f) nb->view.*mpe::gg::NONCE_FIELDS[f].ptr = (const uint32_t*)nb->blob + layout.off[f];
   (void)hipMemset(nb->blob, 0, nb->bytes);
   *out = nb;
   return MPE_OK;

@@ -9,6 +9,7 @@ import torch
 
 from . import _native as N
 N_ = N
+from . import wire
 from .words import ints_to_words, words_to_ints
 
 
@@ -1309,11 +1310,8 @@ def sample_scalar(ctx, batch, seed, stream_id):
 
 def gg20_nonce_shapes(S, n, L, B):
     """rows x words of every field of mpe_gg20_nonces (include/mpecdsa_hip.h) for B sessions x L local parties"""
-    P = L * (S - 1)
-    return dict(k=(B * L, 8), gamma=(B * L, 8), blind=(B * L, 8), r_a=(B * L, 64), al_alpha=(B * L * n, 24), al_beta=(B * L * n, 64),
-                al_gamma=(B * L * n, 88), al_rho=(B * L * n, 72), mb_beta_tag=(B * P * 2, 64), mb_r=(B * P * 2, 64), mb_nonce_b=(B * P * 2, 8),
-                mb_nonce_bt=(B * P * 2, 8), l=(B * L, 8), ped_s1=(B * L, 8), ped_s2=(B * L, 8), pdl_alpha=(B * P, 24), pdl_beta=(B * P, 64),
-                pdl_rho=(B * P, 72), pdl_gamma=(B * P, 88), heg_s1=(B * L, 8), heg_s2=(B * L, 8), msg=(B, 8))
+    rows = wire.nonce_rows(S, n, L, B)
+    return {f: (rows[f], words) for f, _, words in wire.NONCE_FIELDS}
 
 
 def gg20_sample_nonces(ctx, keys, B, seed, batch_counter, local=None, keyset=None, msg=None, out=None, sigset=None, local_party=None):

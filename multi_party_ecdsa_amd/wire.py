@@ -181,6 +181,26 @@ def msg_words(S, n, rnd):
     return {0: SUB0 * (n + 1), 1: SUB1 * 2 * (S - 1), 2: WIDTHS["W2"], 3: WIDTHS["W3"], 4: SUB4 * S, 5: WIDTHS["W5"], 7: WIDTHS["W6"]}[rnd]
 
 
+# ---- the arrays of mpe_gg20_nonces (include/mpecdsa_hip.h, the comment above the struct) ------------------------------------
+# Every field as (name, row domain, words) in declaration order, msg last; csrc/mpe_gg20_nonces.h states the same table for the
+# library (tests/test_gg20_layout_cpu.py compares the two).  Domains: PI [B][L], AP [B][L][n], MB [B][L][S-1][2], PP [B][L][S-1], B [B].
+NONCE_FIELDS = (
+    ("k", "PI", 8), ("gamma", "PI", 8), ("blind", "PI", 8), ("r_a", "PI", 64),
+    ("al_alpha", "AP", 24), ("al_beta", "AP", 64), ("al_gamma", "AP", 88), ("al_rho", "AP", 72),
+    ("mb_beta_tag", "MB", 64), ("mb_r", "MB", 64), ("mb_nonce_b", "MB", 8), ("mb_nonce_bt", "MB", 8),
+    ("l", "PI", 8), ("ped_s1", "PI", 8), ("ped_s2", "PI", 8),
+    ("pdl_alpha", "PP", 24), ("pdl_beta", "PP", 64), ("pdl_rho", "PP", 72), ("pdl_gamma", "PP", 88),
+    ("heg_s1", "PI", 8), ("heg_s2", "PI", 8),
+    ("msg", "B", 8),
+)
+
+
+def nonce_rows(S, n, L, B):
+    """rows of every field of mpe_gg20_nonces for B sessions x L local parties of S signers among n (B = L = 1: per session-party)"""
+    per = dict(PI=B * L, AP=B * L * n, MB=B * L * (S - 1) * 2, PP=B * L * (S - 1), B=B)
+    return {f: per[dom] for f, dom, _ in NONCE_FIELDS}
+
+
 def field(record, name, base=0):
     """the slice a field takes in a record (or in a slab row whose record starts at `base`)"""
     off, words = next((o, k) for f, o, k in RECORDS[record] if f == name)

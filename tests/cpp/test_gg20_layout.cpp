@@ -1,10 +1,13 @@
 // Host-only dump of the GG20 message layout and the per-round scratch sizing (multi_party_ecdsa_amd/csrc/mpe_gg20_msg.h), for
 // tests/test_gg20_layout_cpu.py: every record as `field <record> <name> <offset> <words>` lines, the widths as `width <name> <words>`,
 // and for a few batch shapes `tmp <B S n L V PV> <tmp_bytes_of> <take of rounds 0 1 2 4 5> <the earlier hand-written bound>`.
+// The arrays of mpe_gg20_nonces (mpe_gg20_nonces.h) follow: `nonce <index> <name> <domain> <words>` per field, and for a few shapes
+// `nonce_rows <S n L B> <name> <rows> <word offset in the blob of mpe_gg20_nonces_alloc>`.
 // Built with `hipcc --cuda-host-only` (no GPU needed).
 #include <cstdio>
 
 #include "../../multi_party_ecdsa_amd/csrc/mpe_gg20_msg.h"
+#include "../../multi_party_ecdsa_amd/csrc/mpe_gg20_nonces.h"
 
 using namespace mpe::gg;
 
@@ -44,6 +47,14 @@ int main() {
                 take[4], earlier);
     for (const size_t t : take) bad += t > total;
     bad += total > earlier;
+  }
+  for (int f = 0; f < NF; ++f) std::printf("nonce %d %s %s %d\n", f, NONCE_FIELDS[f].name, DOM_NAMES[(int)NONCE_FIELDS[f].dom], NONCE_FIELDS[f].words);
+  const int nonce_shapes[][4] = {{2, 3, 1, 1}, {2, 3, 2, 1}, {3, 5, 3, 4}, {3, 4, 2, 5}, {6, 8, 6, 3}, {2, 3, 2, 0}};      // S n L B
+  for (const auto& s : nonce_shapes) {
+    const NonceBlob blob = nonce_blob(s[0], s[1], s[2], s[3]);
+    for (int f = 0; f < NF; ++f)
+      std::printf("nonce_rows %d %d %d %d %s %zu %zu\n", s[0], s[1], s[2], s[3], NONCE_FIELDS[f].name, nonce_rows(NONCE_FIELDS[f].dom, s[0], s[1], s[2], s[3]),
+                  blob.off[f]);
   }
   if (bad) { std::printf("FAILED %d scratch bounds\n", bad); return 1; }
   std::printf("OK\n");

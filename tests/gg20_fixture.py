@@ -23,9 +23,10 @@ class KeysStruct(C.Structure):
                [(f, C.c_void_p) for f in ("x", "p", "q", "N", "Nt", "h1", "h2", "y", "X")]
 
 
-NONCE_FIELDS = ["k", "gamma", "blind", "r_a", "al_alpha", "al_beta", "al_gamma", "al_rho", "mb_beta_tag", "mb_r",
-                "mb_nonce_b", "mb_nonce_bt", "l", "ped_s1", "ped_s2", "pdl_alpha", "pdl_beta", "pdl_rho", "pdl_gamma",
-                "heg_s1", "heg_s2", "msg"]
+# the arrays of mpe_gg20_nonces: the package's table too (tests/test_gg20_layout_cpu.py pins it to include/mpecdsa_hip.h)
+NONCE_FIELDS = [f for f, _, _ in wire.NONCE_FIELDS]
+NONCE_WIDTHS = {f: words for f, _, words in wire.NONCE_FIELDS}
+nonce_rows = wire.nonce_rows
 
 
 class NoncesStruct(C.Structure):
@@ -84,10 +85,7 @@ def make_nonces(lk, B, seed="sessions"):
                 for f in ("alpha", "beta", "rho", "gamma"):
                     z["pdl_" + f].append(nn[f])
         z["msg"].append(int.from_bytes(__import__("hashlib").sha256(b"session %d" % b).digest(), "big"))
-    widths = dict(k=8, gamma=8, blind=8, r_a=64, al_alpha=24, al_beta=64, al_gamma=88, al_rho=72, mb_beta_tag=64, mb_r=64,
-                  mb_nonce_b=8, mb_nonce_bt=8, l=8, ped_s1=8, ped_s2=8, pdl_alpha=24, pdl_beta=64, pdl_rho=72, pdl_gamma=88,
-                  heg_s1=8, heg_s2=8, msg=8)
-    return {f: F.words(v, widths[f]) for f, v in z.items()}
+    return {f: F.words(v, NONCE_WIDTHS[f]) for f, v in z.items()}
 
 
 def nonces_struct(arrs):
@@ -220,9 +218,7 @@ class OracleParty:
 def party_nonces(nonces, lk, i):
     """the [B][1] slice of the [B][S] nonce arrays that belongs to signer ordinal i (msg stays whole)"""
     S, n = lk["S"], lk["n"]
-    per = dict(k=1, gamma=1, blind=1, r_a=1, l=1, ped_s1=1, ped_s2=1, heg_s1=1, heg_s2=1, al_alpha=n, al_beta=n, al_gamma=n, al_rho=n,
-               mb_beta_tag=2 * (S - 1), mb_r=2 * (S - 1), mb_nonce_b=2 * (S - 1), mb_nonce_bt=2 * (S - 1), pdl_alpha=S - 1, pdl_beta=S - 1,
-               pdl_rho=S - 1, pdl_gamma=S - 1)
+    per = nonce_rows(S, n, 1, 1)
     out = {}
     for f, v in nonces.items():
         if f == "msg":
@@ -304,18 +300,6 @@ def oracle_blame(lk, which, opened, B, keyset=None):
         kset = None if keyset is None else np.ascontiguousarray(keyset, dtype=np.int32)
         getattr(orc.lib, "orc_gg20_blame5" if which == "b5" else "orc_gg20_blame6")(C.byref(ks), orc._p(kset), B, st, orc._p(bad))
     return bad
-
-
-NONCE_WIDTHS = dict(k=8, gamma=8, blind=8, r_a=64, al_alpha=24, al_beta=64, al_gamma=88, al_rho=72, mb_beta_tag=64, mb_r=64,
-                    mb_nonce_b=8, mb_nonce_bt=8, l=8, ped_s1=8, ped_s2=8, pdl_alpha=24, pdl_beta=64, pdl_rho=72, pdl_gamma=88,
-                    heg_s1=8, heg_s2=8, msg=8)
-
-
-def nonce_rows(S, n, L, B):
-    P = L * (S - 1)
-    return dict(k=B * L, gamma=B * L, blind=B * L, r_a=B * L, al_alpha=B * L * n, al_beta=B * L * n, al_gamma=B * L * n, al_rho=B * L * n,
-                mb_beta_tag=B * P * 2, mb_r=B * P * 2, mb_nonce_b=B * P * 2, mb_nonce_bt=B * P * 2, l=B * L, ped_s1=B * L, ped_s2=B * L,
-                pdl_alpha=B * P, pdl_beta=B * P, pdl_rho=B * P, pdl_gamma=B * P, heg_s1=B * L, heg_s2=B * L, msg=B)
 
 
 def oracle_sample_nonces(lk, B, seed, counter, local=None, keyset=None, msg=None):

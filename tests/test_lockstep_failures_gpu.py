@@ -141,6 +141,26 @@ def test_no_state_computed_ahead_leaks_from_one_chunk_into_the_next(table):
         ctx.close()
 
 
+def test_every_chunk_reads_its_own_rows_of_every_nonce_array(gpu_ctx, keys):
+    """three signers of four parties — n, S and S - 1 all distinct, so the rows of a session start at another offset in every row
+    domain of mpe_gg20_nonces ([B][L], [B][L][n], [B][L][S-1][2], [B][L][S-1], [B]) — five sessions in chunks of two, the last chunk
+    partial: r, s, recid and status of every session are the oracle's on the same arrays and those of the batch in one piece (a wrong
+    width or domain for any one field hands sessions 2-4 another row's value)"""
+    import gg20_fixture as G
+    lk = G.make_local_keys(keys, 2, 4, [0, 1, 3], seed="lockstep-strides")
+    bt = LC.Batch("strides", lk, G.make_nonces(lk, 5, seed="lockstep-strides"), 5)
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(bt.B) as ex:                     # one session per host thread (ctypes releases the GIL), each writes its own row
+        rows = list(ex.map(lambda b: G.oracle_sign(lk, bt.nonces, bt.B, first=b, count=1), range(bt.B)))
+    wr, ws, wrecid, wstatus = [np.stack([rows[b][j][b] for b in range(bt.B)]) for j in (0, 1, 2, 4)]
+    assert not wstatus.any()
+    chunked, whole = _sign(gpu_ctx, bt, chunk=2), _sign(gpu_ctx, bt, chunk=0)
+    for got, where in ((chunked, "chunk = 2"), (whole, "chunk = 0")):
+        for f, want in (("status", wstatus), ("r", wr), ("s", ws), ("recid", wrecid)):
+            assert np.array_equal(got[f], want), f"{where}: {f} differs from the oracle's"
+    _same(chunked, whole, "chunk = 2 against chunk = 0")
+
+
 def test_a_context_and_a_key_object_sign_cleanly_after_batches_with_failures(table, keys):
     """one context on the schedule, one key object: a batch with failures, the clean parity case, a batch in which EVERY session fails
     (nobody consumes what was started ahead for a signature), the clean case again — the clean case gives the oracle's bytes each time"""

@@ -174,11 +174,8 @@ def test_objects_hosting_different_parties_never_share_a_stream():
     t, n, signers = 2, 5, [0, 2, 4]
     lk = G.make_local_keys(keys, t, n, signers)
     B, S = 3, len(signers)
-    P1 = S - 1
     full, _ = G.oracle_sample_nonces(lk, B, SEED, 9)
-    per = {"k": 1, "gamma": 1, "blind": 1, "r_a": 1, "al_alpha": n, "al_beta": n, "al_gamma": n, "al_rho": n, "mb_beta_tag": 2 * P1, "mb_r": 2 * P1,
-           "mb_nonce_b": 2 * P1, "mb_nonce_bt": 2 * P1, "l": 1, "ped_s1": 1, "ped_s2": 1, "pdl_alpha": P1, "pdl_beta": P1, "pdl_rho": P1,
-           "pdl_gamma": P1, "heg_s1": 1, "heg_s2": 1}
+    per = {f: m for f, m in G.nonce_rows(S, n, 1, 1).items() if f != "msg"}          # rows per session-party
     seen = {}
     for ordinal in range(S):
         one, _ = G.oracle_sample_nonces(lk, B, SEED, 9, local=[ordinal])
