@@ -257,10 +257,10 @@ int mpe_paillier_open(mpe_ctx* ctx, const mpe_paillier* sk, int batch, const int
   hipStream_t st = (hipStream_t)stream;
   MPE_TRY(paillier_decrypt(ctx, sk, batch, d_key_idx, rows(d_c, 128), d_m, st));
   const int nk = sk->nkeys;
-  MPE_TRY(ws_reserve(ctx, ((size_t)nk * 64 * 3 + modinv_ws_words(sk->ms_n, nk)) * 4 + 65536, st));
+  MPE_TRY(ws_begin(ctx, st));
   uint32_t *phi = ws_array<uint32_t>(ctx, (size_t)nk * 64), *u = ws_array<uint32_t>(ctx, (size_t)nk * 64), *d = ws_array<uint32_t>(ctx, (size_t)nk * 64);
   uint8_t* ok = ws_array<uint8_t>(ctx, ((size_t)nk + 255) & ~(size_t)255);
-  if (!phi || !u || !d || !ok) { mpe_set_error_msg("mpe_paillier_open: workspace"); return MPE_E_NOMEM; }
+  MPE_TRY(ws_ok(ctx));
   MPE_LAUNCH_1D(bl::open_phi_kernel, nk, st, nk, sk->N, sk->pq32, phi);
   MPE_TRY(launch_modinv(ctx, sk->ms_n, nk, rows(nullptr, 1), rows(phi, 64), u, ok, st));
   MPE_LAUNCH_1D(bl::open_d_kernel, nk, st, nk, sk->N, phi, u, ok, d);
@@ -286,15 +286,13 @@ int mpe_gg20_blame5_sets(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, con
   hipStream_t st = (hipStream_t)stream;
   const int S = keys->S, P1 = S - 1, nPI = batch * S, nPP = nPI * P1;
   const bl::Dim d = bl::blame_dim(ctx, keys, batch, d_keyset, d_sigset);
-  // own arrays at the top of the workspace (never handed out, never moved: ws_top), the Paillier composites below
-  const size_t own = ((size_t)nPI * (64 + 128) + (size_t)nPP * 128) * 4 + ((size_t)nPI + 3 * (size_t)nPP) * 4 + (size_t)nPI * 2 + nPP + 16 * 256;   // BIdx: one [nPI] + three [nPP] arrays; 256 B slack per take()
-  MPE_TRY(ws_reserve(ctx, own + ws_need_encrypt(nPI) + ws_need_mul_add_enc(nPP) + (1u << 20), st));
-  char* top = (char*)ctx->ws + ctx->ws_bytes;
-  auto take = [&](size_t bytes) { top -= (bytes + 255) & ~(size_t)255; return (void*)top; };
-  bl::BIdx ix{(int32_t*)take((size_t)nPI * 4), (int32_t*)take((size_t)nPP * 4), (int32_t*)take((size_t)nPP * 4), (int32_t*)take((size_t)nPP * 4)};
-  uint32_t *k64 = (uint32_t*)take((size_t)nPI * 64 * 4), *ca = (uint32_t*)take((size_t)nPI * 128 * 4), *cb = (uint32_t*)take((size_t)nPP * 128 * 4);
-  uint8_t *g_ok = (uint8_t*)take(nPI), *ca_ok = (uint8_t*)take(nPI), *cb_ok = (uint8_t*)take(nPP);
-  ctx->ws_top = (size_t)(((char*)ctx->ws + ctx->ws_bytes) - top);
+  // own arrays first, kept (WsKeep) under the Paillier composites
+  MPE_TRY(ws_begin(ctx, st));
+  bl::BIdx ix{ws_array<int32_t>(ctx, nPI), ws_array<int32_t>(ctx, nPP), ws_array<int32_t>(ctx, nPP), ws_array<int32_t>(ctx, nPP)};
+  uint32_t *k64 = ws_array<uint32_t>(ctx, (size_t)nPI * 64), *ca = ws_array<uint32_t>(ctx, (size_t)nPI * 128), *cb = ws_array<uint32_t>(ctx, (size_t)nPP * 128);
+  uint8_t *g_ok = ws_array<uint8_t>(ctx, nPI), *ca_ok = ws_array<uint8_t>(ctx, nPI), *cb_ok = ws_array<uint8_t>(ctx, nPP);
+  MPE_TRY(ws_ok(ctx));
+  WsKeep keep(ctx->ws);
   int rc = MPE_OK;
   hipLaunchKernelGGL(bl::bidx_kernel, dim3(blocks_for(nPP > nPI ? nPP : nPI, 64)), dim3(64), 0, st, d, ix);
   hipLaunchKernelGGL(bl::gamma_check_kernel, dim3(blocks_for(nPI, 64)), dim3(64), 0, st, nPI, in->gamma, in->g_gamma, g_ok);
@@ -311,7 +309,6 @@ int mpe_gg20_blame5_sets(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, con
     hipLaunchKernelGGL(bl::blame5_combine_kernel, dim3(blocks_for(batch, 64)), dim3(64), 0, st, d, g_ok, ca_ok, cb_ok, in->k, in->gamma, in->beta_tag,
                        in->delta, d_bad_actors);
   }
-  ctx->ws_top = 0;
   if (rc != MPE_OK) return rc;
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) { mpe_set_error("mpe_gg20_blame5", e); return MPE_E_HIP; }
@@ -331,15 +328,13 @@ int mpe_gg20_blame6_sets(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, con
   hipStream_t st = (hipStream_t)stream;
   const int S = keys->S, P1 = S - 1, nPI = batch * S, nPP = nPI * P1;
   const bl::Dim d = bl::blame_dim(ctx, keys, batch, d_keyset, d_sigset);
-  const size_t own = ((size_t)nPI * (64 + 128) + (size_t)nPP * (128 + 16)) * 4 + ((size_t)nPI + 3 * (size_t)nPP) * 4 + (size_t)nPI * 2 + nPP + 16 * 256;   // BIdx: one [nPI] + three [nPP] arrays; 256 B slack per take()
-  MPE_TRY(ws_reserve(ctx, own + ws_need_encrypt(nPP) + (1u << 20), st));
-  char* top = (char*)ctx->ws + ctx->ws_bytes;
-  auto take = [&](size_t bytes) { top -= (bytes + 255) & ~(size_t)255; return (void*)top; };
-  bl::BIdx ix{(int32_t*)take((size_t)nPI * 4), (int32_t*)take((size_t)nPP * 4), (int32_t*)take((size_t)nPP * 4), (int32_t*)take((size_t)nPP * 4)};
-  uint32_t *k64 = (uint32_t*)take((size_t)nPI * 64 * 4), *ca = (uint32_t*)take((size_t)nPI * 128 * 4), *cb = (uint32_t*)take((size_t)nPP * 128 * 4),
-           *gni = (uint32_t*)take((size_t)nPP * 16 * 4);
-  uint8_t *dd_ok = (uint8_t*)take(nPI), *ca_ok = (uint8_t*)take(nPI), *mu_ok = (uint8_t*)take(nPP);
-  ctx->ws_top = (size_t)(((char*)ctx->ws + ctx->ws_bytes) - top);
+  MPE_TRY(ws_begin(ctx, st));
+  bl::BIdx ix{ws_array<int32_t>(ctx, nPI), ws_array<int32_t>(ctx, nPP), ws_array<int32_t>(ctx, nPP), ws_array<int32_t>(ctx, nPP)};
+  uint32_t *k64 = ws_array<uint32_t>(ctx, (size_t)nPI * 64), *ca = ws_array<uint32_t>(ctx, (size_t)nPI * 128), *cb = ws_array<uint32_t>(ctx, (size_t)nPP * 128),
+           *gni = ws_array<uint32_t>(ctx, (size_t)nPP * 16);
+  uint8_t *dd_ok = ws_array<uint8_t>(ctx, nPI), *ca_ok = ws_array<uint8_t>(ctx, nPI), *mu_ok = ws_array<uint8_t>(ctx, nPP);
+  MPE_TRY(ws_ok(ctx));
+  WsKeep keep(ctx->ws);
   hipLaunchKernelGGL(bl::bidx_kernel, dim3(blocks_for(nPP > nPI ? nPP : nPI, 64)), dim3(64), 0, st, d, ix);
   hipLaunchKernelGGL(bl::widen_kernel, dim3(blocks_for(nPI * 64, 256)), dim3(256), 0, st, nPI, in->k, k64);
   // Enc_ek_i(miu_ij; miu_randomness_ij) == m_b_mat[i][j].c   :327-339     and     Enc(k_i) == m_a_vec[i].c   :342-354
@@ -355,7 +350,6 @@ int mpe_gg20_blame6_sets(mpe_ctx* ctx, const mpe_gg20_keys* keys, int batch, con
                        bl::Ecddh{in->a1, in->a2, in->z}, dd_ok);
     hipLaunchKernelGGL(bl::blame6_combine_kernel, dim3(blocks_for(batch, 64)), dim3(64), 0, st, d, mu_ok, ca_ok, dd_ok, d_bad_actors);
   }
-  ctx->ws_top = 0;
   if (rc != MPE_OK) return rc;
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) { mpe_set_error("mpe_gg20_blame6", e); return MPE_E_HIP; }
@@ -369,9 +363,9 @@ int mpe_gg20_blame7(mpe_ctx* ctx, int n_signers, int batch, const mpe_gg20_blame
   using namespace mpe;
   hipStream_t st = (hipStream_t)stream;
   const int nPI = batch * n_signers;
-  MPE_TRY(ws_reserve(ctx, (size_t)nPI + 4096, st));
+  MPE_TRY(ws_begin(ctx, st));
   uint8_t* ok = ws_array<uint8_t>(ctx, nPI);
-  if (!ok) return MPE_E_NOMEM;
+  MPE_TRY(ws_ok(ctx));
   hipLaunchKernelGGL(bl::blame7_kernel, dim3(blocks_for(nPI, 64)), dim3(64), 0, st, batch, n_signers, in->s, in->r, in->R_dash, in->m, in->R, in->S, ok);
   hipLaunchKernelGGL(bl::mask_from_flags_kernel, dim3(blocks_for(batch, 64)), dim3(64), 0, st, batch, n_signers, ok, d_bad_actors);
   const hipError_t e = hipGetLastError();

@@ -55,7 +55,7 @@ static int bob_generate(mpe_ctx* ctx, const mpe_paillier* pk, const mpe_statemen
                         const int32_t* st_idx, const uint32_t* a_enc, const uint32_t* mta_enc, const uint32_t* b,
                         const uint32_t* beta_prim, const uint32_t* r, const mpe_bob_nonces* nn, int check,
                         const mpe_bob_proof* out, uint32_t* u_out, hipStream_t st) {
-  MPE_TRY(ws_reserve(ctx, (size_t)B * 2400 * 4 + 65536, st));
+  MPE_TRY(ws_begin(ctx, st));
   Seq q{ctx, st, B};
   const Rows ksel = sel_of(key_idx, pk->nkeys), ssel = sel_of(st_idx, stm->count);
   const Rows h1 = tab_rows(stm->h1, 64, st_idx, stm->count), h2 = tab_rows(stm->h2, 64, st_idx, stm->count);
@@ -106,7 +106,7 @@ static int bob_generate(mpe_ctx* ctx, const mpe_paillier* pk, const mpe_statemen
 static int bob_verify(mpe_ctx* ctx, const mpe_paillier* pk, const mpe_statements* stm, int B, const int32_t* key_idx,
                       const int32_t* st_idx, const uint32_t* a_enc, const uint32_t* mta_enc, const BobProofRows& pr,
                       const uint32_t* X, const uint32_t* u, uint8_t* ok, hipStream_t st) {
-  MPE_TRY(ws_reserve(ctx, (size_t)B * (3600 + 3 * CRT_WS_WORDS) * 4 + 65536, st));
+  MPE_TRY(ws_begin(ctx, st));
   Seq q{ctx, st, B};
   const Rows ksel = sel_of(key_idx, pk->nkeys), ssel = sel_of(st_idx, stm->count);
   const Rows h1 = tab_rows(stm->h1, 64, st_idx, stm->count), h2 = tab_rows(stm->h2, 64, st_idx, stm->count);

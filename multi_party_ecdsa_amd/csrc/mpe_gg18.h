@@ -298,12 +298,11 @@ int mpe_gg18_message_b(mpe_ctx* ctx, const mpe_paillier* pk, int batch, const in
   if (!d_key_idx && pk->nkeys != 1 && pk->nkeys < batch) return MPE_E_ARG;
   if (batch == 0) return MPE_OK;
   hipStream_t st = (hipStream_t)stream;
-  // beta_tag mod q at the top of the workspace (wiped with it), the ciphertext's composites below
-  MPE_TRY(mpe::ws_reserve(ctx, (size_t)batch * 3100 * 4 + (1u << 20), st));
-  char* top = (char*)ctx->ws + ctx->ws_bytes;
-  top -= ((size_t)batch * 8 * 4 + 255) & ~(size_t)255;
-  uint32_t* btq = (uint32_t*)top;
-  mpe::WsTop hold(ctx, top);
+  // beta_tag mod q in the workspace (wiped with it), kept under the ciphertext's composites
+  MPE_TRY(mpe::ws_begin(ctx, st));
+  uint32_t* btq = mpe::ws_array<uint32_t>(ctx, (size_t)batch * 8);
+  MPE_TRY(mpe::ws_ok(ctx));
+  mpe::WsKeep keep(ctx->ws);
   return mpe::mta_message_b_tail(ctx, pk, batch, d_key_idx, d_b, d_ca, d_r, d_beta_tag, d_nonce_b, d_nonce_bt, btq, d_cb, d_beta, b_proof, beta_tag_proof, st);
 }
 

@@ -973,7 +973,6 @@ __global__ void ca_all_from_local_kernel(int S, int B, const uint32_t* __restric
   const int ind = (int)(jb / B), b = (int)(jb % B);
   ca_all[g] = c_a[((size_t)b * S + ind) * 128 + w];
 }
-static size_t ws_need_inversion_ahead(const mpe_paillier* pk, size_t nVI) { return nVI * (128 + 128 + 1) * 4 + modinv_ws_words(pk->ms_nn, (int)nVI) * 4 + 16384; }
 
 // ---- beta^N of the PDL proofs ahead of round 4 (struct Ahead).  May the ladders start?  Round 0 adds "the ciphertexts' event exists", round 2 ensure_aux
 static bool pdl_ahead_eligible(const mpe_gg20_session* s, const Counts& c) {
@@ -1017,7 +1016,7 @@ static int round0(mpe_gg20_session* s, uint32_t* d_out, hipStream_t st) {
   // (r0_kernel — k_i, g^gamma_i, the commitments: 0.9 ms of EC — is launched BEHIND the fork below: the x^N ladders of a small batch need
   //  the nonces only and start at once; the encryption's tail waits for k_i through an event)
   // small batches: the encryption of k_i runs beside the first half of the range proofs (the proofs need c only for their
-  // transcript hash); both composites draw from ONE workspace reservation
+  // transcript hash); both composites draw from ONE use of the workspace (WsHold)
   const bool par = small_batch(ctx, c.nAP);
   const size_t nXN = c.nPI + c.nAP;
   // (round 6) lock-step signing: the inversion of the ciphertexts that round 1's verifiers need (6.7 ms of dependent short launches at
@@ -1027,12 +1026,9 @@ static int round0(mpe_gg20_session* s, uint32_t* d_out, hipStream_t st) {
   for (int l = 0; l < d.L && all_local_in_order; ++l) all_local_in_order = d.loc[l] == l;
   const bool ahead = par && a.lockstep && a.cinv && all_local_in_order && !ctx->no_r1_inversion_ahead && round1_merges(ctx, c);
   a.cinv_done = false;
-  if (par && rc == MPE_OK) {
-    rc = ws_reserve(ctx, ws_need_encrypt((int)c.nPI) + ws_need_alice_generate((int)c.nAP) + nXN * (64 + 128 + 1 + CRT_WS_WORDS) * 4 + 65536 +
-                         (ahead ? ws_need_inversion_ahead(K->pub, c.nVI) : 0), st);
-    if (rc == MPE_OK) ctx->ws_hold++;
-  }
+  if (par && rc == MPE_OK) rc = ws_begin(ctx, st);
   const bool held = par && rc == MPE_OK;
+  WsHold hold(ctx->ws, held);
   // ... and every x^N the key holders compute this round (the randomness of MessageA.c, the beta of each range proof) goes
   // through ONE launch: two concurrent launches of a few hundred waves each start on the same SIMDs of every CU and take
   // 15 ms where one launch of 1 024 waves takes 11.5
@@ -1050,7 +1046,7 @@ static int round0(mpe_gg20_session* s, uint32_t* d_out, hipStream_t st) {
     uint32_t* xs = ws_array<uint32_t>(ctx, nXN * 64);
     uint32_t* xn = ws_array<uint32_t>(ctx, nXN * 128);
     int32_t* kx = ws_array<int32_t>(ctx, nXN);
-    if (!xs || !xn || !kx) rc = MPE_E_NOMEM;
+    rc = ws_ok(ctx);
     if (rc == MPE_OK) {
       (void)hipMemcpyAsync(xs, Z.r_a, c.nPI * 64 * 4, hipMemcpyDeviceToDevice, sx);
       (void)hipMemcpyAsync(xs + c.nPI * 64, Z.al_beta, c.nAP * 64 * 4, hipMemcpyDeviceToDevice, sx);
@@ -1094,7 +1090,6 @@ static int round0(mpe_gg20_session* s, uint32_t* d_out, hipStream_t st) {
   g.join();                                       // (again: with c_ready the proofs waited for the event only)
   // ... and the FIRST ladder of the PDL proofs' beta^N, once the ciphertexts are there: the 5 ms before round 1's ladder hold an inversion and a hash
   if (rc == MPE_OK && c_ready && pdl_ahead_eligible(s, c)) { (void)hipStreamWaitEvent(ctx->aux[1], c_ready, 0); rc = pdl_ahead_queue(s, c, false); }
-  if (held) ctx->ws_hold--;
   gg_trace(s->ctx, st, "alice_generate", rc);
   PACK(c.nAP, n, n + 1, 0, SUB0, M0A.z, ap.z); PACK(c.nAP, n, n + 1, 0, SUB0, M0A.e, ap.e); PACK(c.nAP, n, n + 1, 0, SUB0, M0A.s, ap.s);
   PACK(c.nAP, n, n + 1, 0, SUB0, M0A.s1, ap.s1); PACK(c.nAP, n, n + 1, 0, SUB0, M0A.s2, ap.s2);
@@ -1115,9 +1110,6 @@ __global__ void gather_rows_kernel(int n, Rows src, int src_words, int words, ui
 // session instead of launches of 12 and of 4, so that e.g. 4 096 sessions are 65 536 items = two full passes of the chip where the
 // separate launches took 1.5 + 0.5 passes rounded up to whole trips (the pipelined engine's super-batches live at these sizes).
 // Operands are gathered into contiguous rows first (800 bytes per item against a ladder of ~2 500 multiplications modulo N^2).
-static size_t ws_need_round1_merged(const mpe_paillier* pk, size_t nVI, size_t nMB) {
-  return (nVI + nMB) * (size_t)(64 + 128 + 8 + 1 + 128) * 4 + nVI * (128 + 128 + 1) * 4 + modinv_ws_words(pk->ms_nn, (int)nVI) * 4 + 65536;
-}
 static int round1_merged_ladders(mpe_ctx* ctx, const mpe_paillier* pk, size_t nVI, const int32_t* kpub_vi, Rows cipher_vi, Rows s_vi, Rows e_vi,
                                  size_t nMB, const int32_t* kpub_mb, Rows ca_mb, const uint32_t* bsel, const uint32_t* mb_r,
                                  const uint32_t** m_vi, const uint8_t** inv_ok_vi, const uint32_t** x_mb, hipStream_t st,
@@ -1140,7 +1132,7 @@ static int round1_merged_ladders(mpe_ctx* ctx, const mpe_paillier* pk, size_t nV
   uint32_t* e2 = ws_array<uint32_t>(ctx, n * 8);
   int32_t* key = ws_array<int32_t>(ctx, n);
   uint32_t* out = ws_array<uint32_t>(ctx, n * 128);
-  if (!b1 || !b2 || !e2 || !key || !out) { mpe_set_error_msg("round1: workspace under-reserved"); return MPE_E_NOMEM; }
+  MPE_TRY(ws_ok(ctx));
   auto gather = [&](size_t cnt, Rows src, int sw, int words, uint32_t* dst) {
     if (cnt) hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((cnt * words + 255) / 256)), dim3(256), 0, st, (int)cnt, src, sw, words, dst);
   };
@@ -1173,7 +1165,7 @@ static int round1(mpe_gg20_session* s, const uint32_t* d_in, const int64_t* h_of
   uint32_t *Bpk = r1.Bpk, *BR = r1.BR, *Bz = r1.Bz, *BTpk = r1.BTpk, *BTR = r1.BTR, *BTz = r1.BTz;
   GG_LAUNCH(idx1_kernel, c.nVI, d, in0, sub0_vi);
   // small batches: the verification of the peers' range proofs and the construction of my MessageBs are independent
-  // (the reference runs them back to back inside MessageB::b) — two streams, one workspace reservation
+  // (the reference runs them back to back inside MessageB::b) — two streams, one use of the workspace (WsHold)
   const bool par = small_batch(ctx, c.nVI);
   // the ladders of both halves of the round in ONE launch (round1_merged_ladders): always for large batches, and for a small batch (par)
   // when its two ladder launches on forked streams would overfill the chip (more than 3/4 of the resident groups between them) — then
@@ -1184,16 +1176,14 @@ static int round1(mpe_gg20_session* s, const uint32_t* d_in, const int64_t* h_of
   const bool merged = round1_merges(ctx, c);
   const bool ahead = merged && s->ahead.cinv_done;            // round 0 inverted the ciphertexts already (lock-step signing of a small batch)
   s->ahead.cinv_done = false;
-  if (par && !merged && rc == MPE_OK) { rc = ws_reserve(ctx, ws_need_alice_verify((int)c.nVI) + ws_need_mul_add_enc((int)c.nMB), st); if (rc == MPE_OK) ctx->ws_hold++; }
-  bool held = par && !merged && rc == MPE_OK;
+  // the two halves share the workspace whenever they run side by side or hand each other the merged ladders' output
+  if ((par || merged) && rc == MPE_OK) rc = ws_begin(ctx, st);
+  const bool held = (par || merged) && rc == MPE_OK;
+  WsHold hold(ctx->ws, held);
   const uint32_t *m_vi = nullptr, *x_mb = nullptr;
   const uint8_t* inv_ok_vi = nullptr;
   AliceProofRows pr{rows(d_in + M0A.z.off, SUB0, sub0_vi), rows(d_in + M0A.e.off, SUB0, sub0_vi), rows(d_in + M0A.s.off, SUB0, sub0_vi),
                     rows(d_in + M0A.s1.off, SUB0, sub0_vi), rows(d_in + M0A.s2.off, SUB0, sub0_vi)};
-  if (merged && rc == MPE_OK) {
-    rc = ws_reserve(ctx, ws_need_alice_verify((int)c.nVI) + ws_need_mul_add_enc((int)c.nMB) + ws_need_round1_merged(K->pub, c.nVI, c.nMB), st);
-    if (rc == MPE_OK) { ctx->ws_hold++; held = true; }
-  }
   // small batches: the merged ladder launch goes to the forked stream, in front of MessageB's tail (which needs its x_mb), and the
   // verification's N~ side — fixed-base powers, z^e, an inversion: ~6 ms of short kernels at 1 024 sessions — starts at once on the
   // caller's stream BESIDE it: the ladder's waves are the older ones on their SIMDs and keep 0.92 of their speed (mpe_sched.h), the
@@ -1235,7 +1225,6 @@ static int round1(mpe_gg20_session* s, const uint32_t* d_in, const int64_t* h_of
     rc = alice_verify(ctx, K->pub, K->stm, (int)c.nVI, s->ix.kpub_vi, s->ix.st_vi, rows(s->ca_all, 128, s->ix.ca_vi), pr, ok_vi, st, Handed{m_vi, m_ready}, inv_ok_vi);
   gg_trace(s->ctx, st, "alice_verify", rc);
   g.join();
-  if (held) ctx->ws_hold--;
   GG_LAUNCH(status1_kernel, c.nPI, d, ok_vi, STAT(1), BADR(1));
   const int per = 2 * P1;
   PACK(c.nMB, per, per, 0, SUB1, M1.c, c_b); PACK(c.nMB, per, per, 0, SUB1, M1.b_pk, Bpk); PACK(c.nMB, per, per, 0, SUB1, M1.b_R, BR);

@@ -10,6 +10,25 @@
 #include "../../include/mpecdsa_hip.h"
 #include "mpe_kernels_heavy.h"
 #include "mpe_sched.h"
+#include "mpe_ws.h"
+
+void mpe_set_error(const char* what, hipError_t e);
+void mpe_set_error_msg(const char* what);
+
+namespace mpe {
+// the device side of the context workspace (mpe_ws.h)
+struct WsHip {
+  static void* alloc(size_t bytes) {
+    void* p = nullptr;
+    const hipError_t e = hipMalloc(&p, bytes);
+    if (e != hipSuccess) { mpe_set_error("hipMalloc(workspace)", e); return nullptr; }
+    return p;
+  }
+  static void free(void* p) { (void)hipFree(p); }
+  static void zero(void* p, size_t bytes, void* stream) { (void)hipMemsetAsync(p, 0, bytes, (hipStream_t)stream); }
+  static void sync(void* stream) { (void)hipStreamSynchronize((hipStream_t)stream); }
+};
+}  // namespace mpe
 
 struct mpe_ctx {
   int device = 0;
@@ -63,11 +82,9 @@ struct mpe_ctx {
   bool aux_ready = false;         // ensure_aux made the streams and events above
   bool allow_par = true;          // MPE_NO_PAR=1 switches the concurrency off (A/B runs)
   int par_items = 32768;          // composites fork when they have at most this many items
-  // bump-allocated workspace for the intermediates of composite operations (Paillier, proofs)
-  void* ws = nullptr;
-  size_t ws_bytes = 0, ws_off = 0;
-  int ws_hold = 0;                // > 0: a caller runs several composites concurrently out of ONE reservation: ws_reserve only checks
-  size_t ws_top = 0;              // bytes a composite keeps at the TOP of the workspace (its own arrays): never handed out, never moved
+  // bump-allocated workspace for the intermediates of composite operations (Paillier, proofs): grows by chaining blocks, settles into
+  // one (mpe_ws.h); mpe_ctx_wipe / mpe_ctx_scratch_audit / mpe_ctx_destroy cover every block
+  mpe::WsArena<mpe::WsHip> ws;
   // cached device memory of the GG20 round pipeline: one session object's state (mpe_gg20_session) and the message slabs of
   // mpe_gg20_sign — kept across calls so that a step does not pay hipMalloc / hipFree
   void* sess_buf = nullptr;
@@ -112,9 +129,6 @@ struct mpe_pairset {
   const uint32_t* mod_words = nullptr;   // [count][half_bits/32], owned by the caller (the key set)
 };
 
-void mpe_set_error(const char* what, hipError_t e);
-void mpe_set_error_msg(const char* what);
-
 namespace mpe {
 
 inline Rows rows(const uint32_t* p, int stride, const int32_t* idx = nullptr, int words = 0) {
@@ -149,9 +163,13 @@ int pair_modexp_2048(mpe_ctx* ctx, const mpe_pairset* ps, int batch, Rows mod_se
 int pair_modexp_1024(mpe_ctx* ctx, const mpe_pairset* ps, int batch, Rows mod_sel, Rows base, Rows exps, int exp_words,
                      Rows base2, Rows exps2, int exp2_words, int half, uint32_t* out, hipStream_t st, int public_exp);
 
-// workspace: reserve once per composite call (may reallocate -> synchronises the stream), then bump-allocate
-int ws_reserve(mpe_ctx* ctx, size_t bytes, hipStream_t st);
-void* ws_alloc(mpe_ctx* ctx, size_t bytes);
+// workspace (mpe_ws.h): ws_begin once per composite call (synchronises the stream when the last use left more than one block), then
+// bump-allocate (256-byte aligned); ws_ok once behind the allocations of code that does not go through Seq, before its first launch
+inline int ws_begin(mpe_ctx* ctx, hipStream_t st) { return ctx->ws.begin(st) ? MPE_OK : MPE_E_NOMEM; }
+inline void* ws_alloc(mpe_ctx* ctx, size_t bytes) { return ctx->ws.alloc(bytes); }
+inline int ws_ok(const mpe_ctx* ctx) { return ctx->ws.failed ? MPE_E_NOMEM : MPE_OK; }
+using WsHold = WsArena<WsHip>::Hold;       // WsHold hold(ctx->ws, on);
+using WsKeep = WsArena<WsHip>::Keep;       // WsKeep keep(ctx->ws);
 // window-table scratch of the stream slot `st` belongs to (nullptr + error set when it cannot be grown)
 uint32_t* tables_for(mpe_ctx* ctx, size_t need, hipStream_t st);
 bool ensure_aux(mpe_ctx* ctx);
@@ -164,12 +182,6 @@ struct Fork {
   hipStream_t s(int i) const { return (on && i > 0) ? ctx->aux[first + i - 1] : main; }
   void join();
   void branch_done_wait(int i, hipStream_t waiter);     // `waiter` waits for what branch i has queued so far
-};
-// a composite's own arrays at the top of the workspace: reserved against ws_alloc / ws_reserve until the composite returns
-struct WsTop {
-  mpe_ctx* c;
-  WsTop(mpe_ctx* ctx, const char* top) : c(ctx) { c->ws_top = (size_t)(((const char*)c->ws + c->ws_bytes) - top); }
-  ~WsTop() { c->ws_top = 0; }
 };
 template <class T>
 inline T* ws_array(mpe_ctx* ctx, size_t count) { return (T*)ws_alloc(ctx, count * sizeof(T)); }

@@ -184,14 +184,14 @@ int mpe_correct_key_prove(mpe_ctx* ctx, const mpe_paillier* sk, uint32_t* d_sigm
   if (!sk->has_private) { mpe_set_error_msg("mpe_correct_key_prove: key set has no private part"); return MPE_E_ARG; }
   hipStream_t st = (hipStream_t)stream;
   const int nk = sk->nkeys, M = kg::CK_M2, n = nk * M;
-  MPE_TRY(ws_reserve(ctx, ((size_t)n * (64 * 4 + 8 + 1) + (size_t)nk * 64 * 5 + modinv_ws_words(sk->ms_n, nk)) * 4 + 65536, st));
+  MPE_TRY(ws_begin(ctx, st));
   int32_t* key_of = ws_array<int32_t>(ctx, n);
   uint32_t *lo = ws_array<uint32_t>(ctx, (size_t)n * 64), *hi = ws_array<uint32_t>(ctx, (size_t)n * 8), *hiT = ws_array<uint32_t>(ctx, (size_t)n * 64),
            *lor = ws_array<uint32_t>(ctx, (size_t)n * 64), *rho = ws_array<uint32_t>(ctx, (size_t)n * 64), *two = ws_array<uint32_t>(ctx, (size_t)nk * 64),
            *T = ws_array<uint32_t>(ctx, (size_t)nk * 64), *phi = ws_array<uint32_t>(ctx, (size_t)nk * 64), *u = ws_array<uint32_t>(ctx, (size_t)nk * 64),
            *d = ws_array<uint32_t>(ctx, (size_t)nk * 64);
   uint8_t* ok = ws_array<uint8_t>(ctx, ((size_t)nk + 255) & ~(size_t)255);
-  if (!key_of || !lo || !hi || !hiT || !lor || !rho || !two || !T || !phi || !u || !d || !ok) { mpe_set_error_msg("correct_key_prove: workspace"); return MPE_E_NOMEM; }
+  MPE_TRY(ws_ok(ctx));
   const Rows ksel{nullptr, key_of, 0, 0};
   hipLaunchKernelGGL(kg::iota_div_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, st, n, M, key_of);
   hipLaunchKernelGGL(kg::ck_rho_kernel, dim3(blocks_for(n, 64)), dim3(64), 0, st, nk, ctx->enc, sk->N, lo, hi);
@@ -222,12 +222,12 @@ int mpe_composite_dlog_prove(mpe_ctx* ctx, int batch, const uint32_t* d_N, const
   hipStream_t st = (hipStream_t)stream;
   mpe_modset* ms = nullptr;
   MPE_TRY(modset_create_dev(ctx, 2048, batch, d_N, &ms, st));
-  int rc = ws_reserve(ctx, (size_t)batch * (64 + 8) * 4 + 65536, st);
+  int rc = ws_begin(ctx, st);
   if (rc != MPE_OK) { mpe_modset_destroy(ms); return rc; }
   Seq q{ctx, st, batch};
   uint32_t* e = q.words(8);
   rc = launch_modexp(ctx, ms, batch, rows(nullptr, 1), rows(d_g, 64), no_rows(), rows(d_r, 16), 16, d_x, st);
-  q.rc = rc;
+  if (rc != MPE_OK) q.rc = rc;
   HashDesc d;
   d.n = 4;
   { const HashField canon[4] = {hf(rows(d_x, 64), 64), hf(rows(d_g, 64), 64), hf(rows(d_N, 64), 64), hf(rows(d_ni, 64), 64)};   // (x, g, N, ni)
@@ -248,13 +248,13 @@ int mpe_correct_key_verify(mpe_ctx* ctx, int batch, const uint32_t* d_N, const u
   const int M = kg::CK_M2, n = batch * M;
   mpe_modset* ms = nullptr;
   MPE_TRY(modset_create_dev(ctx, 2048, batch, d_N, &ms, st));
-  int rc = ws_reserve(ctx, ((size_t)n * (64 * 5 + 8 + 1) + (size_t)batch * 64 * 3) * 4 + 65536, st);
+  int rc = ws_begin(ctx, st);
   if (rc != MPE_OK) { mpe_modset_destroy(ms); return rc; }
   int32_t* key_of = ws_array<int32_t>(ctx, n);
   uint32_t *lo = ws_array<uint32_t>(ctx, (size_t)n * 64), *hi = ws_array<uint32_t>(ctx, (size_t)n * 8), *sn = ws_array<uint32_t>(ctx, (size_t)n * 64),
            *hiT = ws_array<uint32_t>(ctx, (size_t)n * 64), *lor = ws_array<uint32_t>(ctx, (size_t)n * 64), *two = ws_array<uint32_t>(ctx, (size_t)batch * 64),
            *T = ws_array<uint32_t>(ctx, (size_t)batch * 64);
-  if (!key_of || !lo || !hi || !sn || !hiT || !lor || !two || !T) { mpe_modset_destroy(ms); mpe_set_error_msg("correct_key: workspace"); return MPE_E_NOMEM; }
+  if ((rc = ws_ok(ctx)) != MPE_OK) { mpe_modset_destroy(ms); return rc; }
   const Rows ksel{nullptr, key_of, 0, 0};
   hipLaunchKernelGGL(kg::iota_div_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, st, n, M, key_of);
   hipLaunchKernelGGL(kg::ck_small_factor_kernel, dim3(blocks_for(batch, 64)), dim3(64), 0, st, batch, d_N, d_ok);
@@ -283,7 +283,7 @@ int mpe_composite_dlog_verify(mpe_ctx* ctx, int batch, const uint32_t* d_N, cons
   hipStream_t st = (hipStream_t)stream;
   mpe_modset* ms = nullptr;
   MPE_TRY(modset_create_dev(ctx, 2048, batch, d_N, &ms, st));
-  int rc = ws_reserve(ctx, ((size_t)batch * (64 * 6 + 8) + modinv_ws_words(ms, batch) * 2) * 4 + 65536, st);
+  int rc = ws_begin(ctx, st);
   if (rc != MPE_OK) { mpe_modset_destroy(ms); return rc; }
   Seq q{ctx, st, batch};
   const Rows sel = rows(nullptr, 1);                                    // modulus i for item i

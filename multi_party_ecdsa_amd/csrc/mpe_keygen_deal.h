@@ -129,10 +129,10 @@ int mpe_keygen_verify_round3(mpe_ctx* ctx, int batch, int n_parties, int t1, con
   if (batch == 0) return MPE_OK;
   hipStream_t st = (hipStream_t)stream;
   const int S = batch / n_parties;
-  MPE_TRY(ws_reserve(ctx, (size_t)S * t1 * 64 + (size_t)S * 4 + (size_t)batch + 65536, st));
+  MPE_TRY(ws_begin(ctx, st));
   uint32_t *glob = ws_array<uint32_t>(ctx, (size_t)S * t1 * 16), *sess_bad = ws_array<uint32_t>(ctx, (size_t)S);
   uint8_t* dl_ok = ws_array<uint8_t>(ctx, (size_t)batch);
-  if (!glob || !sess_bad || !dl_ok) { mpe_set_error_msg("keygen round3: workspace"); return MPE_E_NOMEM; }
+  MPE_TRY(ws_ok(ctx));
   (void)hipMemsetAsync(sess_bad, 0, (size_t)S * 4, st);
   if (d_bad_actors) (void)hipMemsetAsync(d_bad_actors, 0, (size_t)S * 4, st);
   MPE_LAUNCH_1D(dlog_verify_kernel, batch, st, batch, ctx->enc, d_pk, d_R, d_z, dl_ok);                     // :419, the device code of mpe_dlog_verify

@@ -17,28 +17,6 @@ void mpe_set_error_msg(const char* what) { g_last_error = what; }
 // =============================================================================================
 namespace mpe {
 
-int ws_reserve(mpe_ctx* ctx, size_t bytes, hipStream_t st) {
-  if (ctx->ws_hold) {               // several composites share one reservation (they run concurrently): no reset, no move
-    if (ctx->ws_off + bytes + ctx->ws_top > ctx->ws_bytes) { mpe_set_error_msg("workspace: the shared reservation is too small"); return MPE_E_NOMEM; }
-    return MPE_OK;
-  }
-  ctx->ws_off = 0;
-  if (bytes + ctx->ws_top <= ctx->ws_bytes) return MPE_OK;
-  if (ctx->ws_top) { mpe_set_error_msg("workspace: cannot grow while a caller keeps arrays at its top"); return MPE_E_NOMEM; }
-  if (ctx->ws) { (void)hipStreamSynchronize(st); (void)hipFree(ctx->ws); ctx->ws = nullptr; ctx->ws_bytes = 0; }
-  const size_t want = bytes + (bytes >> 2) + (1u << 20);
-  hipError_t e = hipMalloc(&ctx->ws, want);
-  if (e != hipSuccess) { mpe_set_error("hipMalloc(workspace)", e); return MPE_E_NOMEM; }
-  ctx->ws_bytes = want;
-  return MPE_OK;
-}
-void* ws_alloc(mpe_ctx* ctx, size_t bytes) {
-  const size_t off = (ctx->ws_off + 255) & ~(size_t)255;
-  if (off + bytes + ctx->ws_top > ctx->ws_bytes) return nullptr;     // ws_reserve under-estimated: a library bug
-  ctx->ws_off = off + bytes;
-  return (char*)ctx->ws + off;
-}
-
 static int slot_of(const mpe_ctx* ctx, hipStream_t st) {
   for (int i = 0; i < 3; ++i) if (ctx->aux[i] && st == ctx->aux[i]) return i + 1;
   return 0;
@@ -438,11 +416,15 @@ int mpe_ctx_create(mpe_ctx** out, int device) {
   return MPE_OK;
 }
 
-// every device buffer the context owns: first what mpe_ctx_wipe zeroes (window tables, workspace), then the session arena and the message slabs
-struct CtxBuf { void* p; size_t bytes; }; constexpr int CTX_SCRATCH = 5, CTX_BUFS = 7;
-static std::array<CtxBuf, CTX_BUFS> ctx_bufs(const mpe_ctx* ctx) {
-  return {{{ctx->tables[0], ctx->tables_bytes[0]}, {ctx->tables[1], ctx->tables_bytes[1]}, {ctx->tables[2], ctx->tables_bytes[2]},
-           {ctx->tables[3], ctx->tables_bytes[3]}, {ctx->ws, ctx->ws_bytes}, {ctx->sess_buf, ctx->sess_bytes}, {ctx->slab_buf, ctx->slab_bytes}}};
+// every device buffer the context owns: first what mpe_ctx_wipe zeroes (window tables, every block of the workspace), then, with `all`,
+// the session arena and the message slabs
+struct CtxBuf { void* p; size_t bytes; };
+static std::vector<CtxBuf> ctx_bufs(const mpe_ctx* ctx, bool all) {
+  std::vector<CtxBuf> b;
+  for (int i = 0; i < 4; ++i) b.push_back({ctx->tables[i], ctx->tables_bytes[i]});
+  for (const auto& blk : ctx->ws.blocks) b.push_back({blk.p, blk.bytes});
+  if (all) { b.push_back({ctx->sess_buf, ctx->sess_bytes}); b.push_back({ctx->slab_buf, ctx->slab_bytes}); }
+  return b;
 }
 
 // Zeroes every scratch buffer the context owns (window tables, composite workspace): they hold powers of secret bases and
@@ -450,8 +432,7 @@ static std::array<CtxBuf, CTX_BUFS> ctx_bufs(const mpe_ctx* ctx) {
 int mpe_ctx_wipe(mpe_ctx* ctx, void* stream) {
   if (!ctx) return MPE_E_ARG;
   hipStream_t st = (hipStream_t)stream;
-  const auto b = ctx_bufs(ctx);
-  for (int i = 0; i < CTX_SCRATCH; ++i) if (b[i].p) (void)hipMemsetAsync(b[i].p, 0, b[i].bytes, st);
+  for (const CtxBuf& b : ctx_bufs(ctx, false)) if (b.p) (void)hipMemsetAsync(b.p, 0, b.bytes, st);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) { mpe_set_error("mpe_ctx_wipe", e); return MPE_E_HIP; }
   return MPE_OK;
@@ -473,12 +454,11 @@ int mpe_ctx_scratch_audit(mpe_ctx* ctx, uint64_t* nonzero_words, uint64_t* total
   hipError_t e = hipMalloc((void**)&d, 8);
   if (e != hipSuccess) { mpe_set_error("hipMalloc(audit)", e); return MPE_E_NOMEM; }
   (void)hipMemsetAsync(d, 0, 8, st);
-  const auto b = ctx_bufs(ctx);
   uint64_t tot = 0;
-  for (int i = 0; i < CTX_BUFS; ++i) {
-    if (!b[i].p || !b[i].bytes) continue;
-    tot += b[i].bytes;
-    hipLaunchKernelGGL(count_nonzero_kernel, dim3(4096), dim3(256), 0, st, (const uint32_t*)b[i].p, b[i].bytes / 4, d);
+  for (const CtxBuf& b : ctx_bufs(ctx, true)) {
+    if (!b.p || !b.bytes) continue;
+    tot += b.bytes;
+    hipLaunchKernelGGL(count_nonzero_kernel, dim3(4096), dim3(256), 0, st, (const uint32_t*)b.p, b.bytes / 4, d);
   }
   unsigned long long h = 0;
   e = hipMemcpyAsync(&h, d, 8, hipMemcpyDeviceToHost, st);
@@ -492,11 +472,9 @@ int mpe_ctx_scratch_audit(mpe_ctx* ctx, uint64_t* nonzero_words, uint64_t* total
 
 int mpe_ctx_destroy(mpe_ctx* ctx) {
   if (!ctx) return MPE_E_ARG;
-  (void)mpe_ctx_wipe(ctx, nullptr);
-  const auto b = ctx_bufs(ctx);
-  for (int i = CTX_SCRATCH; i < CTX_BUFS; ++i) if (b[i].p) (void)hipMemsetAsync(b[i].p, 0, b[i].bytes, nullptr);
+  for (const CtxBuf& b : ctx_bufs(ctx, true)) if (b.p) (void)hipMemsetAsync(b.p, 0, b.bytes, nullptr);
   (void)hipDeviceSynchronize();
-  for (int i = 0; i < CTX_BUFS; ++i) if (b[i].p) (void)hipFree(b[i].p);
+  for (const CtxBuf& b : ctx_bufs(ctx, true)) if (b.p) (void)hipFree(b.p);
   if (ctx->aux_ready) {
     for (int i = 0; i < 3; ++i) { (void)hipStreamDestroy(ctx->aux[i]); (void)hipEventDestroy(ctx->ev_join[i]); }
     for (int i = 0; i < 2; ++i) (void)hipEventDestroy(ctx->ev_fork[i]);

@@ -154,12 +154,12 @@ int mpe_lindell_partial_sig(mpe_ctx* ctx, const mpe_paillier* pk, int batch, con
   if (!d_key_idx && pk->nkeys != 1 && pk->nkeys < batch) return MPE_E_ARG;
   if (batch == 0) return MPE_OK;
   hipStream_t st = (hipStream_t)stream;
-  // own arrays at the top of the workspace, the composite below (the scheme of mpe_mta.h)
-  MPE_TRY(mpe::ws_reserve(ctx, (size_t)batch * (128 * 3 + 64 + 8 + 64) * 4 + (1u << 20), st));
-  char* top = (char*)ctx->ws + ctx->ws_bytes;
-  uint32_t* ps = (uint32_t*)(top -= ((size_t)batch * 64 * 4 + 255) & ~(size_t)255);
-  uint32_t* v = (uint32_t*)(top -= ((size_t)batch * 8 * 4 + 255) & ~(size_t)255);
-  mpe::WsTop hold(ctx, top);
+  // own arrays first, kept under the composite (the scheme of mpe_mta.h)
+  MPE_TRY(mpe::ws_begin(ctx, st));
+  uint32_t* ps = mpe::ws_array<uint32_t>(ctx, (size_t)batch * 64);
+  uint32_t* v = mpe::ws_array<uint32_t>(ctx, (size_t)batch * 8);
+  MPE_TRY(mpe::ws_ok(ctx));
+  mpe::WsKeep keep(ctx->ws);
   MPE_LAUNCH_1D(mpe::lindell_p2_prep_kernel, batch, st, batch, d_k2, d_x2, d_R1, d_msg, d_rho, ps, v);
   // c3 = c_key^v * Enc(ps; r): Paillier::encrypt, Paillier::mul, Paillier::add   :408-421
   return mpe::paillier_mul_add_enc(ctx, pk, batch, d_key_idx, mpe::rows(d_c_key, 128), mpe::rows(v, 8), 8, ps, d_r, d_c3, st);
@@ -172,10 +172,10 @@ int mpe_lindell_sign(mpe_ctx* ctx, const mpe_paillier* sk, int batch, const int3
   if (!d_key_idx && sk->nkeys != 1 && sk->nkeys < batch) return MPE_E_ARG;
   if (batch == 0) return MPE_OK;
   hipStream_t st = (hipStream_t)stream;
-  MPE_TRY(mpe::ws_reserve(ctx, (size_t)batch * (2 * (3 + 64 + 32 + 64 + 64) + 64) * 4 + (1u << 20), st));
-  char* top = (char*)ctx->ws + ctx->ws_bytes;
-  uint32_t* s_tag = (uint32_t*)(top -= ((size_t)batch * 64 * 4 + 255) & ~(size_t)255);
-  mpe::WsTop hold(ctx, top);
+  MPE_TRY(mpe::ws_begin(ctx, st));
+  uint32_t* s_tag = mpe::ws_array<uint32_t>(ctx, (size_t)batch * 64);
+  MPE_TRY(mpe::ws_ok(ctx));
+  mpe::WsKeep keep(ctx->ws);
   MPE_TRY(mpe::paillier_decrypt(ctx, sk, batch, d_key_idx, mpe::rows(d_c3, 128), s_tag, st));               // :538-542
   MPE_LAUNCH_1D(mpe::lindell_p1_finish_kernel, batch, st, batch, s_tag, d_k1, d_R2, d_r, d_s, d_recid);
   return MPE_OK;

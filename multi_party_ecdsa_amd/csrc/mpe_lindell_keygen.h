@@ -219,11 +219,8 @@ int mpe_lindell_ntilde_generate(mpe_ctx* ctx, int count, const uint8_t* h_seed32
   const int cap = max_attempts ? max_attempts : pr::DEFAULT_MAX_ATTEMPTS;
   auto sid = [&](int f) { return counter | ((uint64_t)f << 56); };
   // p~, q~, phi, the 9-word sampling rows of xhi and h1^-1 live in the context workspace (mpe_ctx_wipe covers them); the two prime
-  // searches and the inversion allocate below these arrays, one after the other
-  mpe_modset shape;                                             // what modinv_ws_words reads of the moduli set created below
-  shape.bits = 2048; shape.K = Cfg2048::K; shape.count = count;
-  const size_t own = (size_t)count * (32 + 32 + 64 * 3 + 9 + 1) * 4 + (size_t)count + 16 * 256;
-  MPE_TRY(ws_reserve(ctx, own + 2 * pr::search_ws_bytes(count) + modinv_ws_words(&shape, count) * 4, st));
+  // searches and the inversion allocate behind these arrays, one after the other
+  MPE_TRY(ws_begin(ctx, st));
   uint32_t* pt = ws_array<uint32_t>(ctx, (size_t)count * 32);
   uint32_t* qt = ws_array<uint32_t>(ctx, (size_t)count * 32);
   uint32_t* nt_ms = ws_array<uint32_t>(ctx, (size_t)count * 64);
@@ -233,7 +230,7 @@ int mpe_lindell_ntilde_generate(mpe_ctx* ctx, int count, const uint8_t* h_seed32
   uint32_t* two256 = ws_array<uint32_t>(ctx, 9);
   int32_t* bad = ws_array<int32_t>(ctx, count);
   uint8_t* inv_ok = ws_array<uint8_t>(ctx, count);
-  if (!pt || !qt || !nt_ms || !phi || !h1inv || !xhi9 || !two256 || !bad || !inv_ok) return MPE_E_NOMEM;
+  MPE_TRY(ws_ok(ctx));
   MPE_TRY(pr::search_primes(ctx, count, key, sid(6), cap, pt, nullptr, nullptr, st));                          // Paillier::keypair()  :597
   MPE_TRY(pr::search_primes(ctx, count, key, sid(7), cap, qt, nullptr, nullptr, st));
   MPE_LAUNCH_1D(pr::nt_setup_kernel, count, st, count, pt, qt, nt_ms, phi, bad);                               // N~, phi  :599

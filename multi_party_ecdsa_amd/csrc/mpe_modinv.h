@@ -382,19 +382,14 @@ static ModsetView inv_view_of(const mpe_modset* ms) {
   return v;
 }
 
-static size_t modinv_ws_words(const mpe_modset* ms, int B) {
-  const int K = ms->K, K32 = ms->bits / 32, maxch = B / 16 + (ms->count < B ? ms->count : B) + 2;     // chunks <= B / chunk + the moduli that have items
-  return (size_t)B * (2 * K + 3) + (size_t)maxch * (2 * K32 + 8) + ms->count + 4096;
-}
-
-// out/ok: [B]; scratch comes from the context workspace (callers include modinv_ws_words in their reservation)
+// out/ok: [B]; scratch comes from the context workspace
 template <class C, typename LT>
 static int launch_modinv_batched(mpe_ctx* ctx, const mpe_modset* ms, int B, Rows mod_sel, Rows a, uint32_t* out, uint8_t* ok,
                                  hipStream_t st) {
   // chunk = items inverted through ONE real inversion: 64 for throughput; a small batch is latency-bound, and the up / down
   // sweeps are `chunk` sequential multiplications, so it takes short chunks (more, but concurrent, wave gcds)
   const int CH = B <= ctx->par_items ? 16 : 64;
-  const int nmod = ms->count, maxch = B / CH + (nmod < B ? nmod : B) + 2;
+  const int nmod = ms->count, maxch = B / CH + (nmod < B ? nmod : B) + 2;     // chunks <= B / chunk + the moduli that have items
   InvPlan p;
   p.cnt = ws_array<int32_t>(ctx, nmod + 1);
   p.rank = ws_array<int32_t>(ctx, B);
@@ -409,10 +404,7 @@ static int launch_modinv_batched(mpe_ctx* ctx, const mpe_modset* ms, int B, Rows
   uint32_t* Tinv = ws_array<uint32_t>(ctx, (size_t)maxch * C::K32);
   uint8_t* Tok = ws_array<uint8_t>(ctx, maxch);
   uint8_t* need = ws_array<uint8_t>(ctx, B);
-  if (!p.cnt || !p.rank || !p.perm || !p.ch_start || !p.ch_len || !p.ch_mod || !p.nch || !xm || !pre || !T || !Tinv || !Tok || !need) {
-    mpe_set_error_msg("modinv: workspace under-reserved");
-    return MPE_E_NOMEM;
-  }
+  MPE_TRY(ws_ok(ctx));
   (void)hipMemsetAsync(p.cnt, 0, (size_t)(nmod + 1) * 4, st);
   (void)hipMemsetAsync(need, 0, (size_t)B, st);
   (void)hipMemsetAsync(ok, 0, (size_t)B, st);

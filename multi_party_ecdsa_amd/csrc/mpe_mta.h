@@ -78,14 +78,14 @@ int mpe_mta_message_a(mpe_ctx* ctx, const mpe_paillier* pk, const mpe_statements
   if (batch == 0) return MPE_OK;
   hipStream_t st = (hipStream_t)stream;
   const int nst = stm->count, total = batch * nst;
-  // own arrays at the top of the workspace, composites below (same scheme as the GG20 pipeline)
-  MPE_TRY(mpe::ws_reserve(ctx, ((size_t)total * 2100 + (size_t)batch * 1000) * 4 + (1u << 20), st));
-  char* top = (char*)ctx->ws + ctx->ws_bytes;
-  int32_t* b_of = (int32_t*)(top -= ((size_t)total * 4 + 255) & ~(size_t)255);
-  int32_t* st_of = (int32_t*)(top -= ((size_t)total * 4 + 255) & ~(size_t)255);
-  int32_t* key_it = (int32_t*)(top -= ((size_t)total * 4 + 255) & ~(size_t)255);
-  uint32_t* a64 = (uint32_t*)(top -= ((size_t)batch * 64 * 4 + 255) & ~(size_t)255);
-  mpe::WsTop hold(ctx, top);
+  // own arrays first, kept while the composites below take and reuse what lies behind them
+  MPE_TRY(mpe::ws_begin(ctx, st));
+  int32_t* b_of = mpe::ws_array<int32_t>(ctx, total);
+  int32_t* st_of = mpe::ws_array<int32_t>(ctx, total);
+  int32_t* key_it = mpe::ws_array<int32_t>(ctx, total);
+  uint32_t* a64 = mpe::ws_array<uint32_t>(ctx, (size_t)batch * 64);
+  MPE_TRY(mpe::ws_ok(ctx));
+  mpe::WsKeep keep(ctx->ws);
   MPE_LAUNCH_1D(mpe::mta_idx_kernel, total, st, total, nst, pk->nkeys, d_key_idx, b_of, st_of, key_it);
   // c = Enc(a; r)   (:68-75)   a zero-extended to the plaintext width
   (void)hipMemsetAsync(a64, 0, (size_t)batch * 64 * 4, st);
@@ -108,15 +108,14 @@ int mpe_mta_message_b(mpe_ctx* ctx, const mpe_paillier* pk, const mpe_statements
   if (batch == 0) return MPE_OK;
   hipStream_t st = (hipStream_t)stream;
   const int nst = stm->count, total = batch * nst;
-  MPE_TRY(mpe::ws_reserve(ctx, ((size_t)total * 2400 + (size_t)batch * 700) * 4 + (1u << 20), st));
-  char* top = (char*)ctx->ws + ctx->ws_bytes;
-  auto take = [&](size_t bytes) { top -= (bytes + 255) & ~(size_t)255; return (void*)top; };
-  int32_t* b_of = (int32_t*)take((size_t)total * 4);
-  int32_t* st_of = (int32_t*)take((size_t)total * 4);
-  int32_t* key_it = (int32_t*)take((size_t)total * 4);
-  uint8_t* ok_items = (uint8_t*)take((size_t)total);
-  uint32_t* btq = (uint32_t*)take((size_t)batch * 8 * 4);
-  mpe::WsTop hold(ctx, top);
+  MPE_TRY(mpe::ws_begin(ctx, st));
+  int32_t* b_of = mpe::ws_array<int32_t>(ctx, total);
+  int32_t* st_of = mpe::ws_array<int32_t>(ctx, total);
+  int32_t* key_it = mpe::ws_array<int32_t>(ctx, total);
+  uint8_t* ok_items = mpe::ws_array<uint8_t>(ctx, total);
+  uint32_t* btq = mpe::ws_array<uint32_t>(ctx, (size_t)batch * 8);
+  MPE_TRY(mpe::ws_ok(ctx));
+  mpe::WsKeep keep(ctx->ws);
   MPE_LAUNCH_1D(mpe::mta_idx_kernel, total, st, total, nst, pk->nkeys, d_key_idx, b_of, st_of, key_it);
   // verify Alice's range proofs against every statement   (:119-131); any failure -> Err(InvalidKey) -> ok = 0
   MPE_TRY(mpe::alice_verify(ctx, pk, stm, total, key_it, st_of, mpe::rows(d_ca, 128, b_of), mpe::dense(range_proofs), ok_items, st));

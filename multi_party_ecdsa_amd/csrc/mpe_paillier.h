@@ -256,9 +256,10 @@ static int paillier_create(mpe_ctx* ctx, int nk, const uint32_t* d_N, const uint
     if ((rc = modset_create_dev(ctx, 2048, (int)nk2, pk->sq64, &pk->ms_pp, st)) != MPE_OK) return fail(rc);
     if ((rc = modset_create_dev(ctx, 2048, (int)nk2, pk->pq64, &pk->ms_p, st)) != MPE_OK) return fail(rc);
     // (other prime)^(own-2) mod own = (other prime)^-1 mod own   (Fermat; own is prime)
-    if ((rc = ws_reserve(ctx, nk2 * 128 * 4 + 4096, st)) != MPE_OK) return fail(rc);
+    if ((rc = ws_begin(ctx, st)) != MPE_OK) return fail(rc);
     uint32_t* inv_other = ws_array<uint32_t>(ctx, nk2 * 64);
     uint32_t* inv_sq = ws_array<uint32_t>(ctx, nk2 * 64);
+    if ((rc = ws_ok(ctx)) != MPE_OK) return fail(rc);
     rc = launch_modexp(ctx, pk->ms_p, (int)nk2, rows(nullptr, 1), rows(pk->pq32, 32, pk->swap_idx, 32), no_rows(),
                        rows(pk->em2, 32), 32, inv_other, st);
     if (rc != MPE_OK) return fail(rc);
@@ -293,15 +294,12 @@ static Rows key_rows(const mpe_paillier* pk, const uint32_t* table, int stride, 
   return Rows{table, nullptr, pk->nkeys == 1 ? 0 : stride, words};
 }
 
-// words of workspace per item that modexp_nn takes when it goes through the CRT
-constexpr size_t CRT_WS_WORDS = 2 + 2 * 64 + 2 * 128 + 192;
-
 // base^exps mod N_k^2.  holder = the caller is the owner of the key (it may use p and q): the two halves
 // mod p^2 | q^2 on the 2048-bit engine, then  x = x_p E_p + x_q E_q mod N^2.  Same residue as the direct form.
 // pow_n: the exponent is N itself.  Then x^N = (x^q)^p and x^q = a (mod p) with a = x^(q mod (p-1)) mod p gives
 // x^N = a^p (mod p^2): a 1024-bit exponentiation modulo p (one pass per squaring) and one modulo p^2 (two passes)
 // instead of a 2048-bit one modulo p^2 — a quarter less work, the same residue.
-// scratch: 2 B x (1 + 64 + 128) words of the caller's own (a launch that outlives the workspace reservation it was queued under: the PDL
+// scratch: 2 B x (1 + 64 + 128) words of the caller's own (a launch that outlives the workspace use it was queued under: the PDL
 // proofs' beta^N started rounds ahead, mpe_gg20.h round2); nullptr: the context workspace
 static inline size_t modexp_nn_scratch_words(size_t B) { return 2 * B * (1 + 64 + 128) + 256; }
 static int modexp_nn(mpe_ctx* ctx, const mpe_paillier* pk, int B, Rows ksel, Rows base, Rows exps, int ew, bool holder,
@@ -316,7 +314,7 @@ static int modexp_nn(mpe_ctx* ctx, const mpe_paillier* pk, int B, Rows ksel, Row
   int32_t* half_of = scratch ? (int32_t*)scratch : ws_array<int32_t>(ctx, B2);
   uint32_t* u = scratch ? scratch + (((size_t)B2 + 63) & ~(size_t)63) : ws_array<uint32_t>(ctx, (size_t)B2 * 64);
   uint32_t* y = scratch ? u + (size_t)B2 * 64 : ws_array<uint32_t>(ctx, (size_t)B2 * 128);
-  if (!half_of || !u || !y) { mpe_set_error_msg("workspace under-reserved (modexp_nn)"); return MPE_E_NOMEM; }
+  if (!scratch) MPE_TRY(ws_ok(ctx));
   if (phase != 2) MPE_LAUNCH_1D(crt_half_kernel, B2, st, B2, ksel, half_of);
   const int bw = base.words ? base.words : 128;
   Rows lo{base.p, base.idx, base.stride, bw < 64 ? bw : 64, 1};
@@ -352,8 +350,7 @@ static int modexp_nn2(mpe_ctx* ctx, const mpe_paillier* pk, int B, Rows ksel, Ro
 // x^e mod N for the HOLDER of N = p q (the provers' s = r^e beta mod N: range_proofs.rs:84, zk_pdl_with_slack/mod.rs:113): x^e mod p and
 // x^e mod q in half mode on the 1024-bit pair engine (one pass per multiplication on half the limbs: a quarter of the multiply-adds of the
 // 2048-bit ladder, and 36 instead of 72 steps of latency per multiplication for a small batch), recombined with the CRT idempotents as in
-// paillier_decrypt.  Same residue.  Scratch: MODEXP_N_HOLDER_WS_WORDS words per item from the context workspace.
-constexpr size_t MODEXP_N_HOLDER_WS_WORDS = 2 * (3 + 64 + 64) + 64;
+// paillier_decrypt.  Same residue.  Scratch: from the context workspace.
 static int modexp_n_holder(mpe_ctx* ctx, const mpe_paillier* pk, int B, const int32_t* key_idx, Rows base, Rows exps, int ew, uint32_t* out,
                            hipStream_t st) {
   const int B2 = 2 * B;
@@ -362,7 +359,7 @@ static int modexp_n_holder(mpe_ctx* ctx, const mpe_paillier* pk, int B, const in
   int32_t* keyj = ws_array<int32_t>(ctx, B2);
   uint32_t* u = ws_array<uint32_t>(ctx, (size_t)B2 * 64);
   uint32_t* y = ws_array<uint32_t>(ctx, (size_t)B2 * 64);
-  if (!item_of || !half_of || !keyj || !u || !y) { mpe_set_error_msg("workspace under-reserved (modexp_n_holder)"); return MPE_E_NOMEM; }
+  MPE_TRY(ws_ok(ctx));
   MPE_LAUNCH_1D(dec_index_kernel, B2, st, B2, pk->nkeys, key_idx, item_of, half_of, keyj);
   MPE_TRY(launch_pair_modexp(ctx, pk->ps_pp, B2, Rows{nullptr, half_of, 0, 0}, Rows{base.p, base.idx, base.stride, base.words ? base.words : 64, 1},
                              Rows{exps.p, exps.idx, exps.stride, exps.words, 1}, ew, no_rows(), no_rows(), 0, u, st, 1));
@@ -371,16 +368,13 @@ static int modexp_n_holder(mpe_ctx* ctx, const mpe_paillier* pk, int B, const in
   return MPE_OK;
 }
 
-// workspace needs of the composites (a caller that runs several of them concurrently reserves the sum once)
-static inline size_t ws_need_encrypt(int B) { return (size_t)B * (256 + CRT_WS_WORDS) * 4 + 8192; }
-static inline size_t ws_need_mul_add_enc(int B) { return (size_t)B * 128 * 4 * 3 + 8192; }
-
 // rn_pre: r^N mod N^2 already computed by the caller (a small-batch round merges every x^N of its key holders into one launch)
 static int paillier_encrypt(mpe_ctx* ctx, const mpe_paillier* pk, int B, const int32_t* key_idx, const uint32_t* d_m,
                             const uint32_t* d_r, uint32_t* d_c, bool holder, hipStream_t st, const uint32_t* rn_pre = nullptr) {
-  MPE_TRY(ws_reserve(ctx, ws_need_encrypt(B), st));
+  MPE_TRY(ws_begin(ctx, st));
   uint32_t* x = ws_array<uint32_t>(ctx, (size_t)B * 128);
   uint32_t* gm = ws_array<uint32_t>(ctx, (size_t)B * 128);
+  MPE_TRY(ws_ok(ctx));
   // r^N mod N^2
   if (rn_pre) x = const_cast<uint32_t*>(rn_pre);
   else
@@ -396,9 +390,11 @@ static int paillier_encrypt(mpe_ctx* ctx, const mpe_paillier* pk, int B, const i
 // x_pre: c_a^k r^N mod N^2 already computed by the caller (Round 1 merges these ladders with those of its verifications)
 static int paillier_mul_add_enc(mpe_ctx* ctx, const mpe_paillier* pk, int B, const int32_t* key_idx, Rows c_a, Rows k, int kw,
                                 const uint32_t* d_m, const uint32_t* d_r, uint32_t* d_out, hipStream_t st, const uint32_t* x_pre = nullptr) {
-  MPE_TRY(ws_reserve(ctx, ws_need_mul_add_enc(B), st));
+  MPE_TRY(ws_begin(ctx, st));
   uint32_t* x = ws_array<uint32_t>(ctx, (size_t)B * 128);
   uint32_t* gm = ws_array<uint32_t>(ctx, (size_t)B * 128);
+  uint32_t* y = ctx->use_multiexp || x_pre ? nullptr : ws_array<uint32_t>(ctx, (size_t)B * 128);
+  MPE_TRY(ws_ok(ctx));
   const Rows ksel = key_selector(pk, key_idx), Nrow = key_rows(pk, pk->N, 64, key_idx);
   MPE_LAUNCH_1D(enc_gm_kernel, B, st, B, pk->nkeys, d_m, key_idx, pk->N, gm);
   if (x_pre) {
@@ -406,7 +402,6 @@ static int paillier_mul_add_enc(mpe_ctx* ctx, const mpe_paillier* pk, int B, con
   } else if (ctx->use_multiexp) {
     MPE_TRY(modexp_nn2(ctx, pk, B, ksel, rows(d_r, 64, nullptr, 64), Nrow, 64, c_a, k, kw, x, st));
   } else {
-    uint32_t* y = ws_array<uint32_t>(ctx, (size_t)B * 128);
     MPE_TRY(modexp_nn(ctx, pk, B, ksel, rows(d_r, 64, nullptr, 64), Nrow, 64, false, x, st));
     MPE_TRY(modexp_nn(ctx, pk, B, ksel, c_a, k, kw, false, y, st));
     MPE_TRY(launch_modmul(ctx, pk->ms_nn, B, ksel, rows(x, 128), rows(y, 128), x, st));
@@ -419,7 +414,7 @@ static int paillier_mul_add_enc(mpe_ctx* ctx, const mpe_paillier* pk, int B, con
 static int paillier_decrypt(mpe_ctx* ctx, const mpe_paillier* pk, int B, const int32_t* key_idx, Rows c, uint32_t* d_m,
                             hipStream_t st) {
   const int B2 = 2 * B;
-  MPE_TRY(ws_reserve(ctx, (size_t)B2 * (3 * 4 + (64 + 32 + 64 + 64) * 4) + 16384, st));
+  MPE_TRY(ws_begin(ctx, st));
   int32_t* item_of = ws_array<int32_t>(ctx, B2);
   int32_t* half_of = ws_array<int32_t>(ctx, B2);
   int32_t* keyj = ws_array<int32_t>(ctx, B2);
@@ -427,6 +422,7 @@ static int paillier_decrypt(mpe_ctx* ctx, const mpe_paillier* pk, int B, const i
   uint32_t* t = ws_array<uint32_t>(ctx, (size_t)B2 * 32);
   uint32_t* mh = ws_array<uint32_t>(ctx, (size_t)B2 * 64);
   uint32_t* y = ws_array<uint32_t>(ctx, (size_t)B2 * 64);
+  MPE_TRY(ws_ok(ctx));
   MPE_LAUNCH_1D(dec_index_kernel, B2, st, B2, pk->nkeys, key_idx, item_of, half_of, keyj);
   // u = c^(p-1) mod p^2 | c^(q-1) mod q^2   (c is double-width for the 2048-bit engine); half-item j reads row j >> 1
   if (ctx->use_pair) {

@@ -462,8 +462,6 @@ static size_t pass_candidates(int batch, int pass = PASS_CANDIDATES) {
   const size_t a = (size_t)batch << MIN_BLOCK_LOG;
   return a > (size_t)pass ? a : (size_t)pass;
 }
-// bytes of context workspace one search of `batch` items takes (the caller reserves, the search only allocates)
-static size_t search_ws_bytes(int batch) { return (2 * pass_candidates(batch) + 3 * (size_t)batch + 64) * 4 + 8 * 256; }
 
 static int mr_grid(const mpe_ctx* ctx, size_t entries) {
   const size_t units = (entries + Cfg1024::GROUPS - 1) / Cfg1024::GROUPS, cap = (size_t)ctx->cus * 8;
@@ -482,7 +480,7 @@ static int search_primes(mpe_ctx* ctx, int batch, const smp::Seed& key, uint64_t
   int32_t* list1 = ws_array<int32_t>(ctx, capC);
   int32_t* list2 = ws_array<int32_t>(ctx, capC);
   int32_t* cnt = ws_array<int32_t>(ctx, 8);                   // [0] survivors, [1] round-1 passers, [2] next items, [3], [4] unit queues
-  if (!items[0] || !items[1] || !best || !list1 || !list2 || !cnt) { mpe_set_error_msg("prime search: workspace under-reserved"); return MPE_E_NOMEM; }
+  MPE_TRY(ws_ok(ctx));                                       // (the caller began the workspace use, the search only allocates)
   hipLaunchKernelGGL(iota_kernel, dim3(blocks_for(batch, 256)), dim3(256), 0, st, batch, items[0], best);
   int U = batch, a0 = 0, cur = 0;
   while (U > 0 && a0 < max_attempts) {                        // at most max_attempts / 16 passes
@@ -535,7 +533,6 @@ static size_t safe_pass_capacity(int batch, int pass) {
   const size_t most = (size_t)batch << SAFE_MAX_BLOCK_LOG;
   return pass_candidates(batch, (int)(most < (size_t)pass ? most : (size_t)pass));
 }
-static size_t safe_search_ws_bytes(const mpe_ctx* ctx, int batch) { return (3 * safe_pass_capacity(batch, 1 << ctx->safe_pass_log) + 3 * (size_t)batch + 64) * 4 + 12 * 256; }
 
 static int search_safe_primes(mpe_ctx* ctx, int batch, const smp::Seed& key, uint64_t sid, int max_attempts, uint32_t* d_out, int32_t* d_attempt, int32_t* d_fail,
                               hipStream_t st) {
@@ -549,7 +546,7 @@ static int search_safe_primes(mpe_ctx* ctx, int batch, const smp::Seed& key, uin
   int32_t* list[3] = {ws_array<int32_t>(ctx, capC), ws_array<int32_t>(ctx, capC), ws_array<int32_t>(ctx, capC)};
   // [0] head survivors, [1] sieve survivors, [2] round 1 on c, [3] round 1 on the half, [4] rounds 2..8 on c, [5] next items, [8..12] unit queues
   int32_t* cnt = ws_array<int32_t>(ctx, 16);
-  if (!items[0] || !items[1] || !best || !list[0] || !list[1] || !list[2] || !cnt) { mpe_set_error_msg("safe prime search: workspace under-reserved"); return MPE_E_NOMEM; }
+  MPE_TRY(ws_ok(ctx));
   hipLaunchKernelGGL(iota_kernel, dim3(blocks_for(batch, 256)), dim3(256), 0, st, batch, items[0], best);
   int32_t* const none = nullptr;
   int U = batch, a0 = 0, cur = 0;
@@ -689,10 +686,10 @@ int mpe_is_probable_prime(mpe_ctx* ctx, int batch, const uint32_t* d_n, int roun
   hipStream_t st = (hipStream_t)stream;
   pr::SieveTab T;
   MPE_TRY(pr::sieve_table(ctx->device, &T));
-  MPE_TRY(ws_reserve(ctx, ((size_t)batch + 64) * 4 + 1024, st));
+  MPE_TRY(ws_begin(ctx, st));
   int32_t* list = ws_array<int32_t>(ctx, batch);
   int32_t* cnt = ws_array<int32_t>(ctx, 8);
-  if (!list || !cnt) return MPE_E_NOMEM;
+  MPE_TRY(ws_ok(ctx));
   (void)hipMemsetAsync(cnt, 0, 8 * sizeof(int32_t), st);
   hipLaunchKernelGGL(pr::table_kernel, dim3(blocks_for(batch, 64)), dim3(64), 0, st, batch, d_n, T, d_ok, list, cnt);
   pr::Source src{d_n, smp::Seed{}, 0u, 0u, nullptr, 0, 0};
@@ -708,7 +705,7 @@ int mpe_sample_prime(mpe_ctx* ctx, int batch, const uint8_t* h_seed32, uint64_t 
   if (!ctx || !h_seed32 || !d_out || batch < 0 || batch > (1 << 22) || bits != 1024 || max_attempts < 0 || max_attempts > (1 << 24)) return MPE_E_ARG;
   if (batch == 0) return MPE_OK;
   using namespace mpe;
-  MPE_TRY(ws_reserve(ctx, pr::search_ws_bytes(batch), (hipStream_t)stream));
+  MPE_TRY(ws_begin(ctx, (hipStream_t)stream));
   return pr::search_primes(ctx, batch, smp::seed_of(h_seed32), stream_id, max_attempts ? max_attempts : pr::DEFAULT_MAX_ATTEMPTS, d_out, d_attempt, d_fail,
                            (hipStream_t)stream);
 }
@@ -718,7 +715,7 @@ int mpe_sample_safe_prime(mpe_ctx* ctx, int batch, const uint8_t* h_seed32, uint
   if (!ctx || !h_seed32 || !d_out || batch < 0 || batch > (1 << 22) || bits != 1024 || max_attempts < 0 || max_attempts > (1 << 24)) return MPE_E_ARG;
   if (batch == 0) return MPE_OK;
   using namespace mpe;
-  MPE_TRY(ws_reserve(ctx, pr::safe_search_ws_bytes(ctx, batch), (hipStream_t)stream));
+  MPE_TRY(ws_begin(ctx, (hipStream_t)stream));
   return pr::search_safe_primes(ctx, batch, smp::seed_of(h_seed32), stream_id, max_attempts ? max_attempts : pr::SAFE_DEFAULT_MAX_ATTEMPTS, d_out, d_attempt, d_fail,
                                 (hipStream_t)stream);
 }
@@ -736,7 +733,6 @@ static int search_any(mpe_ctx* ctx, bool safe, int n, const smp::Seed& key, uint
   if (safe) return search_safe_primes(ctx, n, key, sid, max_attempts ? max_attempts : SAFE_DEFAULT_MAX_ATTEMPTS, d_out, nullptr, nullptr, st);
   return search_primes(ctx, n, key, sid, max_attempts ? max_attempts : DEFAULT_MAX_ATTEMPTS, d_out, nullptr, nullptr, st);
 }
-static size_t search_any_ws_bytes(const mpe_ctx* ctx, bool safe, int n) { return safe ? safe_search_ws_bytes(ctx, n) : search_ws_bytes(n); }
 
 static int paillier_keygen(mpe_ctx* ctx, bool safe, int nkeys, const uint8_t* h_seed32, uint64_t counter, int max_attempts, uint32_t* d_p, uint32_t* d_q, uint32_t* d_N,
                            int32_t* d_fail, hipStream_t st) {
@@ -746,7 +742,7 @@ static int paillier_keygen(mpe_ctx* ctx, bool safe, int nkeys, const uint8_t* h_
   const smp::Seed key = smp::seed_of(h_seed32);
   uint32_t* prime[2] = {d_p, d_q};
   for (int f = 0; f < 2; ++f) {                                // field f draws stream counter | f << 56 (the convention of mpe_gg20_sample_nonces)
-    MPE_TRY(ws_reserve(ctx, search_any_ws_bytes(ctx, safe, nkeys), st));
+    MPE_TRY(ws_begin(ctx, st));
     MPE_TRY(search_any(ctx, safe, nkeys, key, counter | ((uint64_t)f << 56), max_attempts, prime[f], st));
   }
   MPE_LAUNCH_1D(keypair_kernel, nkeys, st, nkeys, d_p, d_q, d_N, d_fail);
@@ -775,9 +771,8 @@ static int ntilde_generate(mpe_ctx* ctx, bool safe, int count, const uint8_t* h_
   const smp::Seed key = smp::seed_of(h_seed32);
   auto sid = [&](int f) { return counter | ((uint64_t)f << 56); };
   // the secrets of the call (p~, q~, phi, xi, phi^-1 mod xi) live in the context workspace: mpe_ctx_wipe covers them.  The two prime
-  // searches allocate below these arrays, one after the other (the first one's lists are dead when the second starts).
-  const size_t own = (size_t)count * (32 + 32 + 64 * 4 + 1) * 4 + (size_t)count + 16 * 256;
-  MPE_TRY(ws_reserve(ctx, own + 2 * search_any_ws_bytes(ctx, safe, count), st));
+  // searches allocate behind these arrays, one after the other.
+  MPE_TRY(ws_begin(ctx, st));
   uint32_t* pt = ws_array<uint32_t>(ctx, (size_t)count * 32);
   uint32_t* qt = ws_array<uint32_t>(ctx, (size_t)count * 32);
   uint32_t* nt_ms = ws_array<uint32_t>(ctx, (size_t)count * 64);
@@ -786,7 +781,7 @@ static int ntilde_generate(mpe_ctx* ctx, bool safe, int count, const uint8_t* h_
   uint32_t* phi_inv = ws_array<uint32_t>(ctx, (size_t)count * 64);
   int32_t* bad = ws_array<int32_t>(ctx, count);
   uint8_t* inv_ok = ws_array<uint8_t>(ctx, count);
-  if (!pt || !qt || !nt_ms || !phi || !xi || !phi_inv || !bad || !inv_ok) return MPE_E_NOMEM;
+  MPE_TRY(ws_ok(ctx));
   MPE_TRY(search_any(ctx, safe, count, key, sid(2), max_attempts, pt, st));
   MPE_TRY(search_any(ctx, safe, count, key, sid(3), max_attempts, qt, st));
   MPE_LAUNCH_1D(nt_setup_kernel, count, st, count, pt, qt, nt_ms, phi, bad);

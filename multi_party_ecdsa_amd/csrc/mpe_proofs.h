@@ -207,12 +207,12 @@ struct Seq {
   int rc = MPE_OK;
   uint32_t* words(size_t per_item) {
     uint32_t* p = ws_array<uint32_t>(ctx, (size_t)B * per_item);
-    if (!p && rc == MPE_OK) { rc = MPE_E_NOMEM; mpe_set_error_msg("workspace under-reserved"); }
+    if (!p && rc == MPE_OK) rc = MPE_E_NOMEM;
     return p;
   }
   uint8_t* flags() {
     uint8_t* p = ws_array<uint8_t>(ctx, (size_t)B);
-    if (!p && rc == MPE_OK) { rc = MPE_E_NOMEM; mpe_set_error_msg("workspace under-reserved"); }
+    if (!p && rc == MPE_OK) rc = MPE_E_NOMEM;
     return p;
   }
   // h1^x / h2^x mod N~ of a statement: fixed-base tables when the statement set has them (mpe_fixedbase.h)
@@ -304,8 +304,6 @@ struct Handed {
 // Small batches: z, u and w are independent and run on three streams (mpe::Fork); `outer`: a fork of the CALLER that
 // produces `cipher` concurrently (Round 0 encrypts k_i on another stream) — joined right before the transcript hash.
 // ---------------------------------------------------------------------------------------------
-static inline size_t ws_need_alice_generate(int B) { return (size_t)B * (1400 + CRT_WS_WORDS + MODEXP_N_HOLDER_WS_WORDS) * 4 + 65536; }
-static inline size_t ws_need_alice_verify(int B) { return (size_t)B * 2200 * 4 + 65536; }
 static int merge_rc(const Seq& a, const Seq& b, const Seq& c) { return a.rc != MPE_OK ? a.rc : (b.rc != MPE_OK ? b.rc : c.rc); }
 
 static int alice_generate(mpe_ctx* ctx, const mpe_paillier* pk, const mpe_statements* stm, int B, const int32_t* key_idx,
@@ -313,7 +311,7 @@ static int alice_generate(mpe_ctx* ctx, const mpe_paillier* pk, const mpe_statem
                           const mpe_alice_nonces* nn, const mpe_alice_proof* out, hipStream_t st, Fork* outer = nullptr,
                           Handed bn_pre = {}, hipEvent_t cipher_ready = nullptr) {
   // bn_pre: beta^N mod N^2 from the caller; cipher_ready: the outer branch goes on with other work — wait for this event instead of joining it
-  MPE_TRY(ws_reserve(ctx, ws_need_alice_generate(B), st));
+  MPE_TRY(ws_begin(ctx, st));
   Fork f(ctx, st, 3, B <= ctx->par_items);
   Seq q{ctx, f.s(0), B}, q1{ctx, f.s(1), B}, q2{ctx, f.s(2), B};
   const Rows ksel = sel_of(key_idx, pk->nkeys), ssel = sel_of(st_idx, stm->count);
@@ -358,7 +356,7 @@ static int alice_generate(mpe_ctx* ctx, const mpe_paillier* pk, const mpe_statem
 static int alice_verify(mpe_ctx* ctx, const mpe_paillier* pk, const mpe_statements* stm, int B, const int32_t* key_idx,
                         const int32_t* st_idx, Rows cipher, const AliceProofRows& pr, uint8_t* ok, hipStream_t st,
                         Handed m_pre = {}, const uint8_t* inv_ok_pre = nullptr) {
-  MPE_TRY(ws_reserve(ctx, ws_need_alice_verify(B), st));
+  MPE_TRY(ws_begin(ctx, st));
   Fork f(ctx, st, 3, B <= ctx->par_items);          // (with m_pre the N^2 side is one multiplication: the two N~ branches still fork)
   Seq q{ctx, f.s(0), B}, q1{ctx, f.s(1), B}, q2{ctx, f.s(2), B};
   const Rows ksel = sel_of(key_idx, pk->nkeys), ssel = sel_of(st_idx, stm->count);
@@ -426,7 +424,7 @@ static int pdl_prove(mpe_ctx* ctx, const mpe_paillier* pk, const mpe_statements*
                      hipEvent_t G_ready = nullptr) {                                         // G_ready: G is there although branch 1 goes on
   // outer: a fork of the CALLER whose branch 1 produces the statement points Q, G concurrently (Round 4: R, R_dash); only u1
   // and the transcript hash need them.  bn_pre: beta^N mod N^2 when the caller has queued it elsewhere
-  MPE_TRY(ws_reserve(ctx, (size_t)B * (1400 + CRT_WS_WORDS + MODEXP_N_HOLDER_WS_WORDS) * 4 + 65536, st));
+  MPE_TRY(ws_begin(ctx, st));
   Fork f(ctx, st, 3, B <= ctx->par_items);
   Seq q{ctx, f.s(0), B}, q1{ctx, f.s(1), B}, q2{ctx, f.s(2), B};
   const Rows ksel = sel_of(key_idx, pk->nkeys), ssel = sel_of(st_idx, stm->count);
@@ -477,7 +475,7 @@ static int pdl_prove(mpe_ctx* ctx, const mpe_paillier* pk, const mpe_statements*
 static int pdl_verify(mpe_ctx* ctx, const mpe_paillier* pk, const mpe_statements* stm, int B, const int32_t* key_idx,
                       const int32_t* st_idx, Rows cipher, Rows Qp, Rows Gp, const PdlProofRows& pr, uint8_t* ok,
                       hipStream_t st) {
-  MPE_TRY(ws_reserve(ctx, (size_t)B * 2600 * 4 + 65536, st));
+  MPE_TRY(ws_begin(ctx, st));
   const Rows ksel = sel_of(key_idx, pk->nkeys), ssel = sel_of(st_idx, stm->count);
   const Rows h1 = tab_rows(stm->h1, 64, st_idx, stm->count), h2 = tab_rows(stm->h2, 64, st_idx, stm->count);
   const Rows Nrow = tab_rows(pk->N, 64, key_idx, pk->nkeys);
@@ -639,7 +637,7 @@ int mpe_modinv(mpe_ctx* ctx, const mpe_modset* ms, int batch, const int32_t* d_m
                uint32_t* d_out, uint8_t* d_ok, void* stream) {
   if (!ctx || !ms || !d_a || !d_out || !d_ok || batch < 0) return MPE_E_ARG;
   if (!d_mod_idx && ms->count != 1 && ms->count < batch) return MPE_E_ARG;
-  MPE_TRY(mpe::ws_reserve(ctx, mpe::modinv_ws_words(ms, batch) * 4, (hipStream_t)stream));
+  MPE_TRY(mpe::ws_begin(ctx, (hipStream_t)stream));
   return mpe::launch_modinv(ctx, ms, batch, mpe::sel_of(d_mod_idx, ms->count), mpe::rows(d_a, ms->bits / 32), d_out, d_ok,
                             (hipStream_t)stream);
 }

@@ -285,16 +285,14 @@ static int sample_gg20(mpe_ctx* ctx, const mpe_gg20_keys* K, int per_batch, int 
   const size_t nPI = c.nPI, nAP = c.nAP, nPP = c.nPP, nMB = c.nMB;
   // workspace: the bound-row index of every item + the batched coprimality verdict of from_modulo
   const mpe_modset* msn = K->pub->ms_n;
-  const size_t idx_words = 2 * nPI + 2 * nAP + nMB + 2 * nPP + (size_t)batch + 128;
-  const size_t inv_bytes = (modinv_ws_words(msn, (int)nAP) + nAP * 64) * 4 + nAP + 4096;
-  MPE_TRY(ws_reserve(ctx, idx_words * 4 + inv_bytes + 16 * 256, st));
+  MPE_TRY(ws_begin(ctx, st));
   SIdx x{ws_array<int32_t>(ctx, nPI), ws_array<int32_t>(ctx, nAP), ws_array<int32_t>(ctx, nAP), ws_array<int32_t>(ctx, nMB), ws_array<int32_t>(ctx, nPP),
          ws_array<int32_t>(ctx, nPP), nullptr};
-  if (local_by_party) { x.ord = ws_array<int32_t>(ctx, (size_t)batch); if (!x.ord) return MPE_E_NOMEM; }
+  if (local_by_party) x.ord = ws_array<int32_t>(ctx, (size_t)batch);
   uint32_t* inv = ws_array<uint32_t>(ctx, nAP * 64);
   uint8_t* ok = ws_array<uint8_t>(ctx, nAP);
   int32_t* owner_bad = ws_array<int32_t>(ctx, nPI);           // a draw of this (session, party) gave up
-  if (!x.own_pi || !x.own_ap || !x.st_ap || !x.peer_mb || !x.own_pp || !x.st_pp || !inv || !ok || !owner_bad) return MPE_E_NOMEM;
+  MPE_TRY(ws_ok(ctx));
   (void)hipMemsetAsync(owner_bad, 0, nPI * 4, st);
   size_t total = nMB > nAP ? nMB : nAP;
   if (total < nPI) total = nPI;
@@ -381,9 +379,9 @@ int mpe_sample_below(mpe_ctx* ctx, int batch, const uint8_t* h_seed32, uint64_t 
 int mpe_sample_scalar(mpe_ctx* ctx, int batch, const uint8_t* h_seed32, uint64_t stream_id, uint32_t* d_out, int32_t* d_fail, void* stream) {
   if (!ctx) return MPE_E_ARG;
   static const uint32_t q[8] = {0xD0364141u, 0xBFD25E8Cu, 0xAF48A03Bu, 0xBAAEDCE6u, 0xFFFFFFFEu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
-  MPE_TRY(mpe::ws_reserve(ctx, 4096, (hipStream_t)stream));
+  MPE_TRY(mpe::ws_begin(ctx, (hipStream_t)stream));
   uint32_t* dq = mpe::ws_array<uint32_t>(ctx, 8);
-  if (!dq) return MPE_E_NOMEM;
+  MPE_TRY(mpe::ws_ok(ctx));
   (void)hipMemcpyAsync(dq, q, 32, hipMemcpyHostToDevice, (hipStream_t)stream);
   return mpe::smp::launch_sample(batch, h_seed32, stream_id, 0, dq, 8, nullptr, 1, mpe::smp::F_NONZERO, 8, d_out, d_fail, (hipStream_t)stream, nullptr,
                                  ctx->sampler_max_attempts);

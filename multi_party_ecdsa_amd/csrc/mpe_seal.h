@@ -310,9 +310,9 @@ int mpe_gg20_sealed_presig_export(mpe_gg20_presig_pool* p, const mpe_wrap_key* k
   hipStream_t st = (hipStream_t)stream;
   const int W = mpe_gg20_presig_record_words(p);
   const size_t stage_bytes = ((size_t)count * W + (size_t)count) * 4;      // the records, then the row statuses
-  MPE_TRY(mpe::ws_reserve(p->ctx, stage_bytes + 1024, st));
+  MPE_TRY(mpe::ws_begin(p->ctx, st));
   uint32_t* stage = mpe::ws_array<uint32_t>(p->ctx, (size_t)count * W + (size_t)count);
-  if (!stage) return MPE_E_NOMEM;
+  MPE_TRY(mpe::ws_ok(p->ctx));
   int32_t* code = (int32_t*)(stage + (size_t)count * W);
   hipLaunchKernelGGL(mpe::psg::presig_export_kernel, dim3(mpe::blocks_for(count, 64)), dim3(64), 0, st, p->v, count, d_slot, p->K->y, stage, code);
   int rc = mpe::seal::launched("presig_export_kernel");
@@ -332,9 +332,9 @@ int mpe_gg20_sealed_presig_import(mpe_gg20_presig_pool* p, const mpe_wrap_key* k
   hipStream_t st = (hipStream_t)stream;
   const int W = mpe_gg20_presig_record_words(p);
   const size_t stage_bytes = ((size_t)count * W + (size_t)count) * 4;      // the records, then the AEAD's verdicts
-  MPE_TRY(mpe::ws_reserve(p->ctx, stage_bytes + 1024, st));
+  MPE_TRY(mpe::ws_begin(p->ctx, st));
   uint32_t* stage = mpe::ws_array<uint32_t>(p->ctx, (size_t)count * W + (size_t)count);
-  if (!stage) return MPE_E_NOMEM;
+  MPE_TRY(mpe::ws_ok(p->ctx));
   int32_t* refused = (int32_t*)(stage + (size_t)count * W);
   // authenticate, then claim: a row the AEAD refuses (its stage row is zero) never reaches the slot's state word
   int rc = mpe::seal::launch_unseal(key->d_key, MPE_SEAL_KIND_PRESIG, count, W, d_sealed, stage, refused, st);
