@@ -18,8 +18,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # MPE_LIB_PATH: another build of the SAME library (A/B measurements of kernel variants, tools/ab.sh); never a different backend
 LIB_PATH = os.environ.get("MPE_LIB_PATH") or os.path.join(_HERE, "libmpecdsa_hip.so")
 
-# short names: MPE_GG20_STATUS_BAD_* -> GG20_STATUS_BAD_*, MPE_GG20_PRESIG_* -> PRESIG_*, mpe_gg20_blameN_in -> BlameNIn
-globals().update({k[len("MPE_"):]: v for k, v in vars(_abi).items() if k.startswith("MPE_GG20_STATUS_")})
+# short names: MPE_GG20_STATUS_BAD_* -> GG20_STATUS_BAD_*, MPE_GG20_PRESIG_* -> PRESIG_*, mpe_gg20_blameN_in -> BlameNIn, and
+# MPE_SEAL_* -> SEAL_*, MPE_GG20_KEYSHARE_WORDS, MPE_SHA512_* / MPE_BIP32_* of the sealed records and the child-key sessions
+_SHORT = ("MPE_GG20_STATUS_", "MPE_GG20_KEYSHARE_", "MPE_SEAL_", "MPE_SHA512_", "MPE_BIP32_")
+globals().update({k[len("MPE_"):]: v for k, v in vars(_abi).items() if k.startswith(_SHORT)})
 globals().update({k[len("MPE_GG20_"):]: v for k, v in vars(_abi).items() if k.startswith("MPE_GG20_PRESIG_")})
 Blame5In, Blame6In, Blame7In = _abi.Gg20Blame5In, _abi.Gg20Blame6In, _abi.Gg20Blame7In
 GG20_NONCE_FIELDS = [f for f, _ in _abi.Gg20Nonces._fields_]
@@ -28,17 +30,6 @@ KEYGEN_ROUND1_FIELDS = [f for f, _ in _abi.KeygenRound1._fields_]
 
 def gg20_status_pass_failed(rc):              # MPE_GG20_STATUS_PASS_FAILED(rc), a function-like macro of the header
     return 9000 - rc
-
-
-# The sealed records' constants are TYPED macros in the header (`((uint32_t)16)`), which the generator's integer-constant rule
-# does not take; they are restated here and tests/test_seal_abi_cpu.py compares them with what a C compiler prints.
-SEAL_MAGIC, SEAL_REFUSED, SEAL_MAX_WORDS = 0x3153504D, 841, 4096
-SEAL_KIND_PRESIG, SEAL_KIND_KEYSHARE, SEAL_KIND_USER = 1, 2, 16
-GG20_KEYSHARE_WORDS = 72
-# ... as are those of the child-key sessions and of SHA-512 / BIP32 derivation (tests/test_bip32_cpu.py compares them the same way)
-GG20_STATUS_BAD_TWEAK = 93
-SHA512_MAX_MSG_BYTES, BIP32_MAX_DEPTH = 65536, 16
-BIP32_STATUS_HARDENED, BIP32_STATUS_INVALID, BIP32_STATUS_DEPTH = 1, 2, 3
 
 
 class MpeError(RuntimeError):
@@ -88,3 +79,23 @@ lib = _load()
 def check(rc, what):
     if rc != _abi.MPE_OK:
         raise MpeError(f"{what} failed: rc={rc} ({lib.mpe_last_error().decode()})")
+
+
+class _Call:
+    """`call.mpe_X(*args)` is `check(lib.mpe_X(*args), "mpe_X")`: the function is named once.  `what=` replaces the name in the message.
+    Only for functions that return a status: a count or a string (mpe_paillier_nkeys, mpe_last_error) is read through `lib`."""
+
+    def __getattr__(self, name):
+        if name not in _abi.SIGNATURES:
+            raise AttributeError(f"{name} is not declared in include/mpecdsa_hip.h")
+        if _abi.SIGNATURES[name][0] is not C.c_int:
+            raise TypeError(f"{name} returns {_abi.SIGNATURES[name][0]}, not a status: call it through lib")
+        fn = getattr(lib, name)
+
+        def checked(*args, what=name):
+            check(fn(*args), what)
+        setattr(self, name, checked)              # looked up once per name
+        return checked
+
+
+call = _Call()

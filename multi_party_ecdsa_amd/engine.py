@@ -7,8 +7,7 @@ import os
 import numpy as np
 import torch
 
-from . import _native as N
-N_ = N
+from . import _native as N_                  # (N is a Paillier modulus in this file)
 from . import wire
 from .words import ints_to_words, words_to_ints
 
@@ -20,6 +19,57 @@ def _dev_u32(arr_np, device):
 
 def _to_np_u32(t):
     return t.detach().cpu().numpy().view(np.uint32)
+
+
+def _new(ctx, *shape):
+    """an uninitialised int32 tensor (u32 words) on the context's device: _new(ctx, B, 16), _new(ctx, L, B, 8), _new(ctx, B)"""
+    return torch.empty(shape, dtype=torch.int32, device=ctx.device)
+
+
+def _flags(ctx, B):
+    return torch.empty((B,), dtype=torch.uint8, device=ctx.device)
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def dev(ctx, vals, words):
+    """Python ints -> device word tensor"""
+    return _dev_u32(ints_to_words(vals, words), ctx.device)
+
+
+def host(t):
+    """device word tensor -> Python ints"""
+    return words_to_ints(_to_np_u32(t))
+
+
+def _on_ints(ctx, device_call, *cols, idx=None):
+    """the Python-int form of a device call: cols = (ints, words) per operand; device_call(*word tensors, index tensor or None)
+    gives the device result, which is read back as ints after a sync"""
+    d_idx = None if idx is None else torch.tensor(idx, dtype=torch.int32, device=ctx.device)
+    d_out = device_call(*[dev(ctx, vals, words) for vals, words in cols], d_idx)
+    ctx.sync()
+    return host(d_out)
+
+
+class _Handle:
+    """The owner of one native object: `h` is None until the constructor has it and after close(); a subclass states its destroy call."""
+    h = None
+
+    def _destroy(self):
+        raise NotImplementedError
+
+    def close(self):
+        if self.h:
+            self._destroy()
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 # The LIBRARY reads no environment variable (mpe_ctx_set_option is the only way to change an A/B switch).  This harness — tests,
@@ -43,16 +93,16 @@ def options_from_env(env=None):
     return out
 
 
-class Context:
+class Context(_Handle):
     def __init__(self, device=0, encoding=None, options=None):
-        """encoding: None (the defaults of include/mpecdsa_hip.h) or a dict / N.Encoding — the profile of the recalled
+        """encoding: None (the defaults of include/mpecdsa_hip.h) or a dict / _native.Encoding — the profile of the recalled
         curv / zk-paillier byte conventions this context hashes with (mpe_ctx_set_encoding).
         options: {key: value} for mpe_ctx_set_option, applied on top of the harness's MPE_* environment translation."""
         if not torch.cuda.is_available():
-            raise N.MpeError("no GPU visible: the HIP path cannot run (there is no CPU fallback)")
+            raise N_.MpeError("no GPU visible: the HIP path cannot run (there is no CPU fallback)")
         self.device = torch.device("cuda", device)
         h = C.c_void_p()
-        N.check(N.lib.mpe_ctx_create(C.byref(h), device), "mpe_ctx_create")
+        N_.call.mpe_ctx_create(C.byref(h), device)
         self.h = h
         if encoding is not None:
             self.set_encoding(encoding)
@@ -62,70 +112,62 @@ class Context:
 
     def set_option(self, key, value):
         """mpe_ctx_set_option: an A/B switch of the measurements (none changes a result); before the dependent objects are created"""
-        N.check(N.lib.mpe_ctx_set_option(self.h, str(key).encode(), str(int(value) if isinstance(value, bool) else value).encode()), f"mpe_ctx_set_option({key})")
+        N_.call.mpe_ctx_set_option(self.h, str(key).encode(), str(int(value) if isinstance(value, bool) else value).encode(), what=f"mpe_ctx_set_option({key})")
         self.options[key] = value
 
     def get_option(self, key):
         v = C.c_long(0)
-        N.check(N.lib.mpe_ctx_get_option(self.h, str(key).encode(), C.byref(v)), f"mpe_ctx_get_option({key})")
+        N_.call.mpe_ctx_get_option(self.h, str(key).encode(), C.byref(v), what=f"mpe_ctx_get_option({key})")
         return v.value
 
     def set_device_share(self, contexts):
         """this many contexts work on the device at the same time (mpe_ctx_set_device_share): keep the efficient lane layouts"""
-        N.check(N.lib.mpe_ctx_set_device_share(self.h, int(contexts)), "mpe_ctx_set_device_share")
+        N_.call.mpe_ctx_set_device_share(self.h, int(contexts))
 
     def set_encoding(self, encoding):
-        e = encoding if isinstance(encoding, N.Encoding) else N.Encoding.from_dict(dict(encoding))
-        N.check(N.lib.mpe_ctx_set_encoding(self.h, C.byref(e)), "mpe_ctx_set_encoding")
+        e = encoding if isinstance(encoding, N_.Encoding) else N_.Encoding.from_dict(dict(encoding))
+        N_.call.mpe_ctx_set_encoding(self.h, C.byref(e))
 
     def encoding(self):
-        e = N.Encoding()
-        N.check(N.lib.mpe_ctx_get_encoding(self.h, C.byref(e)), "mpe_ctx_get_encoding")
+        e = N_.Encoding()
+        N_.call.mpe_ctx_get_encoding(self.h, C.byref(e))
         return e.as_dict()
 
     def stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def sync(self):
-        N.check(N.lib.mpe_sync(self.h, self.stream()), "mpe_sync")
+        N_.call.mpe_sync(self.h, self.stream())
 
     def launch_info(self):
-        li = N.LaunchInfo()
-        N.check(N.lib.mpe_last_launch_info(self.h, C.byref(li)), "mpe_last_launch_info")
+        li = N_.LaunchInfo()
+        N_.call.mpe_last_launch_info(self.h, C.byref(li))
         return {k: getattr(li, k) for k, _ in li._fields_}
 
     def prof_enable(self, on=True):
-        N.check(N.lib.mpe_prof_enable(self.h, int(on)), "mpe_prof_enable")
+        N_.call.mpe_prof_enable(self.h, int(on))
 
     def prof_collect(self, max_records=4096):
-        arr = (N.ProfRec * max_records)()
+        arr = (N_.ProfRec * max_records)()
         n = C.c_int(0)
-        N.check(N.lib.mpe_prof_collect(self.h, arr, max_records, C.byref(n)), "mpe_prof_collect")
+        N_.call.mpe_prof_collect(self.h, arr, max_records, C.byref(n))
         return [dict(kind=r.kind, bits=r.bits, exp_words=r.exp_words, batch=r.batch, ms=r.ms, exp2_words=r.exp2_words,
                      sliding_frac=r.sliding_frac) for r in arr[:n.value]]
 
     def wipe(self):
-        N.check(N.lib.mpe_ctx_wipe(self.h, self.stream()), "mpe_ctx_wipe")
+        N_.call.mpe_ctx_wipe(self.h, self.stream())
 
     def scratch_audit(self):
         """(non-zero 32-bit words, total bytes) over every scratch region the context owns"""
         nz, tot = C.c_uint64(0), C.c_uint64(0)
-        N.check(N.lib.mpe_ctx_scratch_audit(self.h, C.byref(nz), C.byref(tot), self.stream()), "mpe_ctx_scratch_audit")
+        N_.call.mpe_ctx_scratch_audit(self.h, C.byref(nz), C.byref(tot), self.stream())
         return nz.value, tot.value
 
-    def close(self):
-        if self.h:
-            N.lib.mpe_ctx_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _destroy(self):
+        N_.lib.mpe_ctx_destroy(self.h)
 
 
-class ModSet:
+class ModSet(_Handle):
     """A set of odd moduli resident in HBM with their Montgomery constants (computed on the GPU)."""
 
     def __init__(self, ctx, bits, moduli):
@@ -134,44 +176,28 @@ class ModSet:
         if isinstance(moduli, torch.Tensor):
             self.d_moduli = moduli.contiguous()
         else:
-            self.d_moduli = _dev_u32(ints_to_words(moduli, self.k32), ctx.device)
+            self.d_moduli = dev(ctx, moduli, self.k32)
         self.count = self.d_moduli.shape[0]
         h = C.c_void_p()
-        N.check(N.lib.mpe_modset_create(ctx.h, bits, self.count, C.c_void_p(self.d_moduli.data_ptr()),
-                                        C.byref(h), ctx.stream()), "mpe_modset_create")
+        N_.call.mpe_modset_create(ctx.h, bits, self.count, _ptr(self.d_moduli), C.byref(h), ctx.stream())
         self.h = h
 
-    def close(self):
-        if self.h:
-            N.lib.mpe_modset_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _destroy(self):
+        N_.lib.mpe_modset_destroy(self.h)
 
 
 def modexp_device(ctx, ms, d_base, d_exp, d_out=None, d_mod_idx=None):
     """All-device call: d_base [B,k32], d_exp [B,ew], optional d_mod_idx [B] int32 -> d_out [B,k32]."""
-    B = d_base.shape[0]
     if d_out is None:
         d_out = torch.empty_like(d_base)
-    idx_ptr = C.c_void_p(d_mod_idx.data_ptr()) if d_mod_idx is not None else None
-    N.check(N.lib.mpe_modexp(ctx.h, ms.h, B, idx_ptr, C.c_void_p(d_base.data_ptr()),
-                             C.c_void_p(d_exp.data_ptr()), d_exp.shape[1], C.c_void_p(d_out.data_ptr()),
-                             ctx.stream()), "mpe_modexp")
+    N_.call.mpe_modexp(ctx.h, ms.h, d_base.shape[0], _ptr(d_mod_idx), _ptr(d_base), _ptr(d_exp), d_exp.shape[1], _ptr(d_out), ctx.stream())
     return d_out
 
 
 def modmul_device(ctx, ms, d_a, d_b, d_out=None, d_mod_idx=None):
-    B = d_a.shape[0]
     if d_out is None:
         d_out = torch.empty_like(d_a)
-    idx_ptr = C.c_void_p(d_mod_idx.data_ptr()) if d_mod_idx is not None else None
-    N.check(N.lib.mpe_modmul(ctx.h, ms.h, B, idx_ptr, C.c_void_p(d_a.data_ptr()), C.c_void_p(d_b.data_ptr()),
-                             C.c_void_p(d_out.data_ptr()), ctx.stream()), "mpe_modmul")
+    N_.call.mpe_modmul(ctx.h, ms.h, d_a.shape[0],_ptr(d_mod_idx), _ptr(d_a), _ptr(d_b), _ptr(d_out), ctx.stream())
     return d_out
 
 
@@ -179,44 +205,27 @@ def mod_pow2(ctx, ms, bases, exps, bases2, exps2, mod_idx=None, exp_bits=None, e
     """Batched `mod_pow(b, e, n) * mod_pow(b2, e2, n) % n` on one ladder (`mpe_modexp2`); e2 is the short exponent."""
     ew = ((exp_bits or max(1, max(int(e).bit_length() for e in exps))) + 31) // 32
     ew2 = ((exp2_bits or max(1, max(int(e).bit_length() for e in exps2))) + 31) // 32
-    dv = lambda xs, w: _dev_u32(ints_to_words(xs, w), ctx.device)
-    d_idx = torch.tensor(mod_idx, dtype=torch.int32, device=ctx.device) if mod_idx is not None else None
-    d_b, d_e, d_b2, d_e2 = dv(bases, ms.k32), dv(exps, ew), dv(bases2, ms.k32), dv(exps2, ew2)
-    d_out = torch.empty_like(d_b)
-    N.check(N.lib.mpe_modexp2(ctx.h, ms.h, len(bases), C.c_void_p(d_idx.data_ptr()) if d_idx is not None else None,
-                              C.c_void_p(d_b.data_ptr()), C.c_void_p(d_e.data_ptr()), ew, C.c_void_p(d_b2.data_ptr()),
-                              C.c_void_p(d_e2.data_ptr()), ew2, C.c_void_p(d_out.data_ptr()), ctx.stream()), "mpe_modexp2")
-    ctx.sync()
-    return words_to_ints(_to_np_u32(d_out))
+
+    def modexp2_device(d_b, d_e, d_b2, d_e2, d_idx):
+        d_out = torch.empty_like(d_b)
+        N_.call.mpe_modexp2(ctx.h, ms.h, len(bases), _ptr(d_idx), _ptr(d_b), _ptr(d_e), ew, _ptr(d_b2), _ptr(d_e2), ew2, _ptr(d_out), ctx.stream())
+        return d_out
+    return _on_ints(ctx, modexp2_device, (bases, ms.k32), (exps, ew), (bases2, ms.k32), (exps2, ew2), idx=mod_idx)
 
 
 def mod_pow(ctx, ms, bases, exps, mod_idx=None, exp_bits=None):
     """Batched `BigInt::mod_pow(base, exp, modulus)` on Python ints (host convenience wrapper)."""
     if exp_bits is None:
         exp_bits = max(1, max(int(e).bit_length() for e in exps))
-    ew = (exp_bits + 31) // 32
-    d_base = _dev_u32(ints_to_words(bases, ms.k32), ctx.device)
-    d_exp = _dev_u32(ints_to_words(exps, ew), ctx.device)
-    d_idx = torch.tensor(mod_idx, dtype=torch.int32, device=ctx.device) if mod_idx is not None else None
-    d_out = modexp_device(ctx, ms, d_base, d_exp, d_mod_idx=d_idx)
-    ctx.sync()
-    return words_to_ints(_to_np_u32(d_out))
+    return _on_ints(ctx, lambda d_base, d_exp, d_idx: modexp_device(ctx, ms, d_base, d_exp, d_mod_idx=d_idx),
+                    (bases, ms.k32), (exps, (exp_bits + 31) // 32), idx=mod_idx)
 
 
 def mod_mul(ctx, ms, a, b, mod_idx=None):
-    d_a = _dev_u32(ints_to_words(a, ms.k32), ctx.device)
-    d_b = _dev_u32(ints_to_words(b, ms.k32), ctx.device)
-    d_idx = torch.tensor(mod_idx, dtype=torch.int32, device=ctx.device) if mod_idx is not None else None
-    d_out = modmul_device(ctx, ms, d_a, d_b, d_mod_idx=d_idx)
-    ctx.sync()
-    return words_to_ints(_to_np_u32(d_out))
+    return _on_ints(ctx, lambda d_a, d_b, d_idx: modmul_device(ctx, ms, d_a, d_b, d_mod_idx=d_idx), (a, ms.k32), (b, ms.k32), idx=mod_idx)
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-class PaillierKeys:
+class PaillierKeys(_Handle):
     """A set of Paillier-2048 keys in HBM (`EncryptionKey{n,nn}` / `DecryptionKey{p,q}` of kzen-paillier).
     Build from moduli (public) or from primes (private; enables decrypt)."""
 
@@ -225,29 +234,19 @@ class PaillierKeys:
         h = C.c_void_p()
         if p is not None:
             # Python ints, or device word tensors [nkeys, 32] (what paillier_keygen returns)
-            self.d_p = p if torch.is_tensor(p) else _dev_u32(ints_to_words(p, 32), ctx.device)
-            self.d_q = q if torch.is_tensor(q) else _dev_u32(ints_to_words(q, 32), ctx.device)
-            N_.check(N_.lib.mpe_paillier_create_private(ctx.h, len(p), _ptr(self.d_p), _ptr(self.d_q), C.byref(h),
-                                                        ctx.stream()), "mpe_paillier_create_private")
+            self.d_p = p if torch.is_tensor(p) else dev(ctx, p, 32)
+            self.d_q = q if torch.is_tensor(q) else dev(ctx, q, 32)
+            N_.call.mpe_paillier_create_private(ctx.h, len(p), _ptr(self.d_p), _ptr(self.d_q), C.byref(h), ctx.stream())
             self.private = True
         else:
-            self.d_N = _dev_u32(ints_to_words(N, 64), ctx.device)
-            N_.check(N_.lib.mpe_paillier_create_public(ctx.h, len(N), _ptr(self.d_N), C.byref(h), ctx.stream()),
-                     "mpe_paillier_create_public")
+            self.d_N = dev(ctx, N, 64)
+            N_.call.mpe_paillier_create_public(ctx.h, len(N), _ptr(self.d_N), C.byref(h), ctx.stream())
             self.private = False
         self.h = h
         self.nkeys = N_.lib.mpe_paillier_nkeys(h)
 
-    def close(self):
-        if self.h:
-            N_.lib.mpe_paillier_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _destroy(self):
+        N_.lib.mpe_paillier_destroy(self.h)
 
     # ---- device-tensor API (int32 tensors holding u32 words) ----
     def encrypt_device(self, d_m, d_r, d_key_idx=None, d_c=None):
@@ -255,8 +254,7 @@ class PaillierKeys:
         B = d_m.shape[0]
         if d_c is None:
             d_c = torch.empty((B, 128), dtype=torch.int32, device=d_m.device)
-        N_.check(N_.lib.mpe_paillier_encrypt(self.ctx.h, self.h, B, _ptr(d_key_idx), _ptr(d_m), _ptr(d_r), _ptr(d_c),
-                                             self.ctx.stream()), "mpe_paillier_encrypt")
+        N_.call.mpe_paillier_encrypt(self.ctx.h, self.h, B, _ptr(d_key_idx), _ptr(d_m), _ptr(d_r), _ptr(d_c), self.ctx.stream())
         return d_c
 
     def decrypt_device(self, d_c, d_key_idx=None, d_m=None):
@@ -264,110 +262,75 @@ class PaillierKeys:
         B = d_c.shape[0]
         if d_m is None:
             d_m = torch.empty((B, 64), dtype=torch.int32, device=d_c.device)
-        N_.check(N_.lib.mpe_paillier_decrypt(self.ctx.h, self.h, B, _ptr(d_key_idx), _ptr(d_c), _ptr(d_m),
-                                             self.ctx.stream()), "mpe_paillier_decrypt")
+        N_.call.mpe_paillier_decrypt(self.ctx.h, self.h, B, _ptr(d_key_idx), _ptr(d_c), _ptr(d_m), self.ctx.stream())
         return d_m
 
     def add_device(self, d_c1, d_c2, d_key_idx=None):
         out = torch.empty_like(d_c1)
-        N_.check(N_.lib.mpe_paillier_add(self.ctx.h, self.h, d_c1.shape[0], _ptr(d_key_idx), _ptr(d_c1), _ptr(d_c2),
-                                         _ptr(out), self.ctx.stream()), "mpe_paillier_add")
+        N_.call.mpe_paillier_add(self.ctx.h, self.h, d_c1.shape[0], _ptr(d_key_idx), _ptr(d_c1), _ptr(d_c2), _ptr(out), self.ctx.stream())
         return out
 
     def mul_device(self, d_c, d_k, d_key_idx=None):
         out = torch.empty_like(d_c)
-        N_.check(N_.lib.mpe_paillier_mul(self.ctx.h, self.h, d_c.shape[0], _ptr(d_key_idx), _ptr(d_c), _ptr(d_k),
-                                         d_k.shape[1], _ptr(out), self.ctx.stream()), "mpe_paillier_mul")
+        N_.call.mpe_paillier_mul(self.ctx.h, self.h, d_c.shape[0], _ptr(d_key_idx), _ptr(d_c), _ptr(d_k), d_k.shape[1], _ptr(out), self.ctx.stream())
         return out
 
     # ---- Python-int convenience wrappers ----
-    def _idx(self, key_idx):
-        return None if key_idx is None else torch.tensor(key_idx, dtype=torch.int32, device=self.ctx.device)
-
     def encrypt(self, m, r, key_idx=None):
-        d = self.encrypt_device(_dev_u32(ints_to_words(m, 64), self.ctx.device),
-                                _dev_u32(ints_to_words(r, 64), self.ctx.device), self._idx(key_idx))
-        self.ctx.sync()
-        return words_to_ints(_to_np_u32(d))
+        return _on_ints(self.ctx, self.encrypt_device, (m, 64), (r, 64), idx=key_idx)
 
     def decrypt(self, c, key_idx=None):
-        d = self.decrypt_device(_dev_u32(ints_to_words(c, 128), self.ctx.device), self._idx(key_idx))
-        self.ctx.sync()
-        return words_to_ints(_to_np_u32(d))
+        return _on_ints(self.ctx, self.decrypt_device, (c, 128), idx=key_idx)
 
     def add(self, c1, c2, key_idx=None):
-        d = self.add_device(_dev_u32(ints_to_words(c1, 128), self.ctx.device),
-                            _dev_u32(ints_to_words(c2, 128), self.ctx.device), self._idx(key_idx))
-        self.ctx.sync()
-        return words_to_ints(_to_np_u32(d))
+        return _on_ints(self.ctx, self.add_device, (c1, 128), (c2, 128), idx=key_idx)
 
     def mul(self, c, k, key_idx=None, k_words=8):
-        d = self.mul_device(_dev_u32(ints_to_words(c, 128), self.ctx.device),
-                            _dev_u32(ints_to_words(k, k_words), self.ctx.device), self._idx(key_idx))
-        self.ctx.sync()
-        return words_to_ints(_to_np_u32(d))
+        return _on_ints(self.ctx, self.mul_device, (c, 128), (k, k_words), idx=key_idx)
 
 
 # ================================================================================================
 # secp256k1, modinv, DLogStatement tables and the proofs (device-tensor API; int32 tensors of u32 words)
 # ================================================================================================
-def _new(ctx, B, words):
-    return torch.empty((B, words), dtype=torch.int32, device=ctx.device)
-
-
-def _flags(ctx, B):
-    return torch.empty((B,), dtype=torch.uint8, device=ctx.device)
-
-
-def dev(ctx, vals, words):
-    """Python ints -> device word tensor"""
-    return _dev_u32(ints_to_words(vals, words), ctx.device)
-
-
-def host(t):
-    """device word tensor -> Python ints"""
-    return words_to_ints(_to_np_u32(t))
-
-
 def modinv_device(ctx, ms, d_a, d_mod_idx=None):
     B = d_a.shape[0]
     out, ok = torch.empty_like(d_a), _flags(ctx, B)
-    N_.check(N_.lib.mpe_modinv(ctx.h, ms.h, B, _ptr(d_mod_idx), _ptr(d_a), _ptr(out), _ptr(ok), ctx.stream()), "mpe_modinv")
+    N_.call.mpe_modinv(ctx.h, ms.h, B, _ptr(d_mod_idx), _ptr(d_a), _ptr(out), _ptr(ok), ctx.stream())
     return out, ok
 
 
 def ec_mul_base(ctx, d_k):
     out = _new(ctx, d_k.shape[0], 16)
-    N_.check(N_.lib.mpe_ec_mul_base(ctx.h, d_k.shape[0], _ptr(d_k), d_k.shape[1], _ptr(out), ctx.stream()), "mpe_ec_mul_base")
+    N_.call.mpe_ec_mul_base(ctx.h, d_k.shape[0], _ptr(d_k), d_k.shape[1], _ptr(out), ctx.stream())
     return out
 
 
 def ec_mul(ctx, d_k, d_P):
     out = _new(ctx, d_k.shape[0], 16)
-    N_.check(N_.lib.mpe_ec_mul(ctx.h, d_k.shape[0], _ptr(d_k), d_k.shape[1], _ptr(d_P), _ptr(out), ctx.stream()), "mpe_ec_mul")
+    N_.call.mpe_ec_mul(ctx.h, d_k.shape[0], _ptr(d_k), d_k.shape[1], _ptr(d_P), _ptr(out), ctx.stream())
     return out
 
 
 def ec_add(ctx, d_P, d_Q):
     out = _new(ctx, d_P.shape[0], 16)
-    N_.check(N_.lib.mpe_ec_add(ctx.h, d_P.shape[0], _ptr(d_P), _ptr(d_Q), _ptr(out), ctx.stream()), "mpe_ec_add")
+    N_.call.mpe_ec_add(ctx.h, d_P.shape[0], _ptr(d_P), _ptr(d_Q), _ptr(out), ctx.stream())
     return out
 
 
 def dlog_prove(ctx, d_sk, d_nonce):
     B = d_sk.shape[0]
     pk, R, z = _new(ctx, B, 16), _new(ctx, B, 16), _new(ctx, B, 8)
-    N_.check(N_.lib.mpe_dlog_prove(ctx.h, B, _ptr(d_sk), _ptr(d_nonce), _ptr(pk), _ptr(R), _ptr(z), ctx.stream()), "mpe_dlog_prove")
+    N_.call.mpe_dlog_prove(ctx.h, B, _ptr(d_sk), _ptr(d_nonce), _ptr(pk), _ptr(R), _ptr(z), ctx.stream())
     return pk, R, z
 
 
 def dlog_verify(ctx, d_pk, d_R, d_z):
     ok = _flags(ctx, d_pk.shape[0])
-    N_.check(N_.lib.mpe_dlog_verify(ctx.h, d_pk.shape[0], _ptr(d_pk), _ptr(d_R), _ptr(d_z), _ptr(ok), ctx.stream()), "mpe_dlog_verify")
+    N_.call.mpe_dlog_verify(ctx.h, d_pk.shape[0], _ptr(d_pk), _ptr(d_R), _ptr(d_z), _ptr(ok), ctx.stream())
     return ok
 
 
-class Statements:
+class Statements(_Handle):
     """Table of `DLogStatement{N: N~, g: h1, ni: h2}` (party_i.rs:225-229) resident in HBM."""
 
     def __init__(self, ctx, Nt, h1, h2, wb=None):
@@ -376,23 +339,13 @@ class Statements:
         self.d = [v if torch.is_tensor(v) else dev(ctx, v, 64) for v in (Nt, h1, h2)]      # ints, or device word tensors [count, 64]
         h = C.c_void_p()
         if wb is None:
-            N_.check(N_.lib.mpe_statements_create(ctx.h, len(Nt), _ptr(self.d[0]), _ptr(self.d[1]), _ptr(self.d[2]),
-                                                  C.byref(h), ctx.stream()), "mpe_statements_create")
+            N_.call.mpe_statements_create(ctx.h, len(Nt), _ptr(self.d[0]), _ptr(self.d[1]), _ptr(self.d[2]), C.byref(h), ctx.stream())
         else:
-            N_.check(N_.lib.mpe_statements_create_wb(ctx.h, len(Nt), _ptr(self.d[0]), _ptr(self.d[1]), _ptr(self.d[2]), int(wb),
-                                                     C.byref(h), ctx.stream()), "mpe_statements_create_wb")
+            N_.call.mpe_statements_create_wb(ctx.h, len(Nt), _ptr(self.d[0]), _ptr(self.d[1]), _ptr(self.d[2]), int(wb), C.byref(h), ctx.stream())
         self.h, self.count = h, len(Nt)
 
-    def close(self):
-        if self.h:
-            N_.lib.mpe_statements_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _destroy(self):
+        N_.lib.mpe_statements_destroy(self.h)
 
 
 ALICE_PROOF_WORDS = dict(z=64, e=8, s=64, s1=25, s2=89)
@@ -413,8 +366,8 @@ def alice_generate(ctx, pk, stm, d_a, d_cipher, d_r, nonces, d_key_idx=None, d_s
     B = d_a.shape[0]
     out = {f: _new(ctx, B, w) for f, w in ALICE_PROOF_WORDS.items()}
     nn, pr = _struct(N_.AliceNonces, nonces), _struct(N_.AliceProof, out)
-    N_.check(N_.lib.mpe_alice_generate(ctx.h, pk.h, stm.h, B, _ptr(d_key_idx), _ptr(d_st_idx), _ptr(d_a), _ptr(d_cipher),
-                                       _ptr(d_r), C.byref(nn), C.byref(pr), ctx.stream()), "mpe_alice_generate")
+    N_.call.mpe_alice_generate(ctx.h, pk.h, stm.h, B, _ptr(d_key_idx), _ptr(d_st_idx), _ptr(d_a), _ptr(d_cipher), _ptr(d_r), C.byref(nn), C.byref(pr),
+                               ctx.stream())
     return out
 
 
@@ -422,8 +375,7 @@ def alice_verify(ctx, pk, stm, d_cipher, proof, d_key_idx=None, d_st_idx=None):
     B = d_cipher.shape[0]
     ok = _flags(ctx, B)
     pr = _struct(N_.AliceProof, proof)
-    N_.check(N_.lib.mpe_alice_verify(ctx.h, pk.h, stm.h, B, _ptr(d_key_idx), _ptr(d_st_idx), _ptr(d_cipher), C.byref(pr),
-                                     _ptr(ok), ctx.stream()), "mpe_alice_verify")
+    N_.call.mpe_alice_verify(ctx.h, pk.h, stm.h, B, _ptr(d_key_idx), _ptr(d_st_idx), _ptr(d_cipher), C.byref(pr), _ptr(ok), ctx.stream())
     return ok
 
 
@@ -432,8 +384,8 @@ def pdl_prove(ctx, pk, stm, d_cipher, d_Q, d_G, d_x, d_r, nonces, d_key_idx=None
     B = d_x.shape[0]
     out = {f: _new(ctx, B, w) for f, w in PDL_PROOF_WORDS.items()}
     nn, pr = _struct(N_.PdlNonces, nonces), _struct(N_.PdlProof, out)
-    N_.check(N_.lib.mpe_pdl_prove(ctx.h, pk.h, stm.h, B, _ptr(d_key_idx), _ptr(d_st_idx), _ptr(d_cipher), _ptr(d_Q), _ptr(d_G),
-                                  _ptr(d_x), _ptr(d_r), C.byref(nn), C.byref(pr), ctx.stream()), "mpe_pdl_prove")
+    N_.call.mpe_pdl_prove(ctx.h, pk.h, stm.h, B, _ptr(d_key_idx), _ptr(d_st_idx), _ptr(d_cipher), _ptr(d_Q), _ptr(d_G), _ptr(d_x), _ptr(d_r), C.byref(nn),
+                          C.byref(pr), ctx.stream())
     return out
 
 
@@ -441,8 +393,7 @@ def pdl_verify(ctx, pk, stm, d_cipher, d_Q, d_G, proof, d_key_idx=None, d_st_idx
     B = d_cipher.shape[0]
     ok = _flags(ctx, B)
     pr = _struct(N_.PdlProof, proof)
-    N_.check(N_.lib.mpe_pdl_verify(ctx.h, pk.h, stm.h, B, _ptr(d_key_idx), _ptr(d_st_idx), _ptr(d_cipher), _ptr(d_Q), _ptr(d_G),
-                                   C.byref(pr), _ptr(ok), ctx.stream()), "mpe_pdl_verify")
+    N_.call.mpe_pdl_verify(ctx.h, pk.h, stm.h, B, _ptr(d_key_idx), _ptr(d_st_idx), _ptr(d_cipher), _ptr(d_Q), _ptr(d_G), C.byref(pr), _ptr(ok), ctx.stream())
     return ok
 
 
@@ -456,7 +407,7 @@ def gg20_msg_words(S, n, rnd):
     return N_.lib.mpe_gg20_msg_words(S, n, rnd)
 
 
-class Gg20Keys:
+class Gg20Keys(_Handle):
     """`LocalKey` material (keygen/rounds.rs:311-322) + the signer set, resident in HBM.
     arrays: dict of numpy uint32 arrays for ALL n parties of every key set: x [K*n,8], p, q [K*n,32], Nt, h1, h2 [K*n,64],
     y [K,16], X [K*n,16] (and optionally N [K*n,64], else p*q).  own: the party indices whose SECRETS (x, p, q) this
@@ -505,37 +456,26 @@ class Gg20Keys:
             sg = (C.c_int32 * len(flat))(*flat)
             if len(flat) != len(self.signer_sets) * self.S:
                 raise ValueError("every signer set of a key object has the same number of signers")
-            N_.check(N_.lib.mpe_gg20_keys_create_sealed(ctx.h, t, n, self.S, len(self.signer_sets), sg, nkeysets, len(own), ow, *dev, C.byref(hd),
-                                                        ctx.stream()), "mpe_gg20_keys_create_sealed")
+            N_.call.mpe_gg20_keys_create_sealed(ctx.h, t, n, self.S, len(self.signer_sets), sg, nkeysets, len(own), ow, *dev, C.byref(hd), ctx.stream())
         elif len(self.signer_sets) == 1:
             sg = (C.c_int32 * len(signers))(*signers)
-            N_.check(N_.lib.mpe_gg20_keys_create(ctx.h, t, n, len(signers), sg, nkeysets, len(own), ow, *dev, C.byref(hd), ctx.stream()),
-                     "mpe_gg20_keys_create")
+            N_.call.mpe_gg20_keys_create(ctx.h, t, n, len(signers), sg, nkeysets, len(own), ow, *dev, C.byref(hd), ctx.stream())
         else:
             flat = [x for s in self.signer_sets for x in s]      # (the library checks the rows: its refusals are part of its contract)
             sg = (C.c_int32 * len(flat))(*flat)
             if len(flat) != len(self.signer_sets) * self.S:
                 raise ValueError("every signer set of a key object has the same number of signers")
-            N_.check(N_.lib.mpe_gg20_keys_create_sets(ctx.h, t, n, self.S, len(self.signer_sets), sg, nkeysets, len(own), ow, *dev, C.byref(hd),
-                                                      ctx.stream()), "mpe_gg20_keys_create_sets")
+            N_.call.mpe_gg20_keys_create_sets(ctx.h, t, n, self.S, len(self.signer_sets), sg, nkeysets, len(own), ow, *dev, C.byref(hd), ctx.stream())
         self.h = hd
 
     def fb_window_bits(self):
         return N_.lib.mpe_gg20_keys_fb_window_bits(self.h)
 
-    def close(self):
-        if self.h:
-            N_.lib.mpe_gg20_keys_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _destroy(self):
+        N_.lib.mpe_gg20_keys_destroy(self.h)
 
 
-class Gg20Session:
+class Gg20Session(_Handle):
     """`RoundN::proceed` for B sessions x the local parties `local` (signer ordinals).  nonces: dict of device int32
     tensors with leading dimensions [B][len(local)] (fields _native.GG20_NONCE_FIELDS; `msg` optional).
     sigset: device int32 [B], the signer set (index into keys.signer_sets) of every session; ordinals are then positions in each
@@ -560,15 +500,13 @@ class Gg20Session:
         h = C.c_void_p()
         if tweaks is not None:
             tweaks = tweaks.contiguous()
-            N_.check(N_.lib.mpe_gg20_session_create_tweaks(ctx.h, keys.h, B, self.L, lc, _ptr(keyset), _ptr(sigset), int(by_party), _ptr(tweaks),
-                                                           C.byref(nn), int(bool(dedup_verify)), C.byref(h), ctx.stream()),
-                     "mpe_gg20_session_create_tweaks")
+            N_.call.mpe_gg20_session_create_tweaks(ctx.h, keys.h, B, self.L, lc, _ptr(keyset), _ptr(sigset), int(by_party), _ptr(tweaks), C.byref(nn),
+                                                   int(bool(dedup_verify)), C.byref(h), ctx.stream())
         elif sigset is None and not by_party:
-            N_.check(N_.lib.mpe_gg20_session_create(ctx.h, keys.h, B, self.L, lc, _ptr(keyset), C.byref(nn), int(bool(dedup_verify)),
-                                                    C.byref(h), ctx.stream()), "mpe_gg20_session_create")
+            N_.call.mpe_gg20_session_create(ctx.h, keys.h, B, self.L, lc, _ptr(keyset), C.byref(nn), int(bool(dedup_verify)), C.byref(h), ctx.stream())
         else:
-            N_.check(N_.lib.mpe_gg20_session_create_sets(ctx.h, keys.h, B, self.L, lc, _ptr(keyset), _ptr(sigset), int(by_party), C.byref(nn),
-                                                         int(bool(dedup_verify)), C.byref(h), ctx.stream()), "mpe_gg20_session_create_sets")
+            N_.call.mpe_gg20_session_create_sets(ctx.h, keys.h, B, self.L, lc, _ptr(keyset), _ptr(sigset), int(by_party), C.byref(nn), int(bool(dedup_verify)),
+                                                 C.byref(h), ctx.stream())
         self.h = h
 
     def _off(self, in_off):
@@ -583,83 +521,70 @@ class Gg20Session:
         nn = _struct(N_.Gg20Nonces, self._nonces)
         self._sigset = sigset
         if tweaks is not None:
-            N_.check(N_.lib.mpe_gg20_session_rearm_tweaks(self.h, _ptr(keyset), _ptr(sigset), _ptr(tweaks.contiguous()), C.byref(nn), self.ctx.stream()),
-                     "mpe_gg20_session_rearm_tweaks")
+            N_.call.mpe_gg20_session_rearm_tweaks(self.h, _ptr(keyset), _ptr(sigset), _ptr(tweaks.contiguous()), C.byref(nn), self.ctx.stream())
         elif sigset is None:
-            N_.check(N_.lib.mpe_gg20_session_rearm(self.h, _ptr(keyset), C.byref(nn), self.ctx.stream()), "mpe_gg20_session_rearm")
+            N_.call.mpe_gg20_session_rearm(self.h, _ptr(keyset), C.byref(nn), self.ctx.stream())
         else:
-            N_.check(N_.lib.mpe_gg20_session_rearm_sets(self.h, _ptr(keyset), _ptr(sigset), C.byref(nn), self.ctx.stream()), "mpe_gg20_session_rearm_sets")
+            N_.call.mpe_gg20_session_rearm_sets(self.h, _ptr(keyset), _ptr(sigset), C.byref(nn), self.ctx.stream())
 
     def child_keys(self):
         """[B, 16] device int32: the public key every session of the batch signs for (mpe_gg20_session_child_keys)"""
-        y = torch.empty((self.B, 16), dtype=torch.int32, device=self.ctx.device)
-        N_.check(N_.lib.mpe_gg20_session_child_keys(self.h, _ptr(y), self.ctx.stream()), "mpe_gg20_session_child_keys")
+        y = _new(self.ctx, self.B, 16)
+        N_.call.mpe_gg20_session_child_keys(self.h, _ptr(y), self.ctx.stream())
         return y
 
     def abort(self):
         """mpe_gg20_session_abort: give the running batch up (state wiped now); rearm() starts the next one"""
-        N_.check(N_.lib.mpe_gg20_session_abort(self.h, self.ctx.stream()), "mpe_gg20_session_abort")
+        N_.call.mpe_gg20_session_abort(self.h, self.ctx.stream())
 
     def round(self, rnd, d_in=None, in_off=None, msg=None, out=None):
         """Runs round `rnd` (0..7, 8 = SignManual::complete).  d_in: the previous round's records of all S senders (device
         int32 tensor; sender j's [B][W] block at record in_off[j], default j*B).  Returns this object's outgoing records
         [L, B, W] (None for rounds 6 and 8); `out`: a contiguous [L, B, W] int32 device tensor to write them into (e.g. this
         rank's slot of an all-gather buffer)."""
-        lib, st = N_.lib, self.ctx.stream()
+        st = self.ctx.stream()
         W = gg20_msg_words(self.S, self.n, rnd) if rnd in GG20_ROUNDS else 0
         if out is not None and W:
             if not (out.is_contiguous() and out.dtype == torch.int32 and out.numel() == self.L * self.B * W and out.device == self.ctx.device):
                 raise ValueError("round(out=...): need a contiguous int32 [L, B, W] tensor on the context's device")
         else:
-            out = torch.empty((self.L, self.B, W), dtype=torch.int32, device=self.ctx.device) if W else None
+            out = _new(self.ctx, self.L, self.B, W) if W else None
         if rnd == 0:
-            N_.check(lib.mpe_gg20_round0(self.h, _ptr(out), st), "mpe_gg20_round0")
+            N_.call.mpe_gg20_round0(self.h, _ptr(out), st)
         elif 1 <= rnd <= 5:
-            N_.check(getattr(lib, f"mpe_gg20_round{rnd}")(self.h, _ptr(d_in), self._off(in_off), _ptr(out), st), f"mpe_gg20_round{rnd}")
+            getattr(N_.call, f"mpe_gg20_round{rnd}")(self.h, _ptr(d_in), self._off(in_off), _ptr(out), st)
         elif rnd == 6:
-            N_.check(lib.mpe_gg20_round6(self.h, _ptr(d_in), self._off(in_off), st), "mpe_gg20_round6")
+            N_.call.mpe_gg20_round6(self.h, _ptr(d_in), self._off(in_off), st)
         elif rnd == 7:
-            N_.check(lib.mpe_gg20_round7(self.h, _ptr(msg), _ptr(out), st), "mpe_gg20_round7")
+            N_.call.mpe_gg20_round7(self.h, _ptr(msg), _ptr(out), st)
         elif rnd == 8:
-            N_.check(lib.mpe_gg20_complete(self.h, _ptr(d_in), self._off(in_off), st), "mpe_gg20_complete")
+            N_.call.mpe_gg20_complete(self.h, _ptr(d_in), self._off(in_off), st)
         else:
             raise ValueError(rnd)
         return out
 
     def fault_inject(self, step, party_mask):
-        N_.check(N_.lib.mpe_gg20_session_fault_inject(self.h, int(step), int(party_mask)), "mpe_gg20_session_fault_inject")
+        N_.call.mpe_gg20_session_fault_inject(self.h, int(step), int(party_mask))
 
     def blame6_state(self, d_nonce):
         """(miu [L,B,S-1,64], a1, a2 [L,B,16], z [L,B,8]): what the local parties publish for the phase-6 blame"""
-        L, B, S, dv = self.L, self.B, self.S, self.ctx.device
-        miu = torch.empty((L, B, S - 1, 64), dtype=torch.int32, device=dv)
-        a1, a2, z = torch.empty((L, B, 16), dtype=torch.int32, device=dv), torch.empty((L, B, 16), dtype=torch.int32, device=dv), torch.empty((L, B, 8), dtype=torch.int32, device=dv)
-        N_.check(N_.lib.mpe_gg20_session_blame6_state(self.h, _ptr(d_nonce), _ptr(miu), _ptr(a1), _ptr(a2), _ptr(z), self.ctx.stream()),
-                 "mpe_gg20_session_blame6_state")
+        ctx, L, B = self.ctx, self.L, self.B
+        miu, a1, a2, z = _new(ctx, L, B, self.S - 1, 64), _new(ctx, L, B, 16), _new(ctx, L, B, 16), _new(ctx, L, B, 8)
+        N_.call.mpe_gg20_session_blame6_state(self.h, _ptr(d_nonce), _ptr(miu), _ptr(a1), _ptr(a2), _ptr(z), self.ctx.stream())
         return miu, a1, a2, z
 
     def result(self, signature=True):
         """dict of device tensors: status, bad_actors, recid [L,B]; r, s [L,B,8]; R [L,B,16]"""
-        L, B, dv = self.L, self.B, self.ctx.device
-        o = dict(status=torch.empty((L, B), dtype=torch.int32, device=dv), bad_actors=torch.empty((L, B), dtype=torch.int32, device=dv),
-                 R=torch.empty((L, B, 16), dtype=torch.int32, device=dv))
+        ctx, L, B = self.ctx, self.L, self.B
+        o = dict(status=_new(ctx, L, B), bad_actors=_new(ctx, L, B), R=_new(ctx, L, B, 16))
         if signature:
-            o.update(r=torch.empty((L, B, 8), dtype=torch.int32, device=dv), s=torch.empty((L, B, 8), dtype=torch.int32, device=dv),
-                     recid=torch.empty((L, B), dtype=torch.int32, device=dv))
-        N_.check(N_.lib.mpe_gg20_session_result(self.h, _ptr(o["status"]), _ptr(o["bad_actors"]), _ptr(o.get("r")), _ptr(o.get("s")),
-                                                _ptr(o.get("recid")), _ptr(o["R"]), self.ctx.stream()), "mpe_gg20_session_result")
+            o.update(r=_new(ctx, L, B, 8), s=_new(ctx, L, B, 8), recid=_new(ctx, L, B))
+        N_.call.mpe_gg20_session_result(self.h, _ptr(o["status"]), _ptr(o["bad_actors"]), _ptr(o.get("r")), _ptr(o.get("s")), _ptr(o.get("recid")),
+                                        _ptr(o["R"]), self.ctx.stream())
         return o
 
-    def close(self):
-        if self.h:
-            N_.lib.mpe_gg20_session_destroy(self.h, self.ctx.stream())
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _destroy(self):
+        N_.lib.mpe_gg20_session_destroy(self.h, self.ctx.stream())
 
 
 def gg20_sign(ctx, keys, nonces, B, dedup_verify=False, chunk=0, want_R=False, keyset=None, sigset=None, tweaks=None):
@@ -667,24 +592,23 @@ def gg20_sign(ctx, keys, nonces, B, dedup_verify=False, chunk=0, want_R=False, k
     r [B,8], s [B,8], recid [B], status [B] (0 = signed and verified) and optionally R [B,16].  sigset: device int32 [B], the signer
     set of every session (mpe_gg20_sign_sets).  tweaks: device int32 [B, 8], session b signs for the child key x + t_b
     (mpe_gg20_sign_tweaks)."""
-    r, s = _new(ctx, B, 8), _new(ctx, B, 8)
-    recid = torch.empty((B,), dtype=torch.int32, device=ctx.device)
+    r, s, recid = _new(ctx, B, 8), _new(ctx, B, 8), _new(ctx, B)
     status = torch.full((B,), -1, dtype=torch.int32, device=ctx.device)
     R = _new(ctx, B, 16) if want_R else None
     nn = _struct(N_.Gg20Nonces, nonces)
     if tweaks is not None:
-        N_.check(N_.lib.mpe_gg20_sign_tweaks(ctx.h, keys.h, B, _ptr(keyset), _ptr(sigset), _ptr(tweaks.contiguous()), C.byref(nn), _ptr(r), _ptr(s),
-                                             _ptr(recid), _ptr(R), _ptr(status), int(bool(dedup_verify)), int(chunk), ctx.stream()), "mpe_gg20_sign_tweaks")
+        N_.call.mpe_gg20_sign_tweaks(ctx.h, keys.h, B, _ptr(keyset), _ptr(sigset), _ptr(tweaks.contiguous()), C.byref(nn), _ptr(r), _ptr(s), _ptr(recid),
+                                     _ptr(R), _ptr(status), int(bool(dedup_verify)), int(chunk), ctx.stream())
     elif sigset is None:
-        N_.check(N_.lib.mpe_gg20_sign(ctx.h, keys.h, B, _ptr(keyset), C.byref(nn), _ptr(r), _ptr(s), _ptr(recid), _ptr(R), _ptr(status),
-                                      int(bool(dedup_verify)), int(chunk), ctx.stream()), "mpe_gg20_sign")
+        N_.call.mpe_gg20_sign(ctx.h, keys.h, B, _ptr(keyset), C.byref(nn), _ptr(r), _ptr(s), _ptr(recid), _ptr(R), _ptr(status), int(bool(dedup_verify)),
+                              int(chunk), ctx.stream())
     else:
-        N_.check(N_.lib.mpe_gg20_sign_sets(ctx.h, keys.h, B, _ptr(keyset), _ptr(sigset), C.byref(nn), _ptr(r), _ptr(s), _ptr(recid), _ptr(R),
-                                           _ptr(status), int(bool(dedup_verify)), int(chunk), ctx.stream()), "mpe_gg20_sign_sets")
+        N_.call.mpe_gg20_sign_sets(ctx.h, keys.h, B, _ptr(keyset), _ptr(sigset), C.byref(nn), _ptr(r), _ptr(s), _ptr(recid), _ptr(R), _ptr(status),
+                                   int(bool(dedup_verify)), int(chunk), ctx.stream())
     return (r, s, recid, status, R) if want_R else (r, s, recid, status)
 
 
-class WrapKey:
+class WrapKey(_Handle):
     """A wrapping key for sealed records (`mpe_wrap_key`): 32 bytes from the operator's KMS or HSM, copied into device memory the
     object owns and zeroed there when it is closed.  Every sealing call needs a `nonce_hi` that is never used twice with this key:
     unless one is given, 64 fresh random bits (`secrets.randbits`) per call."""
@@ -695,7 +619,7 @@ class WrapKey:
             raise ValueError("WrapKey: 32 bytes")
         self.ctx = ctx
         h = C.c_void_p()
-        N_.check(N_.lib.mpe_wrap_key_create(ctx.h, key_bytes, C.byref(h)), "mpe_wrap_key_create")
+        N_.call.mpe_wrap_key_create(ctx.h, key_bytes, C.byref(h))
         self.h = h
 
     @staticmethod
@@ -703,24 +627,16 @@ class WrapKey:
         import secrets
         return C.c_uint64(secrets.randbits(64) if nonce_hi is None else int(nonce_hi))
 
-    def close(self):
-        if self.h:
-            N_.lib.mpe_wrap_key_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _destroy(self):
+        N_.lib.mpe_wrap_key_destroy(self.h)
 
 
 def seal(ctx, wrap, kind, d_plain, nonce_hi=None):
     """caller rows (kind >= 16): d_plain [count, words] device int32 -> sealed rows [count, words + 10] (mpe_seal)"""
     d_plain = d_plain.contiguous()
     count, words = d_plain.shape
-    out = torch.empty((count, words + 10), dtype=torch.int32, device=ctx.device)
-    N_.check(N_.lib.mpe_seal(ctx.h, wrap.h, int(kind), count, words, _ptr(d_plain), WrapKey.nonce(nonce_hi), _ptr(out), ctx.stream()), "mpe_seal")
+    out = _new(ctx, count, words + 10)
+    N_.call.mpe_seal(ctx.h, wrap.h, int(kind), count, words, _ptr(d_plain), WrapKey.nonce(nonce_hi), _ptr(out), ctx.stream())
     return out
 
 
@@ -728,9 +644,8 @@ def unseal(ctx, wrap, kind, d_sealed):
     """sealed rows [count, words + 10] -> (plain [count, words], status [count]): 841 and an all-zero row where a row is refused"""
     d_sealed = d_sealed.contiguous()
     count, words = d_sealed.shape[0], d_sealed.shape[1] - 10
-    plain = torch.empty((count, words), dtype=torch.int32, device=ctx.device)
-    status = torch.empty((count,), dtype=torch.int32, device=ctx.device)
-    N_.check(N_.lib.mpe_unseal(ctx.h, wrap.h, int(kind), count, words, _ptr(d_sealed), _ptr(plain), _ptr(status), ctx.stream()), "mpe_unseal")
+    plain, status = _new(ctx, count, words), _new(ctx, count)
+    N_.call.mpe_unseal(ctx.h, wrap.h, int(kind), count, words, _ptr(d_sealed), _ptr(plain), _ptr(status), ctx.stream())
     return plain, status
 
 
@@ -738,8 +653,8 @@ def poly1305(ctx, d_key, d_msg):
     """the one-time-key MAC on its own: d_key [count, 8] int32 (r | s), d_msg [count, bytes] uint8 -> tags [count, 4] int32"""
     d_key, d_msg = d_key.contiguous(), d_msg.contiguous()
     count = d_key.shape[0]
-    tag = torch.empty((count, 4), dtype=torch.int32, device=ctx.device)
-    N_.check(N_.lib.mpe_poly1305(ctx.h, count, _ptr(d_key), _ptr(d_msg), d_msg.shape[1], _ptr(tag), ctx.stream()), "mpe_poly1305")
+    tag = _new(ctx, count, 4)
+    N_.call.mpe_poly1305(ctx.h, count, _ptr(d_key), _ptr(d_msg), d_msg.shape[1], _ptr(tag), ctx.stream())
     return tag
 
 
@@ -760,7 +675,7 @@ def sha512(ctx, msg):
     -> digests, device uint8 [count, 64] (mpe_sha512)"""
     d_msg = _bytes_rows(ctx, msg, "sha512")
     out = torch.empty((d_msg.shape[0], 64), dtype=torch.uint8, device=ctx.device)
-    N_.check(N_.lib.mpe_sha512(ctx.h, d_msg.shape[0], _ptr(d_msg), d_msg.shape[1], _ptr(out), ctx.stream()), "mpe_sha512")
+    N_.call.mpe_sha512(ctx.h, d_msg.shape[0], _ptr(d_msg), d_msg.shape[1], _ptr(out), ctx.stream())
     return out
 
 
@@ -770,8 +685,7 @@ def hmac_sha512(ctx, key, msg):
     if d_key.shape[0] != d_msg.shape[0]:
         raise ValueError("hmac_sha512: one key per message")
     out = torch.empty((d_msg.shape[0], 64), dtype=torch.uint8, device=ctx.device)
-    N_.check(N_.lib.mpe_hmac_sha512(ctx.h, d_msg.shape[0], _ptr(d_key), d_key.shape[1], _ptr(d_msg), d_msg.shape[1], _ptr(out), ctx.stream()),
-             "mpe_hmac_sha512")
+    N_.call.mpe_hmac_sha512(ctx.h, d_msg.shape[0], _ptr(d_key), d_key.shape[1], _ptr(d_msg), d_msg.shape[1], _ptr(out), ctx.stream())
     return out
 
 
@@ -795,10 +709,10 @@ def bip32_derive(ctx, d_pub, cc, paths, depth=None, parent_idx=None):
                            (v.to(dv).to(torch.int32).contiguous() if isinstance(v, torch.Tensor) else torch.tensor(list(v), dtype=torch.int32, device=dv)))
     d_depth = i32(depth, max_depth)
     d_pidx = None if parent_idx is None else i32(parent_idx, 0)
-    tweak, child = torch.empty((B, 8), dtype=torch.int32, device=dv), torch.empty((B, 16), dtype=torch.int32, device=dv)
-    ccs, status = torch.empty((B, 32), dtype=torch.uint8, device=dv), torch.empty((B,), dtype=torch.int32, device=dv)
-    N_.check(N_.lib.mpe_bip32_derive(ctx.h, B, d_pub.shape[0], _ptr(d_pub), _ptr(d_cc), _ptr(d_pidx), _ptr(d_path), _ptr(d_depth), max_depth,
-                                     _ptr(tweak), _ptr(child), _ptr(ccs), _ptr(status), ctx.stream()), "mpe_bip32_derive")
+    tweak, child, status = _new(ctx, B, 8), _new(ctx, B, 16), _new(ctx, B)
+    ccs = torch.empty((B, 32), dtype=torch.uint8, device=dv)
+    N_.call.mpe_bip32_derive(ctx.h, B, d_pub.shape[0], _ptr(d_pub), _ptr(d_cc), _ptr(d_pidx), _ptr(d_path), _ptr(d_depth), max_depth, _ptr(tweak), _ptr(child),
+                             _ptr(ccs), _ptr(status), ctx.stream())
     return tweak, child, ccs, status
 
 
@@ -806,13 +720,12 @@ def keyshare_seal(ctx, wrap, d_x, d_p, d_q, nonce_hi=None):
     """x [count, 8], p, q [count, 32] (device int32) -> sealed key shares [count, 82] (mpe_gg20_keyshare_seal)"""
     count = d_x.shape[0]
     d_x, d_p, d_q = d_x.contiguous(), d_p.contiguous(), d_q.contiguous()        # (held until the call is queued)
-    out = torch.empty((count, N_.GG20_KEYSHARE_WORDS + 10), dtype=torch.int32, device=ctx.device)
-    N_.check(N_.lib.mpe_gg20_keyshare_seal(ctx.h, wrap.h, count, _ptr(d_x), _ptr(d_p), _ptr(d_q), WrapKey.nonce(nonce_hi), _ptr(out), ctx.stream()),
-             "mpe_gg20_keyshare_seal")
+    out = _new(ctx, count, N_.GG20_KEYSHARE_WORDS + 10)
+    N_.call.mpe_gg20_keyshare_seal(ctx.h, wrap.h, count, _ptr(d_x), _ptr(d_p), _ptr(d_q), WrapKey.nonce(nonce_hi), _ptr(out), ctx.stream())
     return out
 
 
-class PresigPool:
+class PresigPool(_Handle):
     """Device-resident presignatures in single-use slots (`mpe_gg20_presig_*`): `CompletedOfflineStage` of `capacity` sessions for the
     local parties `local` (signer ordinals), kept until the message arrives.  The C-ABI is mechanism only; this object owns the POLICY:
     a host-side free list that hands slots to `deposit` / `import_` and takes them back when a row failed, a signature completed, or
@@ -824,7 +737,7 @@ class PresigPool:
         self.S, self.L = keys.S, len(self.local)
         lc = (C.c_int32 * self.L)(*self.local)
         h = C.c_void_p()
-        N_.check(N_.lib.mpe_gg20_presig_pool_create(ctx.h, keys.h, self.L, lc, self.capacity, C.byref(h)), "mpe_gg20_presig_pool_create")
+        N_.call.mpe_gg20_presig_pool_create(ctx.h, keys.h, self.L, lc, self.capacity, C.byref(h))
         self.h = h
         self.capacity = N_.lib.mpe_gg20_presig_pool_capacity(h)
         self.record_words = N_.lib.mpe_gg20_presig_record_words(h)
@@ -879,9 +792,9 @@ class PresigPool:
         d_slot = self._slots(slots)
         if d_slot.numel() != session.B:
             raise ValueError("deposit: one slot per session row")
-        d_status = torch.empty((session.B,), dtype=torch.int32, device=self.ctx.device)
+        d_status = _new(self.ctx, session.B)
         try:
-            N_.check(N_.lib.mpe_gg20_presig_deposit(self.h, session.h, _ptr(d_slot), _ptr(d_status), self.ctx.stream()), "mpe_gg20_presig_deposit")
+            N_.call.mpe_gg20_presig_deposit(self.h, session.h, _ptr(d_slot), _ptr(d_status), self.ctx.stream())
         except N_.MpeError:
             if mine:
                 self._used.difference_update(slots)
@@ -892,21 +805,19 @@ class PresigPool:
         """`Round7::new` for READY slots: (s_i [L, count, 8], status [count]) device tensors; msg [count, 8] as round 7 takes it"""
         d_slot = self._slots(slots)
         count = d_slot.numel()
-        s_i = torch.empty((self.L, count, 8), dtype=torch.int32, device=self.ctx.device)
-        status = torch.empty((count,), dtype=torch.int32, device=self.ctx.device)
-        N_.check(N_.lib.mpe_gg20_presig_sign(self.h, count, _ptr(d_slot), _ptr(msg), _ptr(s_i), _ptr(status), self.ctx.stream()), "mpe_gg20_presig_sign")
+        s_i, status = _new(self.ctx, self.L, count, 8), _new(self.ctx, count)
+        N_.call.mpe_gg20_presig_sign(self.h, count, _ptr(d_slot), _ptr(msg), _ptr(s_i), _ptr(status), self.ctx.stream())
         return s_i, status
 
     def complete(self, slots, d_in, in_off=None):
         """`SignManual::complete` for SIGNED slots.  d_in: the partial signatures of all S senders (sender j's [count][8] block at record
         in_off[j], default j * count).  Returns dict r, s [L, count, 8], recid, status [L, count]; the slots are EMPTY afterwards."""
         d_slot = self._slots(slots)
-        count, L, dv = d_slot.numel(), self.L, self.ctx.device
-        o = dict(r=torch.empty((L, count, 8), dtype=torch.int32, device=dv), s=torch.empty((L, count, 8), dtype=torch.int32, device=dv),
-                 recid=torch.empty((L, count), dtype=torch.int32, device=dv), status=torch.empty((L, count), dtype=torch.int32, device=dv))
+        count, L, ctx = d_slot.numel(), self.L, self.ctx
+        o = dict(r=_new(ctx, L, count, 8), s=_new(ctx, L, count, 8), recid=_new(ctx, L, count), status=_new(ctx, L, count))
         off = None if in_off is None else (C.c_int64 * self.S)(*[int(x) for x in in_off])
-        N_.check(N_.lib.mpe_gg20_presig_complete(self.h, count, _ptr(d_slot), _ptr(d_in), off, _ptr(o["r"]), _ptr(o["s"]), _ptr(o["recid"]),
-                                                 _ptr(o["status"]), self.ctx.stream()), "mpe_gg20_presig_complete")
+        N_.call.mpe_gg20_presig_complete(self.h, count, _ptr(d_slot), _ptr(d_in), off, _ptr(o["r"]), _ptr(o["s"]), _ptr(o["recid"]), _ptr(o["status"]),
+                                         self.ctx.stream())
         self._pending.append((d_slot, o["status"]))          # 0 and 701 emptied the slot, 821 / 822 did not
         return o
 
@@ -914,11 +825,9 @@ class PresigPool:
         """The online step in one launch (mpe_gg20_sign_online; the pool holds every signer): what gg20_sign_online returns —
         r, s [count, 8], recid, status [count] (811 / 812 from the claim, 701 when the one verify fails; zero outputs unless 0)."""
         d_slot = self._slots(slots)
-        count, dv = d_slot.numel(), self.ctx.device
-        r, s = torch.empty((count, 8), dtype=torch.int32, device=dv), torch.empty((count, 8), dtype=torch.int32, device=dv)
-        recid, status = torch.empty((count,), dtype=torch.int32, device=dv), torch.empty((count,), dtype=torch.int32, device=dv)
-        N_.check(N_.lib.mpe_gg20_sign_online(self.h, count, _ptr(d_slot), _ptr(msg), _ptr(r), _ptr(s), _ptr(recid), _ptr(status),
-                                                    self.ctx.stream()), "mpe_gg20_sign_online")
+        count, ctx = d_slot.numel(), self.ctx
+        r, s, recid, status = _new(ctx, count, 8), _new(ctx, count, 8), _new(ctx, count), _new(ctx, count)
+        N_.call.mpe_gg20_sign_online(self.h, count, _ptr(d_slot), _ptr(msg), _ptr(r), _ptr(s), _ptr(recid), _ptr(status), self.ctx.stream())
         self._pending.append((d_slot, status))              # 0 and 701 emptied the slot, 811 / 812 did not
         return r, s, recid, status
 
@@ -927,13 +836,11 @@ class PresigPool:
         wrap (a WrapKey): the records leave sealed, [count, sealed_words] (mpe_gg20_sealed_presig_export)"""
         d_slot = self._slots(slots)
         count = d_slot.numel()
-        rec = torch.empty((count, self.record_words if wrap is None else self.sealed_words), dtype=torch.int32, device=self.ctx.device)
-        status = torch.empty((count,), dtype=torch.int32, device=self.ctx.device)
+        rec, status = _new(self.ctx, count, self.record_words if wrap is None else self.sealed_words), _new(self.ctx, count)
         if wrap is None:
-            N_.check(N_.lib.mpe_gg20_presig_export(self.h, count, _ptr(d_slot), _ptr(rec), _ptr(status), self.ctx.stream()), "mpe_gg20_presig_export")
+            N_.call.mpe_gg20_presig_export(self.h, count, _ptr(d_slot), _ptr(rec), _ptr(status), self.ctx.stream())
         else:
-            N_.check(N_.lib.mpe_gg20_sealed_presig_export(self.h, wrap.h, count, _ptr(d_slot), WrapKey.nonce(nonce_hi), _ptr(rec), _ptr(status),
-                                                          self.ctx.stream()), "mpe_gg20_sealed_presig_export")
+            N_.call.mpe_gg20_sealed_presig_export(self.h, wrap.h, count, _ptr(d_slot), WrapKey.nonce(nonce_hi), _ptr(rec), _ptr(status), self.ctx.stream())
         self._pending.append((d_slot, status))
         return rec, status
 
@@ -946,36 +853,26 @@ class PresigPool:
             slots = self._take(count)
             self._used.update(slots)
         d_slot = self._slots(slots)
-        status = torch.empty((count,), dtype=torch.int32, device=self.ctx.device)
+        status = _new(self.ctx, count)
         if wrap is None:
-            N_.check(N_.lib.mpe_gg20_presig_import(self.h, count, _ptr(d_slot), _ptr(records.contiguous()), _ptr(status), self.ctx.stream()),
-                     "mpe_gg20_presig_import")
+            N_.call.mpe_gg20_presig_import(self.h, count, _ptr(d_slot), _ptr(records.contiguous()), _ptr(status), self.ctx.stream())
         else:
-            N_.check(N_.lib.mpe_gg20_sealed_presig_import(self.h, wrap.h, count, _ptr(d_slot), _ptr(records.contiguous()), _ptr(status),
-                                                          self.ctx.stream()), "mpe_gg20_sealed_presig_import")
+            N_.call.mpe_gg20_sealed_presig_import(self.h, wrap.h, count, _ptr(d_slot), _ptr(records.contiguous()), _ptr(status), self.ctx.stream())
         return self._filled(d_slot.cpu().numpy(), status.cpu().numpy(), not mine)
 
     def discard(self, slots):
         d_slot = self._slots(slots)
-        N_.check(N_.lib.mpe_gg20_presig_discard(self.h, d_slot.numel(), _ptr(d_slot), self.ctx.stream()), "mpe_gg20_presig_discard")
+        N_.call.mpe_gg20_presig_discard(self.h, d_slot.numel(), _ptr(d_slot), self.ctx.stream())
         self._pending.append((d_slot[(d_slot >= 0) & (d_slot < self.capacity)], None))
 
     def audit(self):
         """dict EMPTY, READY, SIGNED, BUSY (slots per state) and stray (non-zero words of k_i, sigma_i outside READY slots: must be 0)"""
         out = (C.c_int64 * 5)()
-        N_.check(N_.lib.mpe_gg20_presig_pool_audit(self.h, out, self.ctx.stream()), "mpe_gg20_presig_pool_audit")
+        N_.call.mpe_gg20_presig_pool_audit(self.h, out, self.ctx.stream())
         return dict(zip(self.STATES + ("stray",), [int(x) for x in out]))
 
-    def close(self):
-        if self.h:
-            N_.lib.mpe_gg20_presig_pool_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _destroy(self):
+        N_.lib.mpe_gg20_presig_pool_destroy(self.h)
 
 
 def gg20_presign(ctx, keys, nonces, B, pool, keyset=None, dedup_verify=False, sigset=None):
@@ -1011,8 +908,8 @@ def gg20_presign_fused(ctx, keys, nonces, B, pool, slots=None, keyset=None, dedu
     d_status = torch.full((B,), -1, dtype=torch.int32, device=ctx.device)
     nn = _struct(N_.Gg20Nonces, _no_msg(ctx, nonces))
     try:
-        N_.check(N_.lib.mpe_gg20_presign_sets(ctx.h, keys.h, B, _ptr(keyset), _ptr(sigset), C.byref(nn), pool.h, _ptr(d_slot), _ptr(d_status),
-                                              int(bool(dedup_verify)), int(chunk), ctx.stream()), "mpe_gg20_presign_sets")
+        N_.call.mpe_gg20_presign_sets(ctx.h, keys.h, B, _ptr(keyset), _ptr(sigset), C.byref(nn), pool.h, _ptr(d_slot), _ptr(d_status), int(bool(dedup_verify)),
+                                      int(chunk), ctx.stream())
     except N_.MpeError:
         if mine:
             pool._used.difference_update(slots)
@@ -1036,7 +933,7 @@ def gg20_sign_online(pool, slots, msg):
 PLACE_PARTY, PLACE_ROTATED = 0, 1
 
 
-class Comm:
+class Comm(_Handle):
     """mpe_comm_*: the RCCL communicator of the round fan-out behind the C-ABI (include/mpecdsa_hip.h).  `exchange_id(id_or_None)`:
     a callable that carries rank 0's 128 id bytes to every rank (e.g. a torch.distributed broadcast, a file, a socket)."""
     ID_BYTES = 128
@@ -1045,35 +942,27 @@ class Comm:
         self.ctx = ctx
         buf = C.create_string_buffer(self.ID_BYTES)
         if rank == 0:
-            N_.check(N_.lib.mpe_comm_unique_id(buf), "mpe_comm_unique_id")
+            N_.call.mpe_comm_unique_id(buf)
         ident = buf.raw
         if world > 1 or exchange_id is not None:
             ident = bytes(exchange_id(ident if rank == 0 else None))
         h = C.c_void_p()
-        N_.check(N_.lib.mpe_comm_create(ctx.h, ident, rank, world, C.byref(h)), "mpe_comm_create")
+        N_.call.mpe_comm_create(ctx.h, ident, rank, world, C.byref(h))
         self.h, self.rank, self.world = h, rank, world
 
     def layout_self_test(self, rows_per_rank):
         mode, ok = C.c_int(-1), C.c_int(0)
-        N_.check(N_.lib.mpe_comm_layout_self_test(self.h, rows_per_rank, C.byref(mode), C.byref(ok), self.ctx.stream()), "mpe_comm_layout_self_test")
+        N_.call.mpe_comm_layout_self_test(self.h, rows_per_rank, C.byref(mode), C.byref(ok), self.ctx.stream())
         return dict(mode=("inplace", "copy")[mode.value], ok=bool(ok.value))
 
     def all_gather(self, buf, bytes_per_rank):
-        N_.check(N_.lib.mpe_comm_all_gather(self.h, _ptr(buf), bytes_per_rank, self.ctx.stream()), "mpe_comm_all_gather")
+        N_.call.mpe_comm_all_gather(self.h, _ptr(buf), bytes_per_rank, self.ctx.stream())
 
     def round_exchange(self, S, n, rnd, per_rank, batch, slab):
-        N_.check(N_.lib.mpe_gg20_round_exchange(self.h, S, n, rnd, per_rank, batch, _ptr(slab), self.ctx.stream()), "mpe_gg20_round_exchange")
+        N_.call.mpe_gg20_round_exchange(self.h, S, n, rnd, per_rank, batch, _ptr(slab), self.ctx.stream())
 
-    def close(self):
-        if self.h:
-            N_.lib.mpe_comm_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _destroy(self):
+        N_.lib.mpe_comm_destroy(self.h)
 
 
 def comm_library():
@@ -1081,23 +970,23 @@ def comm_library():
     (PyTorch's own copy), "version": ncclGetVersion}"""
     buf = C.create_string_buffer(4096)
     ad, ver = C.c_int(0), C.c_int(0)
-    N_.check(N_.lib.mpe_comm_library(buf, 4096, C.byref(ad), C.byref(ver)), "mpe_comm_library")
+    N_.call.mpe_comm_library(buf, 4096, C.byref(ad), C.byref(ver))
     return dict(path=buf.value.decode(), adopted=bool(ad.value), version=ver.value)
 
 
 def shard_where(placement, S, world, block, party):
     r, s = C.c_int(0), C.c_int(0)
-    N_.check(N_.lib.mpe_gg20_shard_where(placement, S, world, block, party, C.byref(r), C.byref(s)), "mpe_gg20_shard_where")
+    N_.call.mpe_gg20_shard_where(placement, S, world, block, party, C.byref(r), C.byref(s))
     return r.value, s.value
 
 
 def shard_in_off(placement, S, world, batch, block):
     off = (C.c_int64 * S)()
-    N_.check(N_.lib.mpe_gg20_shard_in_off(placement, S, world, batch, block, off), "mpe_gg20_shard_in_off")
+    N_.call.mpe_gg20_shard_in_off(placement, S, world, batch, block, off)
     return list(off)
 
 
-class Gg20Pipeline:
+class Gg20Pipeline(_Handle):
     """mpe_gg20_pipeline_*: a stream of `batch`-session batches, `group` of them coalesced per pass, `lanes` passes in flight on one
     stream each (include/mpecdsa_hip.h).  submit / submit_seeded return a ticket; the result tensors of a ticket are valid after
     wait(ticket) (or after stream_wait on the consuming stream).  With `pool=` (a PresigPool over all S signers of `keys`) the object is
@@ -1107,17 +996,15 @@ class Gg20Pipeline:
         self.ctx, self.keys, self.batch, self.group, self.lanes, self.pool = ctx, keys, batch, group, lanes, pool
         h = C.c_void_p()
         if pool is None:
-            N_.check(N_.lib.mpe_gg20_pipeline_create(ctx.h, keys.h, batch, group, lanes, int(bool(dedup_verify)), C.byref(h)), "mpe_gg20_pipeline_create")
+            N_.call.mpe_gg20_pipeline_create(ctx.h, keys.h, batch, group, lanes, int(bool(dedup_verify)), C.byref(h))
         else:
-            N_.check(N_.lib.mpe_gg20_pipeline_create_presig(ctx.h, keys.h, pool.h, batch, group, lanes, int(bool(dedup_verify)), C.byref(h)),
-                     "mpe_gg20_pipeline_create_presig")
+            N_.call.mpe_gg20_pipeline_create_presig(ctx.h, keys.h, pool.h, batch, group, lanes, int(bool(dedup_verify)), C.byref(h))
         self.h = h
         self._keep = {}                       # ticket -> the tensors the device still reads / writes
 
     def _outs(self, want_R):
         B = self.batch
-        r, s = _new(self.ctx, B, 8), _new(self.ctx, B, 8)
-        recid = torch.empty((B,), dtype=torch.int32, device=self.ctx.device)
+        r, s, recid = _new(self.ctx, B, 8), _new(self.ctx, B, 8), _new(self.ctx, B)
         status = torch.full((B,), -1, dtype=torch.int32, device=self.ctx.device)
         R = _new(self.ctx, B, 16) if want_R else None
         return r, s, recid, status, R
@@ -1128,11 +1015,11 @@ class Gg20Pipeline:
         nn = _struct(N_.Gg20Nonces, nonces)
         t = C.c_uint64(0)
         if sigset is None:
-            N_.check(N_.lib.mpe_gg20_pipeline_submit(self.h, _ptr(keyset), C.byref(nn), _ptr(r), _ptr(s), _ptr(recid), _ptr(R), _ptr(status),
-                                                     self.ctx.stream(), C.byref(t)), "mpe_gg20_pipeline_submit")
+            N_.call.mpe_gg20_pipeline_submit(self.h, _ptr(keyset), C.byref(nn), _ptr(r), _ptr(s), _ptr(recid), _ptr(R), _ptr(status), self.ctx.stream(),
+                                             C.byref(t))
         else:
-            N_.check(N_.lib.mpe_gg20_pipeline_submit_sets(self.h, _ptr(keyset), _ptr(sigset), C.byref(nn), _ptr(r), _ptr(s), _ptr(recid), _ptr(R),
-                                                          _ptr(status), self.ctx.stream(), C.byref(t)), "mpe_gg20_pipeline_submit_sets")
+            N_.call.mpe_gg20_pipeline_submit_sets(self.h, _ptr(keyset), _ptr(sigset), C.byref(nn), _ptr(r), _ptr(s), _ptr(recid), _ptr(R), _ptr(status),
+                                                  self.ctx.stream(), C.byref(t))
         self._keep[t.value] = ((nonces, sigset), keyset, r, s, recid, status, R)
         return t.value
 
@@ -1140,13 +1027,11 @@ class Gg20Pipeline:
         r, s, recid, status, R = self._outs(want_R)
         t = C.c_uint64(0)
         if sigset is None:
-            N_.check(N_.lib.mpe_gg20_pipeline_submit_seeded(self.h, _ptr(keyset), _seed(seed), int(batch_counter), _ptr(msg), _ptr(r), _ptr(s),
-                                                            _ptr(recid), _ptr(R), _ptr(status), self.ctx.stream(), C.byref(t)),
-                     "mpe_gg20_pipeline_submit_seeded")
+            N_.call.mpe_gg20_pipeline_submit_seeded(self.h, _ptr(keyset), _seed(seed), int(batch_counter), _ptr(msg), _ptr(r), _ptr(s), _ptr(recid), _ptr(R),
+                                                    _ptr(status), self.ctx.stream(), C.byref(t))
         else:
-            N_.check(N_.lib.mpe_gg20_pipeline_submit_seeded_sets(self.h, _ptr(keyset), _ptr(sigset), _seed(seed), int(batch_counter), _ptr(msg), _ptr(r),
-                                                                 _ptr(s), _ptr(recid), _ptr(R), _ptr(status), self.ctx.stream(), C.byref(t)),
-                     "mpe_gg20_pipeline_submit_seeded_sets")
+            N_.call.mpe_gg20_pipeline_submit_seeded_sets(self.h, _ptr(keyset), _ptr(sigset), _seed(seed), int(batch_counter), _ptr(msg), _ptr(r), _ptr(s),
+                                                         _ptr(recid), _ptr(R), _ptr(status), self.ctx.stream(), C.byref(t))
         self._keep[t.value] = ((msg, sigset), keyset, r, s, recid, status, R)
         return t.value
 
@@ -1172,8 +1057,7 @@ class Gg20Pipeline:
         nn = _struct(N_.Gg20Nonces, _no_msg(self.ctx, nonces))
         t = C.c_uint64(0)
         try:
-            N_.check(N_.lib.mpe_gg20_pipeline_submit_presig(self.h, _ptr(keyset), _ptr(sigset), C.byref(nn), _ptr(d_slot), _ptr(status),
-                                                            self.ctx.stream(), C.byref(t)), "mpe_gg20_pipeline_submit_presig")
+            N_.call.mpe_gg20_pipeline_submit_presig(self.h, _ptr(keyset), _ptr(sigset), C.byref(nn), _ptr(d_slot), _ptr(status), self.ctx.stream(), C.byref(t))
         except N_.MpeError:
             self.pool._used.difference_update(fresh)
             raise
@@ -1184,8 +1068,8 @@ class Gg20Pipeline:
         d_slot, h_slot, fresh, status = self._presig_slots(slots)
         t = C.c_uint64(0)
         try:
-            N_.check(N_.lib.mpe_gg20_pipeline_submit_presig_seeded(self.h, _ptr(keyset), _ptr(sigset), _seed(seed), int(batch_counter), _ptr(d_slot),
-                                                                   _ptr(status), self.ctx.stream(), C.byref(t)), "mpe_gg20_pipeline_submit_presig_seeded")
+            N_.call.mpe_gg20_pipeline_submit_presig_seeded(self.h, _ptr(keyset), _ptr(sigset), _seed(seed), int(batch_counter), _ptr(d_slot), _ptr(status),
+                                                           self.ctx.stream(), C.byref(t))
         except N_.MpeError:
             self.pool._used.difference_update(fresh)
             raise
@@ -1205,7 +1089,7 @@ class Gg20Pipeline:
     def ticket_rc(self, ticket):
         """(launched, rc) of the pass that carries the batch (rc = MPE_OK while its group is still open)"""
         la, rc = C.c_int(0), C.c_int(0)
-        N_.check(N_.lib.mpe_gg20_pipeline_ticket_rc(self.h, ticket, C.byref(la), C.byref(rc)), "mpe_gg20_pipeline_ticket_rc")
+        N_.call.mpe_gg20_pipeline_ticket_rc(self.h, ticket, C.byref(la), C.byref(rc))
         return bool(la.value), rc.value
 
     def wait(self, ticket, want_R=False, check=True):
@@ -1229,50 +1113,42 @@ class Gg20Pipeline:
         return (r, s, recid, status, R) if want_R else (r, s, recid, status)
 
     def set_deadline_us(self, us):
-        N_.check(N_.lib.mpe_gg20_pipeline_set_deadline_us(self.h, int(us)), "mpe_gg20_pipeline_set_deadline_us")
+        N_.call.mpe_gg20_pipeline_set_deadline_us(self.h, int(us))
 
     def set_eager(self, on=True):
-        N_.check(N_.lib.mpe_gg20_pipeline_set_eager(self.h, int(bool(on))), "mpe_gg20_pipeline_set_eager")
+        N_.call.mpe_gg20_pipeline_set_eager(self.h, int(bool(on)))
 
     def poll(self):
         la = C.c_int(0)
-        N_.check(N_.lib.mpe_gg20_pipeline_poll(self.h, C.byref(la)), "mpe_gg20_pipeline_poll")
+        N_.call.mpe_gg20_pipeline_poll(self.h, C.byref(la))
         return bool(la.value)
 
     def inject_fault(self, passes=1, rc=N_.MPE_E_NOMEM):
-        N_.check(N_.lib.mpe_gg20_pipeline_inject_fault(self.h, int(passes), int(rc)), "mpe_gg20_pipeline_inject_fault")
+        N_.call.mpe_gg20_pipeline_inject_fault(self.h, int(passes), int(rc))
 
     def counters(self):
         v = [C.c_uint64(0) for _ in range(4)]
-        N_.check(N_.lib.mpe_gg20_pipeline_counters(self.h, *[C.byref(x) for x in v]), "mpe_gg20_pipeline_counters")
+        N_.call.mpe_gg20_pipeline_counters(self.h, *[C.byref(x) for x in v])
         return dict(zip(("groups", "by_deadline", "by_idle", "failed"), (x.value for x in v)))
 
     def latency_ms(self, ticket):
         ms = C.c_float(0)
-        N_.check(N_.lib.mpe_gg20_pipeline_latency_ms(self.h, ticket, C.byref(ms)), "mpe_gg20_pipeline_latency_ms")
+        N_.call.mpe_gg20_pipeline_latency_ms(self.h, ticket, C.byref(ms))
         return ms.value
 
     def pass_ms(self, ticket):
         ms = C.c_float(0)
-        N_.check(N_.lib.mpe_gg20_pipeline_pass_ms(self.h, ticket, C.byref(ms)), "mpe_gg20_pipeline_pass_ms")
+        N_.call.mpe_gg20_pipeline_pass_ms(self.h, ticket, C.byref(ms))
         return ms.value
 
     def sampler_failures(self):
         v = C.c_int32(0)
-        N_.check(N_.lib.mpe_gg20_pipeline_sampler_failures(self.h, C.byref(v)), "mpe_gg20_pipeline_sampler_failures")
+        N_.call.mpe_gg20_pipeline_sampler_failures(self.h, C.byref(v))
         return v.value
 
-    def close(self):
-        if self.h:
-            N_.lib.mpe_gg20_pipeline_destroy(self.h)
-            self.h = None
-            self._keep.clear()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _destroy(self):
+        N_.lib.mpe_gg20_pipeline_destroy(self.h)
+        self._keep.clear()
 
 
 # ---- the sampling side of the trait surface (mpe_sample.h): curv Samplable / from_modulo / Scalar::random on the device ----
@@ -1288,7 +1164,7 @@ def _seed(seed):
 
 def sample_bits(ctx, batch, seed, stream_id, bits, out_words):
     out = _new(ctx, batch, out_words)
-    N_.check(N_.lib.mpe_sample_bits(ctx.h, batch, _seed(seed), stream_id, bits, out_words, _ptr(out), ctx.stream()), "mpe_sample_bits")
+    N_.call.mpe_sample_bits(ctx.h, batch, _seed(seed), stream_id, bits, out_words, _ptr(out), ctx.stream())
     return out
 
 
@@ -1296,15 +1172,15 @@ def sample_below(ctx, batch, seed, stream_id, d_bound, out_words, d_bound_idx=No
     """d_bound: device int32 [nbounds, bound_words]; returns (values [batch, out_words], failures as a device int32 [1])"""
     out = _new(ctx, batch, out_words)
     fail = torch.zeros((1,), dtype=torch.int32, device=ctx.device)
-    N_.check(N_.lib.mpe_sample_below(ctx.h, batch, _seed(seed), stream_id, _ptr(d_bound), d_bound.shape[1], d_bound.shape[0], _ptr(d_bound_idx), flags,
-                                     out_words, _ptr(out), _ptr(fail), ctx.stream()), "mpe_sample_below")
+    N_.call.mpe_sample_below(ctx.h, batch, _seed(seed), stream_id, _ptr(d_bound), d_bound.shape[1], d_bound.shape[0], _ptr(d_bound_idx), flags, out_words,
+                             _ptr(out), _ptr(fail), ctx.stream())
     return out, fail
 
 
 def sample_scalar(ctx, batch, seed, stream_id):
     out = _new(ctx, batch, 8)
     fail = torch.zeros((1,), dtype=torch.int32, device=ctx.device)
-    N_.check(N_.lib.mpe_sample_scalar(ctx.h, batch, _seed(seed), stream_id, _ptr(out), _ptr(fail), ctx.stream()), "mpe_sample_scalar")
+    N_.call.mpe_sample_scalar(ctx.h, batch, _seed(seed), stream_id, _ptr(out), _ptr(fail), ctx.stream())
     return out, fail
 
 
@@ -1327,11 +1203,10 @@ def gg20_sample_nonces(ctx, keys, B, seed, batch_counter, local=None, keyset=Non
     nn = _struct(N_.Gg20Nonces, out)
     lc = (C.c_int32 * len(local))(*local)
     if sigset is None and not by_party:
-        N_.check(N_.lib.mpe_gg20_sample_nonces(ctx.h, keys.h, B, len(local), lc, _ptr(keyset), _seed(seed), int(batch_counter), C.byref(nn), _ptr(fail),
-                                               ctx.stream()), "mpe_gg20_sample_nonces")
+        N_.call.mpe_gg20_sample_nonces(ctx.h, keys.h, B, len(local), lc, _ptr(keyset), _seed(seed), int(batch_counter), C.byref(nn), _ptr(fail), ctx.stream())
     else:
-        N_.check(N_.lib.mpe_gg20_sample_nonces_sets(ctx.h, keys.h, B, len(local), lc, _ptr(keyset), _ptr(sigset), int(by_party), _seed(seed),
-                                                    int(batch_counter), C.byref(nn), _ptr(fail), ctx.stream()), "mpe_gg20_sample_nonces_sets")
+        N_.call.mpe_gg20_sample_nonces_sets(ctx.h, keys.h, B, len(local), lc, _ptr(keyset), _ptr(sigset), int(by_party), _seed(seed), int(batch_counter),
+                                            C.byref(nn), _ptr(fail), ctx.stream())
     return out, fail
 
 
@@ -1339,7 +1214,7 @@ def gg20_sample_nonces(ctx, keys, B, seed, batch_counter, local=None, keyset=Non
 def is_probable_prime(ctx, d_n, rounds=8):
     """d_n: device words [B, 32] -> uint8 [B]: trial division below 6370, then `rounds` Miller-Rabin tests to the FIXED bases 2, 3, 5, ..."""
     ok = _flags(ctx, d_n.shape[0])
-    N_.check(N_.lib.mpe_is_probable_prime(ctx.h, d_n.shape[0], _ptr(d_n), rounds, _ptr(ok), ctx.stream()), "mpe_is_probable_prime")
+    N_.call.mpe_is_probable_prime(ctx.h, d_n.shape[0], _ptr(d_n), rounds, _ptr(ok), ctx.stream())
     return ok
 
 
@@ -1348,8 +1223,7 @@ def sample_prime(ctx, batch, seed, stream_id, bits=1024, max_attempts=0):
     out = _new(ctx, batch, bits // 32)
     attempt = torch.zeros((batch,), dtype=torch.int32, device=ctx.device)
     fail = torch.zeros((1,), dtype=torch.int32, device=ctx.device)
-    N_.check(N_.lib.mpe_sample_prime(ctx.h, batch, _seed(seed), stream_id, bits, max_attempts, _ptr(out), _ptr(attempt), _ptr(fail), ctx.stream()),
-             "mpe_sample_prime")
+    N_.call.mpe_sample_prime(ctx.h, batch, _seed(seed), stream_id, bits, max_attempts, _ptr(out), _ptr(attempt), _ptr(fail), ctx.stream())
     return out, attempt, fail
 
 
@@ -1359,8 +1233,7 @@ def sample_safe_prime(ctx, batch, seed, stream_id, bits=1024, max_attempts=0):
     out = _new(ctx, batch, bits // 32)
     attempt = torch.zeros((batch,), dtype=torch.int32, device=ctx.device)
     fail = torch.zeros((1,), dtype=torch.int32, device=ctx.device)
-    N_.check(N_.lib.mpe_sample_safe_prime(ctx.h, batch, _seed(seed), stream_id, bits, max_attempts, _ptr(out), _ptr(attempt), _ptr(fail), ctx.stream()),
-             "mpe_sample_safe_prime")
+    N_.call.mpe_sample_safe_prime(ctx.h, batch, _seed(seed), stream_id, bits, max_attempts, _ptr(out), _ptr(attempt), _ptr(fail), ctx.stream())
     return out, attempt, fail
 
 
@@ -1368,7 +1241,7 @@ def prime_search_counts(ctx, reset=False):
     """what this context's prime searches counted so far, a measurement aid: attempts sieved and the length of the list behind each stage,
     for the plain search (3 figures) and the safe one (6)"""
     v = (C.c_int64 * 9)()
-    N_.check(N_.lib.mpe_prime_search_counts(ctx.h, v, int(reset)), "mpe_prime_search_counts")
+    N_.call.mpe_prime_search_counts(ctx.h, v, int(reset))
     names = ("attempts", "sieve", "round1", "safe_attempts", "safe_sieve_head", "safe_sieve", "safe_round1_c", "safe_round1_half", "safe_rounds2_8_c")
     return dict(zip(names, (int(x) for x in v)))
 
@@ -1379,7 +1252,7 @@ def paillier_keygen(ctx, nkeys, seed, counter, max_attempts=0, safe_primes=False
     p, q, n = _new(ctx, nkeys, 32), _new(ctx, nkeys, 32), _new(ctx, nkeys, 64)
     fail = torch.zeros((1,), dtype=torch.int32, device=ctx.device)
     name = "mpe_paillier_keygen_safe_primes" if safe_primes else "mpe_paillier_keygen"
-    N_.check(getattr(N_.lib, name)(ctx.h, nkeys, _seed(seed), int(counter), max_attempts, _ptr(p), _ptr(q), _ptr(n), _ptr(fail), ctx.stream()), name)
+    getattr(N_.call, name)(ctx.h, nkeys, _seed(seed), int(counter), max_attempts, _ptr(p), _ptr(q), _ptr(n), _ptr(fail), ctx.stream())
     return p, q, n, fail
 
 
@@ -1389,8 +1262,8 @@ def ntilde_generate(ctx, count, seed, counter, max_attempts=0, safe_primes=False
     o = {f: _new(ctx, count, 64) for f in ("Nt", "h1", "h2", "xhi", "xhi_inv")}
     fail = torch.zeros((1,), dtype=torch.int32, device=ctx.device)
     name = "mpe_ntilde_generate_safe_primes" if safe_primes else "mpe_ntilde_generate"
-    N_.check(getattr(N_.lib, name)(ctx.h, count, _seed(seed), int(counter), max_attempts, _ptr(o["Nt"]), _ptr(o["h1"]), _ptr(o["h2"]), _ptr(o["xhi"]),
-                                   _ptr(o["xhi_inv"]), _ptr(fail), ctx.stream()), name)
+    getattr(N_.call, name)(ctx.h, count, _seed(seed), int(counter), max_attempts, _ptr(o["Nt"]), _ptr(o["h1"]), _ptr(o["h2"]), _ptr(o["xhi"]),
+                           _ptr(o["xhi_inv"]), _ptr(fail), ctx.stream())
     o["fail"] = fail
     return o
 
@@ -1398,14 +1271,13 @@ def ntilde_generate(ctx, count, seed, counter, max_attempts=0, safe_primes=False
 # ---- keygen verification math (gg_2020/party_i.rs:260-438) ----
 def correct_key_verify(ctx, d_N, d_sigma):
     ok = _flags(ctx, d_N.shape[0])
-    N_.check(N_.lib.mpe_correct_key_verify(ctx.h, d_N.shape[0], _ptr(d_N), _ptr(d_sigma), _ptr(ok), ctx.stream()), "mpe_correct_key_verify")
+    N_.call.mpe_correct_key_verify(ctx.h, d_N.shape[0], _ptr(d_N), _ptr(d_sigma), _ptr(ok), ctx.stream())
     return ok
 
 
 def composite_dlog_verify(ctx, d_N, d_g, d_ni, d_x, d_y):
     ok = _flags(ctx, d_N.shape[0])
-    N_.check(N_.lib.mpe_composite_dlog_verify(ctx.h, d_N.shape[0], _ptr(d_N), _ptr(d_g), _ptr(d_ni), _ptr(d_x), _ptr(d_y), _ptr(ok),
-                                              ctx.stream()), "mpe_composite_dlog_verify")
+    N_.call.mpe_composite_dlog_verify(ctx.h, d_N.shape[0], _ptr(d_N), _ptr(d_g), _ptr(d_ni), _ptr(d_x), _ptr(d_y), _ptr(ok), ctx.stream())
     return ok
 
 
@@ -1416,7 +1288,7 @@ def keygen_verify_round1(ctx, n_parties, msgs):
     ok = _flags(ctx, B)
     bad = torch.zeros((B // n_parties,), dtype=torch.int32, device=ctx.device)
     st = _struct(N_.KeygenRound1, msgs)
-    N_.check(N_.lib.mpe_keygen_verify_round1(ctx.h, B, n_parties, C.byref(st), _ptr(ok), _ptr(bad), ctx.stream()), "mpe_keygen_verify_round1")
+    N_.call.mpe_keygen_verify_round1(ctx.h, B, n_parties, C.byref(st), _ptr(ok), _ptr(bad), ctx.stream())
     return ok, bad
 
 
@@ -1425,37 +1297,33 @@ def keygen_verify_round2(ctx, n_parties, t1, d_commits, d_share, d_index, d_y):
     B = d_share.shape[0]
     ok = _flags(ctx, B)
     bad = torch.zeros((B // n_parties,), dtype=torch.int32, device=ctx.device)
-    N_.check(N_.lib.mpe_keygen_verify_round2(ctx.h, B, n_parties, t1, _ptr(d_commits), _ptr(d_share), _ptr(d_index), _ptr(d_y), _ptr(ok), _ptr(bad),
-                                             ctx.stream()), "mpe_keygen_verify_round2")
+    N_.call.mpe_keygen_verify_round2(ctx.h, B, n_parties, t1, _ptr(d_commits), _ptr(d_share), _ptr(d_index), _ptr(d_y), _ptr(ok), _ptr(bad), ctx.stream())
     return ok, bad
 
 
 def correct_key_prove(ctx, sk):
     """`NiCorrectKeyProof::proof` for every key of a private key set: sigma [nkeys, 11, 64]"""
     sigma = torch.zeros((sk.nkeys, 11, 64), dtype=torch.int32, device=ctx.device)
-    N_.check(N_.lib.mpe_correct_key_prove(ctx.h, sk.h, _ptr(sigma), ctx.stream()), "mpe_correct_key_prove")
+    N_.call.mpe_correct_key_prove(ctx.h, sk.h, _ptr(sigma), ctx.stream())
     return sigma
 
 
 def composite_dlog_prove(ctx, d_N, d_g, d_ni, d_secret, d_r):
     B = d_N.shape[0]
     x, y = _new(ctx, B, 64), _new(ctx, B, 73)
-    N_.check(N_.lib.mpe_composite_dlog_prove(ctx.h, B, _ptr(d_N), _ptr(d_g), _ptr(d_ni), _ptr(d_secret), _ptr(d_r), _ptr(x), _ptr(y), ctx.stream()),
-             "mpe_composite_dlog_prove")
+    N_.call.mpe_composite_dlog_prove(ctx.h, B, _ptr(d_N), _ptr(d_g), _ptr(d_ni), _ptr(d_secret), _ptr(d_r), _ptr(x), _ptr(y), ctx.stream())
     return x, y
 
 
 def vss_validate_share(ctx, t1, d_commits, d_share, d_index):
     ok = _flags(ctx, d_share.shape[0])
-    N_.check(N_.lib.mpe_vss_validate_share(ctx.h, d_share.shape[0], t1, _ptr(d_commits), _ptr(d_share), _ptr(d_index), _ptr(ok), ctx.stream()),
-             "mpe_vss_validate_share")
+    N_.call.mpe_vss_validate_share(ctx.h, d_share.shape[0], t1, _ptr(d_commits), _ptr(d_share), _ptr(d_index), _ptr(ok), ctx.stream())
     return ok
 
 
 def vss_point_commitment(ctx, t1, d_commits, d_index):
     out = _new(ctx, d_index.shape[0], 16)
-    N_.check(N_.lib.mpe_vss_point_commitment(ctx.h, d_index.shape[0], t1, _ptr(d_commits), _ptr(d_index), _ptr(out), ctx.stream()),
-             "mpe_vss_point_commitment")
+    N_.call.mpe_vss_point_commitment(ctx.h, d_index.shape[0], t1, _ptr(d_commits), _ptr(d_index), _ptr(out), ctx.stream())
     return out
 
 
@@ -1464,9 +1332,8 @@ def vss_share(ctx, n, d_coef):
     """`VerifiableSS::share(t, n, &u_i)` per dealer: d_coef [B, t+1, 8] (coef[0] = u_i) -> (commits [B, t+1, 16], shares [B, n, 8]),
     shares[b, j] = f_b(j + 1).  A zero coefficient gives a neutral commitment row, which vss_validate_share refuses."""
     B, t1 = d_coef.shape[0], d_coef.shape[1]
-    commits = torch.empty((B, t1, 16), dtype=torch.int32, device=ctx.device)
-    shares = torch.empty((B, n, 8), dtype=torch.int32, device=ctx.device)
-    N_.check(N_.lib.mpe_vss_share(ctx.h, B, t1, n, _ptr(d_coef), _ptr(commits), _ptr(shares), ctx.stream()), "mpe_vss_share")
+    commits, shares = _new(ctx, B, t1, 16), _new(ctx, B, n, 8)
+    N_.call.mpe_vss_share(ctx.h, B, t1, n, _ptr(d_coef), _ptr(commits), _ptr(shares), ctx.stream())
     return commits, shares
 
 
@@ -1475,8 +1342,7 @@ def keygen_construct_keypair(ctx, d_shares, d_y, d_nonce):
     d_shares [B, n, 8] received shares in dealer order, d_y [B, n, 16], d_nonce [B, 8] -> (x, ysum, pk, R, z); (pk, R, z) = dlog_prove(x, nonce)"""
     B, n = d_shares.shape[0], d_shares.shape[1]
     x, ysum, pk, R, z = _new(ctx, B, 8), _new(ctx, B, 16), _new(ctx, B, 16), _new(ctx, B, 16), _new(ctx, B, 8)
-    N_.check(N_.lib.mpe_keygen_construct_keypair(ctx.h, B, n, _ptr(d_shares), _ptr(d_y), _ptr(d_nonce), _ptr(x), _ptr(ysum), _ptr(pk), _ptr(R), _ptr(z),
-                                                 ctx.stream()), "mpe_keygen_construct_keypair")
+    N_.call.mpe_keygen_construct_keypair(ctx.h, B, n, _ptr(d_shares), _ptr(d_y), _ptr(d_nonce), _ptr(x), _ptr(ysum), _ptr(pk), _ptr(R), _ptr(z), ctx.stream())
     return x, ysum, pk, R, z
 
 
@@ -1487,8 +1353,7 @@ def keygen_verify_round3(ctx, n_parties, d_commits, d_pk, d_R, d_z, want_xi=Fals
     ok = _flags(ctx, B)
     bad = torch.zeros((B // n_parties,), dtype=torch.int32, device=ctx.device)
     xi = _new(ctx, B, 16) if want_xi else None
-    N_.check(N_.lib.mpe_keygen_verify_round3(ctx.h, B, n_parties, t1, _ptr(d_commits), _ptr(d_pk), _ptr(d_R), _ptr(d_z), _ptr(ok), _ptr(bad), _ptr(xi),
-                                             ctx.stream()), "mpe_keygen_verify_round3")
+    N_.call.mpe_keygen_verify_round3(ctx.h, B, n_parties, t1, _ptr(d_commits), _ptr(d_pk), _ptr(d_R), _ptr(d_z), _ptr(ok), _ptr(bad), _ptr(xi), ctx.stream())
     return (ok, bad, xi) if want_xi else (ok, bad)
 
 
@@ -1588,29 +1453,29 @@ def gg20_keygen(ctx, t, n, B, seed, counter=0, material=None, _fault=None, safe_
 def gg20_blame5(ctx, keys, B, opened, keyset=None, sigset=None):
     """opened: dict of device tensors (fields _native.Blame5In) -> bad_actors bit masks [B] (device int32); sigset: the sessions' signer
     sets (mpe_gg20_blame5_sets)"""
-    bad = torch.empty((B,), dtype=torch.int32, device=ctx.device)
+    bad = _new(ctx, B)
     st_ = _struct(N_.Blame5In, opened)
     if sigset is None:
-        N_.check(N_.lib.mpe_gg20_blame5(ctx.h, keys.h, B, _ptr(keyset), C.byref(st_), _ptr(bad), ctx.stream()), "mpe_gg20_blame5")
+        N_.call.mpe_gg20_blame5(ctx.h, keys.h, B, _ptr(keyset), C.byref(st_), _ptr(bad), ctx.stream())
     else:
-        N_.check(N_.lib.mpe_gg20_blame5_sets(ctx.h, keys.h, B, _ptr(keyset), _ptr(sigset), C.byref(st_), _ptr(bad), ctx.stream()), "mpe_gg20_blame5_sets")
+        N_.call.mpe_gg20_blame5_sets(ctx.h, keys.h, B, _ptr(keyset), _ptr(sigset), C.byref(st_), _ptr(bad), ctx.stream())
     return bad
 
 
 def gg20_blame6(ctx, keys, B, opened, keyset=None, sigset=None):
-    bad = torch.empty((B,), dtype=torch.int32, device=ctx.device)
+    bad = _new(ctx, B)
     st_ = _struct(N_.Blame6In, opened)
     if sigset is None:
-        N_.check(N_.lib.mpe_gg20_blame6(ctx.h, keys.h, B, _ptr(keyset), C.byref(st_), _ptr(bad), ctx.stream()), "mpe_gg20_blame6")
+        N_.call.mpe_gg20_blame6(ctx.h, keys.h, B, _ptr(keyset), C.byref(st_), _ptr(bad), ctx.stream())
     else:
-        N_.check(N_.lib.mpe_gg20_blame6_sets(ctx.h, keys.h, B, _ptr(keyset), _ptr(sigset), C.byref(st_), _ptr(bad), ctx.stream()), "mpe_gg20_blame6_sets")
+        N_.call.mpe_gg20_blame6_sets(ctx.h, keys.h, B, _ptr(keyset), _ptr(sigset), C.byref(st_), _ptr(bad), ctx.stream())
     return bad
 
 
 def gg20_blame7(ctx, S, B, opened):
-    bad = torch.empty((B,), dtype=torch.int32, device=ctx.device)
+    bad = _new(ctx, B)
     st_ = _struct(N_.Blame7In, opened)
-    N_.check(N_.lib.mpe_gg20_blame7(ctx.h, S, B, C.byref(st_), _ptr(bad), ctx.stream()), "mpe_gg20_blame7")
+    N_.call.mpe_gg20_blame7(ctx.h, S, B, C.byref(st_), _ptr(bad), ctx.stream())
     return bad
 
 
@@ -1618,7 +1483,7 @@ def ecddh_prove(ctx, d_x, d_s, statement):
     B = d_x.shape[0]
     out = dict(a1=_new(ctx, B, 16), a2=_new(ctx, B, 16), z=_new(ctx, B, 8))
     stt, pr = _struct(N_.EcddhStatement, statement), _struct(N_.EcddhProof, out)
-    N_.check(N_.lib.mpe_ecddh_prove(ctx.h, B, _ptr(d_x), _ptr(d_s), C.byref(stt), C.byref(pr), ctx.stream()), "mpe_ecddh_prove")
+    N_.call.mpe_ecddh_prove(ctx.h, B, _ptr(d_x), _ptr(d_s), C.byref(stt), C.byref(pr), ctx.stream())
     return out
 
 
@@ -1626,7 +1491,7 @@ def ecddh_verify(ctx, statement, proof):
     B = proof["z"].shape[0]
     ok = _flags(ctx, B)
     stt, pr = _struct(N_.EcddhStatement, statement), _struct(N_.EcddhProof, proof)
-    N_.check(N_.lib.mpe_ecddh_verify(ctx.h, B, C.byref(stt), C.byref(pr), _ptr(ok), ctx.stream()), "mpe_ecddh_verify")
+    N_.call.mpe_ecddh_verify(ctx.h, B, C.byref(stt), C.byref(pr), _ptr(ok), ctx.stream())
     return ok
 
 
@@ -1635,7 +1500,7 @@ def pedersen_prove(ctx, d_m, d_r, d_s1, d_s2):
     B = d_m.shape[0]
     out = dict(com=_new(ctx, B, 16), e=_new(ctx, B, 8), a1=_new(ctx, B, 16), a2=_new(ctx, B, 16), z1=_new(ctx, B, 8), z2=_new(ctx, B, 8))
     pr = _struct(N_.PedersenProof, out)
-    N_.check(N_.lib.mpe_pedersen_prove(ctx.h, B, _ptr(d_m), _ptr(d_r), _ptr(d_s1), _ptr(d_s2), C.byref(pr), ctx.stream()), "mpe_pedersen_prove")
+    N_.call.mpe_pedersen_prove(ctx.h, B, _ptr(d_m), _ptr(d_r), _ptr(d_s1), _ptr(d_s2), C.byref(pr), ctx.stream())
     return out
 
 
@@ -1643,7 +1508,7 @@ def pedersen_verify(ctx, proof):
     B = proof["com"].shape[0]
     ok = _flags(ctx, B)
     pr = _struct(N_.PedersenProof, proof)
-    N_.check(N_.lib.mpe_pedersen_verify(ctx.h, B, C.byref(pr), _ptr(ok), ctx.stream()), "mpe_pedersen_verify")
+    N_.call.mpe_pedersen_verify(ctx.h, B, C.byref(pr), _ptr(ok), ctx.stream())
     return ok
 
 
@@ -1651,7 +1516,7 @@ def heg_prove(ctx, d_x, d_r, d_s1, d_s2, statement):
     B = d_x.shape[0]
     out = dict(T=_new(ctx, B, 16), A3=_new(ctx, B, 16), z1=_new(ctx, B, 8), z2=_new(ctx, B, 8))
     stt, pr = _struct(N_.HegStatement, statement), _struct(N_.HegProof, out)
-    N_.check(N_.lib.mpe_heg_prove(ctx.h, B, _ptr(d_x), _ptr(d_r), _ptr(d_s1), _ptr(d_s2), C.byref(stt), C.byref(pr), ctx.stream()), "mpe_heg_prove")
+    N_.call.mpe_heg_prove(ctx.h, B, _ptr(d_x), _ptr(d_r), _ptr(d_s1), _ptr(d_s2), C.byref(stt), C.byref(pr), ctx.stream())
     return out
 
 
@@ -1659,13 +1524,13 @@ def heg_verify(ctx, statement, proof):
     B = proof["T"].shape[0]
     ok = _flags(ctx, B)
     stt, pr = _struct(N_.HegStatement, statement), _struct(N_.HegProof, proof)
-    N_.check(N_.lib.mpe_heg_verify(ctx.h, B, C.byref(stt), C.byref(pr), _ptr(ok), ctx.stream()), "mpe_heg_verify")
+    N_.call.mpe_heg_verify(ctx.h, B, C.byref(stt), C.byref(pr), _ptr(ok), ctx.stream())
     return ok
 
 
 def hash_commit_point(ctx, d_P, d_blind):
     out = _new(ctx, d_P.shape[0], 8)
-    N_.check(N_.lib.mpe_hash_commit_point(ctx.h, d_P.shape[0], _ptr(d_P), _ptr(d_blind), _ptr(out), ctx.stream()), "mpe_hash_commit_point")
+    N_.call.mpe_hash_commit_point(ctx.h, d_P.shape[0], _ptr(d_P), _ptr(d_blind), _ptr(out), ctx.stream())
     return out
 
 
@@ -1680,9 +1545,8 @@ def bob_generate(ctx, pk, stm, d_a_enc, d_mta_enc, d_b, d_beta_prim, d_r, nonces
     out = {f: _new(ctx, B, w) for f, w in BOB_PROOF_WORDS.items()}
     u = _new(ctx, B, 16) if check else None
     nn, pr = _struct(N_.BobNonces, nonces), _struct(N_.BobProof, out)
-    N_.check(N_.lib.mpe_bob_generate(ctx.h, pk.h, stm.h, B, _ptr(d_key_idx), _ptr(d_st_idx), _ptr(d_a_enc), _ptr(d_mta_enc),
-                                     _ptr(d_b), _ptr(d_beta_prim), _ptr(d_r), C.byref(nn), int(bool(check)), C.byref(pr),
-                                     _ptr(u), ctx.stream()), "mpe_bob_generate")
+    N_.call.mpe_bob_generate(ctx.h, pk.h, stm.h, B, _ptr(d_key_idx), _ptr(d_st_idx), _ptr(d_a_enc), _ptr(d_mta_enc), _ptr(d_b), _ptr(d_beta_prim), _ptr(d_r),
+                             C.byref(nn), int(bool(check)), C.byref(pr), _ptr(u), ctx.stream())
     return out, u
 
 
@@ -1691,8 +1555,8 @@ def bob_verify(ctx, pk, stm, d_a_enc, d_mta_enc, proof, d_X=None, d_u=None, d_ke
     B = d_a_enc.shape[0]
     ok = _flags(ctx, B)
     pr = _struct(N_.BobProof, proof)
-    N_.check(N_.lib.mpe_bob_verify(ctx.h, pk.h, stm.h, B, _ptr(d_key_idx), _ptr(d_st_idx), _ptr(d_a_enc), _ptr(d_mta_enc),
-                                   C.byref(pr), _ptr(d_X), _ptr(d_u), _ptr(ok), ctx.stream()), "mpe_bob_verify")
+    N_.call.mpe_bob_verify(ctx.h, pk.h, stm.h, B, _ptr(d_key_idx), _ptr(d_st_idx), _ptr(d_a_enc), _ptr(d_mta_enc), C.byref(pr), _ptr(d_X), _ptr(d_u), _ptr(ok),
+                           ctx.stream())
     return ok
 
 
@@ -1705,8 +1569,7 @@ def mta_message_a(ctx, pk, stm, d_a, d_r, nonces, d_key_idx=None):
     c = _new(ctx, B, 128)
     proofs = {f: _new(ctx, total, w) for f, w in ALICE_PROOF_WORDS.items()}
     nn, pr = _struct(N_.AliceNonces, nonces), _struct(N_.AliceProof, proofs)
-    N_.check(N_.lib.mpe_mta_message_a(ctx.h, pk.h, stm.h, B, _ptr(d_key_idx), _ptr(d_a), _ptr(d_r), C.byref(nn), _ptr(c),
-                                      C.byref(pr), ctx.stream()), "mpe_mta_message_a")
+    N_.call.mpe_mta_message_a(ctx.h, pk.h, stm.h, B, _ptr(d_key_idx), _ptr(d_a), _ptr(d_r), C.byref(nn), _ptr(c), C.byref(pr), ctx.stream())
     return c, proofs
 
 
@@ -1718,9 +1581,8 @@ def mta_message_b(ctx, pk, stm, d_b, d_ca, range_proofs, d_r, d_beta_tag, d_nonc
                beta_tag_proof=dict(pk=_new(ctx, B, 16), R=_new(ctx, B, 16), z=_new(ctx, B, 8)))
     rp = _struct(N_.AliceProof, range_proofs)
     p1, p2 = _struct(N_.DlogProof, out["b_proof"]), _struct(N_.DlogProof, out["beta_tag_proof"])
-    N_.check(N_.lib.mpe_mta_message_b(ctx.h, pk.h, stm.h, B, _ptr(d_key_idx), _ptr(d_b), _ptr(d_ca), C.byref(rp), _ptr(d_r),
-                                      _ptr(d_beta_tag), _ptr(d_nonce_b), _ptr(d_nonce_bt), _ptr(out["c"]), _ptr(out["beta"]),
-                                      C.byref(p1), C.byref(p2), _ptr(out["ok"]), ctx.stream()), "mpe_mta_message_b")
+    N_.call.mpe_mta_message_b(ctx.h, pk.h, stm.h, B, _ptr(d_key_idx), _ptr(d_b), _ptr(d_ca), C.byref(rp), _ptr(d_r), _ptr(d_beta_tag), _ptr(d_nonce_b),
+                              _ptr(d_nonce_bt), _ptr(out["c"]), _ptr(out["beta"]), C.byref(p1), C.byref(p2), _ptr(out["ok"]), ctx.stream())
     return out
 
 
@@ -1729,8 +1591,8 @@ def mta_verify_get_alpha(ctx, sk, d_cb, b_proof, beta_tag_proof, d_a, d_key_idx=
     B = d_cb.shape[0]
     alpha, share, ok = _new(ctx, B, 8), _new(ctx, B, 64), _flags(ctx, B)
     p1, p2 = _struct(N_.DlogProof, b_proof), _struct(N_.DlogProof, beta_tag_proof)
-    N_.check(N_.lib.mpe_mta_verify_get_alpha(ctx.h, sk.h, B, _ptr(d_key_idx), _ptr(d_cb), C.byref(p1), C.byref(p2), _ptr(d_a),
-                                             _ptr(alpha), _ptr(share), _ptr(ok), ctx.stream()), "mpe_mta_verify_get_alpha")
+    N_.call.mpe_mta_verify_get_alpha(ctx.h, sk.h, B, _ptr(d_key_idx), _ptr(d_cb), C.byref(p1), C.byref(p2), _ptr(d_a), _ptr(alpha), _ptr(share), _ptr(ok),
+                                     ctx.stream())
     return alpha, share, ok
 
 
@@ -1739,8 +1601,8 @@ def lindell_partial_sig(ctx, pk, d_c_key, d_x2, d_k2, d_R1, d_msg, d_rho, d_r, d
     """`PartialSig::compute` batched: returns c3 [B,128] (device)."""
     B = d_c_key.shape[0]
     c3 = _new(ctx, B, 128)
-    N_.check(N_.lib.mpe_lindell_partial_sig(ctx.h, pk.h, B, _ptr(d_key_idx), _ptr(d_c_key), _ptr(d_x2), _ptr(d_k2), _ptr(d_R1),
-                                            _ptr(d_msg), _ptr(d_rho), _ptr(d_r), _ptr(c3), ctx.stream()), "mpe_lindell_partial_sig")
+    N_.call.mpe_lindell_partial_sig(ctx.h, pk.h, B, _ptr(d_key_idx), _ptr(d_c_key), _ptr(d_x2), _ptr(d_k2), _ptr(d_R1), _ptr(d_msg), _ptr(d_rho), _ptr(d_r),
+                                    _ptr(c3), ctx.stream())
     return c3
 
 
@@ -1748,7 +1610,7 @@ def paillier_open(ctx, sk, d_c, d_key_idx=None):
     """kzen-paillier `Open::open`: returns (m [B,64], r [B,64]) with c = (1 + m N) r^N mod N^2."""
     B = d_c.shape[0]
     m, r = _new(ctx, B, 64), _new(ctx, B, 64)
-    N_.check(N_.lib.mpe_paillier_open(ctx.h, sk.h, B, _ptr(d_key_idx), _ptr(d_c), _ptr(m), _ptr(r), ctx.stream()), "mpe_paillier_open")
+    N_.call.mpe_paillier_open(ctx.h, sk.h, B, _ptr(d_key_idx), _ptr(d_c), _ptr(m), _ptr(r), ctx.stream())
     return m, r
 
 
@@ -1758,8 +1620,8 @@ def lindell_pdl_proof(ctx, sk, stm, d_c_key, d_x1, d_r, nonces, d_key_idx=None, 
     out = {f: _new(ctx, B, w) for f, w in PDL_PROOF_WORDS.items()}
     Q = _new(ctx, B, 16)
     nn, pr = _struct(N_.PdlNonces, nonces), _struct(N_.PdlProof, out)
-    N_.check(N_.lib.mpe_lindell_pdl_proof(ctx.h, sk.h, stm.h, B, _ptr(d_key_idx), _ptr(d_st_idx), _ptr(d_c_key), _ptr(d_x1), _ptr(d_r),
-                                          C.byref(nn), _ptr(Q), C.byref(pr), ctx.stream()), "mpe_lindell_pdl_proof")
+    N_.call.mpe_lindell_pdl_proof(ctx.h, sk.h, stm.h, B, _ptr(d_key_idx), _ptr(d_st_idx), _ptr(d_c_key), _ptr(d_x1), _ptr(d_r), C.byref(nn), _ptr(Q),
+                                  C.byref(pr), ctx.stream())
     return Q, out
 
 
@@ -1768,19 +1630,16 @@ def lindell_pdl_verify(ctx, pk, d_Nt, d_h1, d_h2, d_dlog_x, d_dlog_y, d_stmt_N, 
     B = d_stmt_c.shape[0]
     ok = _flags(ctx, B)
     pr = _struct(N_.PdlProof, proof)
-    N_.check(N_.lib.mpe_lindell_pdl_verify(ctx.h, pk.h, B, _ptr(d_key_idx), _ptr(d_Nt), _ptr(d_h1), _ptr(d_h2), _ptr(d_dlog_x), _ptr(d_dlog_y),
-                                           _ptr(d_stmt_N), _ptr(d_stmt_c), _ptr(d_stmt_Q), _ptr(d_c_key), _ptr(d_q1), C.byref(pr), _ptr(ok),
-                                           ctx.stream()), "mpe_lindell_pdl_verify")
+    N_.call.mpe_lindell_pdl_verify(ctx.h, pk.h, B, _ptr(d_key_idx), _ptr(d_Nt), _ptr(d_h1), _ptr(d_h2), _ptr(d_dlog_x), _ptr(d_dlog_y), _ptr(d_stmt_N),
+                                   _ptr(d_stmt_c), _ptr(d_stmt_Q), _ptr(d_c_key), _ptr(d_q1), C.byref(pr), _ptr(ok), ctx.stream())
     return ok
 
 
 def lindell_sign(ctx, sk, d_c3, d_k1, d_R2, d_key_idx=None):
     """`Signature::compute_with_recid` batched: returns (r [B,8], s [B,8], recid [B]) on the device."""
     B = d_c3.shape[0]
-    r, s = _new(ctx, B, 8), _new(ctx, B, 8)
-    recid = torch.empty((B,), dtype=torch.int32, device=ctx.device)
-    N_.check(N_.lib.mpe_lindell_sign(ctx.h, sk.h, B, _ptr(d_key_idx), _ptr(d_c3), _ptr(d_k1), _ptr(d_R2), _ptr(r), _ptr(s),
-                                     _ptr(recid), ctx.stream()), "mpe_lindell_sign")
+    r, s, recid = _new(ctx, B, 8), _new(ctx, B, 8), _new(ctx, B)
+    N_.call.mpe_lindell_sign(ctx.h, sk.h, B, _ptr(d_key_idx), _ptr(d_c3), _ptr(d_k1), _ptr(d_R2), _ptr(r), _ptr(s), _ptr(recid), ctx.stream())
     return r, s, recid
 
 
@@ -1788,7 +1647,7 @@ def lindell_sign(ctx, sk, d_c3, d_k1, d_R2, d_key_idx=None):
 def hash_commit_bigint(ctx, d_m, d_blind):
     """HashCommitment over a 256-bit BigInt m [B,8] (minimal bytes, as the blind factor): com [B,8]"""
     out = _new(ctx, d_m.shape[0], 8)
-    N_.check(N_.lib.mpe_hash_commit_bigint(ctx.h, d_m.shape[0], _ptr(d_m), _ptr(d_blind), _ptr(out), ctx.stream()), "mpe_hash_commit_bigint")
+    N_.call.mpe_hash_commit_bigint(ctx.h, d_m.shape[0], _ptr(d_m), _ptr(d_blind), _ptr(out), ctx.stream())
     return out
 
 
@@ -1796,16 +1655,16 @@ def lindell_keygen_first_msg(ctx, d_x1, d_nonce, d_blind_pk, d_blind_pok):
     """party one's `KeyGenFirstMsg::create_commitments_with_fixed_secret_share` (party_one.rs:179-219): dict Q1, R, z, pk_com, pok_com"""
     B = d_x1.shape[0]
     o = dict(Q1=_new(ctx, B, 16), R=_new(ctx, B, 16), z=_new(ctx, B, 8), pk_com=_new(ctx, B, 8), pok_com=_new(ctx, B, 8))
-    N_.check(N_.lib.mpe_lindell_keygen_first_msg(ctx.h, B, _ptr(d_x1), _ptr(d_nonce), _ptr(d_blind_pk), _ptr(d_blind_pok), _ptr(o["Q1"]), _ptr(o["R"]),
-                                                 _ptr(o["z"]), _ptr(o["pk_com"]), _ptr(o["pok_com"]), ctx.stream()), "mpe_lindell_keygen_first_msg")
+    N_.call.mpe_lindell_keygen_first_msg(ctx.h, B, _ptr(d_x1), _ptr(d_nonce), _ptr(d_blind_pk), _ptr(d_blind_pok), _ptr(o["Q1"]), _ptr(o["R"]), _ptr(o["z"]),
+                                         _ptr(o["pk_com"]), _ptr(o["pok_com"]), ctx.stream())
     return o
 
 
 def lindell_keygen_verify_first_msg(ctx, d_pk_com, d_pok_com, d_blind_pk, d_blind_pok, d_Q1, d_R, d_z):
     """party two's `KeyGenSecondMsg::verify_commitments_and_dlog_proof` (party_two.rs:180-223): ok [B]"""
     ok = _flags(ctx, d_Q1.shape[0])
-    N_.check(N_.lib.mpe_lindell_keygen_verify_first_msg(ctx.h, d_Q1.shape[0], _ptr(d_pk_com), _ptr(d_pok_com), _ptr(d_blind_pk), _ptr(d_blind_pok),
-                                                        _ptr(d_Q1), _ptr(d_R), _ptr(d_z), _ptr(ok), ctx.stream()), "mpe_lindell_keygen_verify_first_msg")
+    N_.call.mpe_lindell_keygen_verify_first_msg(ctx.h, d_Q1.shape[0], _ptr(d_pk_com), _ptr(d_pok_com), _ptr(d_blind_pk), _ptr(d_blind_pok), _ptr(d_Q1),
+                                                _ptr(d_R), _ptr(d_z), _ptr(ok), ctx.stream())
     return ok
 
 
@@ -1814,32 +1673,30 @@ def lindell_eph_first_msg(ctx, d_k2, d_nonce, d_blind_pk, d_blind_pok):
     B = d_k2.shape[0]
     o = dict(pub=_new(ctx, B, 16), c=_new(ctx, B, 16), a1=_new(ctx, B, 16), a2=_new(ctx, B, 16), z=_new(ctx, B, 8), pk_com=_new(ctx, B, 8),
              pok_com=_new(ctx, B, 8))
-    N_.check(N_.lib.mpe_lindell_eph_first_msg(ctx.h, B, _ptr(d_k2), _ptr(d_nonce), _ptr(d_blind_pk), _ptr(d_blind_pok), _ptr(o["pub"]), _ptr(o["c"]),
-                                              _ptr(o["a1"]), _ptr(o["a2"]), _ptr(o["z"]), _ptr(o["pk_com"]), _ptr(o["pok_com"]), ctx.stream()),
-             "mpe_lindell_eph_first_msg")
+    N_.call.mpe_lindell_eph_first_msg(ctx.h, B, _ptr(d_k2), _ptr(d_nonce), _ptr(d_blind_pk), _ptr(d_blind_pok), _ptr(o["pub"]), _ptr(o["c"]), _ptr(o["a1"]),
+                                      _ptr(o["a2"]), _ptr(o["z"]), _ptr(o["pk_com"]), _ptr(o["pok_com"]), ctx.stream())
     return o
 
 
 def lindell_eph_verify_first_msg(ctx, d_pk_com, d_pok_com, d_blind_pk, d_blind_pok, d_pub, d_c, d_a1, d_a2, d_z):
     """party one's `EphKeyGenSecondMsg::verify_commitments_and_dlog_proof` (party_one.rs:437-483): ok [B]"""
     ok = _flags(ctx, d_pub.shape[0])
-    N_.check(N_.lib.mpe_lindell_eph_verify_first_msg(ctx.h, d_pub.shape[0], _ptr(d_pk_com), _ptr(d_pok_com), _ptr(d_blind_pk), _ptr(d_blind_pok),
-                                                     _ptr(d_pub), _ptr(d_c), _ptr(d_a1), _ptr(d_a2), _ptr(d_z), _ptr(ok), ctx.stream()),
-             "mpe_lindell_eph_verify_first_msg")
+    N_.call.mpe_lindell_eph_verify_first_msg(ctx.h, d_pub.shape[0], _ptr(d_pk_com), _ptr(d_pok_com), _ptr(d_blind_pk), _ptr(d_blind_pok), _ptr(d_pub),
+                                             _ptr(d_c), _ptr(d_a1), _ptr(d_a2), _ptr(d_z), _ptr(ok), ctx.stream())
     return ok
 
 
 def ecdsa_verify(ctx, d_pub, d_msg, d_r, d_s):
     """`party_one::verify` (party_one.rs:567-592) batched: ok [B]; high s and s >= q are refused, r is compared with P.x as integers"""
     ok = _flags(ctx, d_pub.shape[0])
-    N_.check(N_.lib.mpe_ecdsa_verify(ctx.h, d_pub.shape[0], _ptr(d_pub), _ptr(d_msg), _ptr(d_r), _ptr(d_s), _ptr(ok), ctx.stream()), "mpe_ecdsa_verify")
+    N_.call.mpe_ecdsa_verify(ctx.h, d_pub.shape[0], _ptr(d_pub), _ptr(d_msg), _ptr(d_r), _ptr(d_s), _ptr(ok), ctx.stream())
     return ok
 
 
 def scalar_mul(ctx, d_a, d_b):
     """a b mod q per row [B,8]"""
     out = _new(ctx, d_a.shape[0], 8)
-    N_.check(N_.lib.mpe_scalar_mul(ctx.h, d_a.shape[0], _ptr(d_a), _ptr(d_b), _ptr(out), ctx.stream()), "mpe_scalar_mul")
+    N_.call.mpe_scalar_mul(ctx.h, d_a.shape[0], _ptr(d_a), _ptr(d_b), _ptr(out), ctx.stream())
     return out
 
 
@@ -1848,8 +1705,8 @@ def lindell_ntilde_generate(ctx, count, seed, counter, max_attempts=0):
     o = {f: _new(ctx, count, 64) for f in ("Nt", "h1", "h2")}
     o["xhi"] = _new(ctx, count, 8)
     fail = torch.zeros((1,), dtype=torch.int32, device=ctx.device)
-    N_.check(N_.lib.mpe_lindell_ntilde_generate(ctx.h, count, _seed(seed), int(counter), max_attempts, _ptr(o["Nt"]), _ptr(o["h1"]), _ptr(o["h2"]),
-                                                _ptr(o["xhi"]), _ptr(fail), ctx.stream()), "mpe_lindell_ntilde_generate")
+    N_.call.mpe_lindell_ntilde_generate(ctx.h, count, _seed(seed), int(counter), max_attempts, _ptr(o["Nt"]), _ptr(o["h1"]), _ptr(o["h2"]), _ptr(o["xhi"]),
+                                        _ptr(fail), ctx.stream())
     o["fail"] = fail
     return o
 
@@ -2017,10 +1874,10 @@ def gg18_sign_keys(ctx, t, n, signers, local, d_x_i, d_pk_vec, d_k_i, d_gamma_i)
     """`SignKeys::create`: x_i, k_i, gamma_i [L,B,8], pk_vec [B,n,16] -> dict w_i [L,B,8], g_w_i, g_gamma_i [L,B,16], g_w [S,B,16], status [L,B]"""
     L, B = d_k_i.shape[0], d_k_i.shape[1]
     S = len(signers)
-    o = dict(w_i=_new(ctx, L * B, 8).reshape(L, B, 8), g_w_i=_new(ctx, L * B, 16).reshape(L, B, 16), g_gamma_i=_new(ctx, L * B, 16).reshape(L, B, 16),
-             g_w=_new(ctx, S * B, 16).reshape(S, B, 16), status=torch.zeros((L, B), dtype=torch.int32, device=ctx.device))
-    N_.check(N_.lib.mpe_gg18_sign_keys(ctx.h, t, n, *_g18_dims(signers, local), B, _ptr(d_x_i), _ptr(d_pk_vec), _ptr(d_k_i), _ptr(d_gamma_i), _ptr(o["w_i"]),
-                                       _ptr(o["g_w_i"]), _ptr(o["g_gamma_i"]), _ptr(o["g_w"]), _ptr(o["status"]), ctx.stream()), "mpe_gg18_sign_keys")
+    o = dict(w_i=_new(ctx, L, B, 8), g_w_i=_new(ctx, L, B, 16), g_gamma_i=_new(ctx, L, B, 16),
+             g_w=_new(ctx, S, B, 16), status=torch.zeros((L, B), dtype=torch.int32, device=ctx.device))
+    N_.call.mpe_gg18_sign_keys(ctx.h, t, n, *_g18_dims(signers, local), B, _ptr(d_x_i), _ptr(d_pk_vec), _ptr(d_k_i), _ptr(d_gamma_i), _ptr(o["w_i"]),
+                               _ptr(o["g_w_i"]), _ptr(o["g_gamma_i"]), _ptr(o["g_w"]), _ptr(o["status"]), ctx.stream())
     return o
 
 
@@ -2030,40 +1887,39 @@ def gg18_message_b(ctx, pk, d_b, d_ca, d_r, d_beta_tag, d_nonce_b, d_nonce_bt, d
     out = dict(c=_new(ctx, B, 128), beta=_new(ctx, B, 8), b_proof=dict(pk=_new(ctx, B, 16), R=_new(ctx, B, 16), z=_new(ctx, B, 8)),
                beta_tag_proof=dict(pk=_new(ctx, B, 16), R=_new(ctx, B, 16), z=_new(ctx, B, 8)))
     p1, p2 = _struct(N_.DlogProof, out["b_proof"]), _struct(N_.DlogProof, out["beta_tag_proof"])
-    N_.check(N_.lib.mpe_gg18_message_b(ctx.h, pk.h, B, _ptr(d_key_idx), _ptr(d_b), _ptr(d_ca), _ptr(d_r), _ptr(d_beta_tag), _ptr(d_nonce_b), _ptr(d_nonce_bt),
-                                       _ptr(out["c"]), _ptr(out["beta"]), C.byref(p1), C.byref(p2), ctx.stream()), "mpe_gg18_message_b")
+    N_.call.mpe_gg18_message_b(ctx.h, pk.h, B, _ptr(d_key_idx), _ptr(d_b), _ptr(d_ca), _ptr(d_r), _ptr(d_beta_tag), _ptr(d_nonce_b), _ptr(d_nonce_bt),
+                               _ptr(out["c"]), _ptr(out["beta"]), C.byref(p1), C.byref(p2), ctx.stream())
     return out
 
 
 def gg18_phase2(ctx, signers, local, d_k_i, d_gamma_i, d_w_i, d_alpha, d_beta, d_miu, d_ni, d_ok_gamma, d_ok_w, d_w_pk, d_g_w, d_status):
     """the alpha verdicts (201 / 202), `phase2_delta_i`, `phase2_sigma_i`: per-peer inputs [L,S-1,B,..] -> (delta_i, sigma_i) [L,B,8]"""
     L, B = d_k_i.shape[0], d_k_i.shape[1]
-    delta, sigma = _new(ctx, L * B, 8).reshape(L, B, 8), _new(ctx, L * B, 8).reshape(L, B, 8)
-    N_.check(N_.lib.mpe_gg18_phase2(ctx.h, *_g18_dims(signers, local), B, _ptr(d_k_i), _ptr(d_gamma_i), _ptr(d_w_i), _ptr(d_alpha), _ptr(d_beta), _ptr(d_miu),
-                                    _ptr(d_ni), _ptr(d_ok_gamma), _ptr(d_ok_w), _ptr(d_w_pk), _ptr(d_g_w), _ptr(delta), _ptr(sigma), _ptr(d_status),
-                                    ctx.stream()), "mpe_gg18_phase2")
+    delta, sigma = _new(ctx, L, B, 8), _new(ctx, L, B, 8)
+    N_.call.mpe_gg18_phase2(ctx.h, *_g18_dims(signers, local), B, _ptr(d_k_i), _ptr(d_gamma_i), _ptr(d_w_i), _ptr(d_alpha), _ptr(d_beta), _ptr(d_miu),
+                            _ptr(d_ni), _ptr(d_ok_gamma), _ptr(d_ok_w), _ptr(d_w_pk), _ptr(d_g_w), _ptr(delta), _ptr(sigma), _ptr(d_status), ctx.stream())
     return delta, sigma
 
 
 def gg18_phase4(ctx, signers, local, d_delta, d_b_pk, d_g_gamma, d_blind, d_com, d_status):
     """`phase3_reconstruct_delta` + `phase4` + the own g_gamma_i: broadcast [S,B,..], b_pk [L,S-1,B,16] -> R [L,B,16]"""
     L, B = d_status.shape
-    R = _new(ctx, L * B, 16).reshape(L, B, 16)
-    N_.check(N_.lib.mpe_gg18_phase4(ctx.h, *_g18_dims(signers, local), B, _ptr(d_delta), _ptr(d_b_pk), _ptr(d_g_gamma), _ptr(d_blind), _ptr(d_com), _ptr(R),
-                                    _ptr(d_status), ctx.stream()), "mpe_gg18_phase4")
+    R = _new(ctx, L, B, 16)
+    N_.call.mpe_gg18_phase4(ctx.h, *_g18_dims(signers, local), B, _ptr(d_delta), _ptr(d_b_pk), _ptr(d_g_gamma), _ptr(d_blind), _ptr(d_com), _ptr(R),
+                            _ptr(d_status), ctx.stream())
     return R
 
 
 def gg18_phase5a(ctx, signers, local, d_k_i, d_sigma_i, d_msg, d_R, d_l_i, d_rho_i, d_blind, d_s1, d_s2, d_nonce, d_status):
     """`phase5_local_sig` + `phase5a_broadcast_5b_zkproof`: dict s_i, V, A, B, com, heg{T, A3, z1, z2}, dlog{pk, R, z}, all [L,B,..]"""
     L, B = d_status.shape
-    new = lambda w: _new(ctx, L * B, w).reshape(L, B, w)
+    new = lambda w: _new(ctx, L, B, w)
     o = dict(s_i=new(8), V=new(16), A=new(16), B=new(16), com=new(8), heg=dict(T=new(16), A3=new(16), z1=new(8), z2=new(8)),
              dlog=dict(pk=new(16), R=new(16), z=new(8)))
     hp, dp = _struct(N_.HegProof, o["heg"]), _struct(N_.DlogProof, o["dlog"])
-    N_.check(N_.lib.mpe_gg18_phase5a(ctx.h, *_g18_dims(signers, local), B, _ptr(d_k_i), _ptr(d_sigma_i), _ptr(d_msg), _ptr(d_R), _ptr(d_l_i), _ptr(d_rho_i),
-                                     _ptr(d_blind), _ptr(d_s1), _ptr(d_s2), _ptr(d_nonce), _ptr(o["s_i"]), _ptr(o["V"]), _ptr(o["A"]), _ptr(o["B"]),
-                                     _ptr(o["com"]), C.byref(hp), C.byref(dp), _ptr(d_status), ctx.stream()), "mpe_gg18_phase5a")
+    N_.call.mpe_gg18_phase5a(ctx.h, *_g18_dims(signers, local), B, _ptr(d_k_i), _ptr(d_sigma_i), _ptr(d_msg), _ptr(d_R), _ptr(d_l_i), _ptr(d_rho_i),
+                             _ptr(d_blind), _ptr(d_s1), _ptr(d_s2), _ptr(d_nonce), _ptr(o["s_i"]), _ptr(o["V"]), _ptr(o["A"]), _ptr(o["B"]), _ptr(o["com"]),
+                             C.byref(hp), C.byref(dp), _ptr(d_status), ctx.stream())
     return o
 
 
@@ -2073,34 +1929,34 @@ GG18_PHASE5B_FIELDS = ("V", "A", "B", "blind", "com", "T", "A3", "z1", "z2", "dl
 def gg18_phase5c(ctx, signers, local, d_msg, d_y, d_R, d_l_i, d_rho_i, d_blind2, bc, d_status):
     """`phase5c`: bc = dict GG18_PHASE5B_FIELDS of broadcast arrays [S,B,..] -> (u, t [L,B,16], com2 [L,B,8])"""
     L, B = d_status.shape
-    u, t, com2 = _new(ctx, L * B, 16).reshape(L, B, 16), _new(ctx, L * B, 16).reshape(L, B, 16), _new(ctx, L * B, 8).reshape(L, B, 8)
+    u, t, com2 = _new(ctx, L, B, 16), _new(ctx, L, B, 16), _new(ctx, L, B, 8)
     st = _struct(N_.Gg18Phase5bMsgs, bc)
-    N_.check(N_.lib.mpe_gg18_phase5c(ctx.h, *_g18_dims(signers, local), B, _ptr(d_msg), _ptr(d_y), _ptr(d_R), _ptr(d_l_i), _ptr(d_rho_i), _ptr(d_blind2),
-                                     C.byref(st), _ptr(u), _ptr(t), _ptr(com2), _ptr(d_status), ctx.stream()), "mpe_gg18_phase5c")
+    N_.call.mpe_gg18_phase5c(ctx.h, *_g18_dims(signers, local), B, _ptr(d_msg), _ptr(d_y), _ptr(d_R), _ptr(d_l_i), _ptr(d_rho_i), _ptr(d_blind2), C.byref(st),
+                             _ptr(u), _ptr(t), _ptr(com2), _ptr(d_status), ctx.stream())
     return u, t, com2
 
 
 def gg18_phase5d(ctx, signers, local, d_u, d_t, d_blind2, d_com2, d_B, d_status):
     """`phase5d` over the broadcast arrays [S,B,..]: writes 541 / 542 into d_status"""
     B = d_status.shape[1]
-    N_.check(N_.lib.mpe_gg18_phase5d(ctx.h, *_g18_dims(signers, local), B, _ptr(d_u), _ptr(d_t), _ptr(d_blind2), _ptr(d_com2), _ptr(d_B), _ptr(d_status),
-                                     ctx.stream()), "mpe_gg18_phase5d")
+    N_.call.mpe_gg18_phase5d(ctx.h, *_g18_dims(signers, local), B, _ptr(d_u), _ptr(d_t), _ptr(d_blind2), _ptr(d_com2), _ptr(d_B), _ptr(d_status), ctx.stream())
 
 
 def gg18_output_signature(ctx, signers, local, d_s_own, d_s_all, d_R, d_msg, d_y, d_status):
     """`output_signature`: s_own, R [L,B,..], s_all [S,B,8] -> (r, s [L,B,8], recid [L,B]); zero unless the status is 0"""
     L, B = d_status.shape
-    r, s = _new(ctx, L * B, 8).reshape(L, B, 8), _new(ctx, L * B, 8).reshape(L, B, 8)
+    r, s = _new(ctx, L, B, 8), _new(ctx, L, B, 8)
     recid = torch.zeros((L, B), dtype=torch.int32, device=ctx.device)
-    N_.check(N_.lib.mpe_gg18_output_signature(ctx.h, *_g18_dims(signers, local), B, _ptr(d_s_own), _ptr(d_s_all), _ptr(d_R), _ptr(d_msg), _ptr(d_y), _ptr(r),
-                                              _ptr(s), _ptr(recid), _ptr(d_status), ctx.stream()), "mpe_gg18_output_signature")
+    N_.call.mpe_gg18_output_signature(ctx.h, *_g18_dims(signers, local), B, _ptr(d_s_own), _ptr(d_s_all), _ptr(d_R), _ptr(d_msg), _ptr(d_y), _ptr(r), _ptr(s),
+                                      _ptr(recid), _ptr(d_status), ctx.stream())
     return r, s, recid
 
 
-class Gg18Wallet:
+class Gg18Wallet(_Handle):
     """What GG18 signing reads of a `LocalKey`, resident in HBM, in the shape Gg20Keys takes it: arrays = dict of numpy uint32 arrays over
     ALL n parties: x [n,8], p, q [n,32], X [n,16] (pk_vec), y [1,16], optionally N [n,64] (else p q).  own: the party indices whose
     secrets (x, p, q) this object gets (default all); the other parties' rows of x, p, q never leave the host."""
+    pk = sk = None
 
     def __init__(self, ctx, t, n, arrays, own=None):
         self.ctx, self.t, self.n = ctx, t, n
@@ -2115,15 +1971,10 @@ class Gg18Wallet:
         self.pk = PaillierKeys(ctx, N=words_to_ints(Nw[:n]))                        # every party's public key
         self.sk = PaillierKeys(ctx, p=up(a["p"][self.own]), q=up(a["q"][self.own]))  # the own ones, in the order of `own`
 
-    def close(self):
-        self.pk.close()
-        self.sk.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def close(self):                          # no handle of its own: the two key sets
+        for keys in (self.pk, self.sk):
+            if keys is not None:
+                keys.close()
 
 
 # stream fields of gg18_sign (field f draws stream counter | f << 56; 0..21 are mpe_gg20_sample_nonces', 0..15 the keygen chains',

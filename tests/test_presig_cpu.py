@@ -38,7 +38,7 @@ def test_header_declares_every_call_the_harness_binds_and_states_the_codes_once(
     assert declared == {"mpe_gg20_presig_" + c for c in CALLS}
     assert declared <= set(native.EXPORTED)
     engine = open(os.path.join(ROOT, "multi_party_ecdsa_amd", "engine.py")).read()
-    assert set(re.findall(r"lib\.(mpe_gg20_presig_\w+)\(", engine)) == declared              # the harness binds them all
+    assert set(re.findall(r"(?:lib|call)\.(mpe_gg20_presig_\w+)\(", engine)) == declared     # the harness binds them all
     defines = dict(re.findall(r"#define MPE_GG20_PRESIG_(\w+) (\d+)", hdr))
     want = dict(RECORD_VERSION=PP.RECORD_VERSION, DEPOSIT_RANGE=PP.DEPOSIT_RANGE, DEPOSIT_NOT_EMPTY=PP.DEPOSIT_NOT_EMPTY,
                 SESSION_FAILED=PP.SESSION_FAILED, SIGN_RANGE=PP.SIGN_RANGE, SIGN_NOT_READY=PP.SIGN_NOT_READY,

@@ -34,10 +34,11 @@ def preprocess():
 
 
 def constants():
-    out = []
-    for m in re.finditer(r"^#define\s+(MPE_\w+)\s+\(?(-?\d+)\)?", open(HEADER).read(), re.M):
-        out.append((m.group(1), int(m.group(2))))
-    return out
+    """`#define MPE_X 12`, `(-1)`, and the typed form `((int)841)` / `((uint32_t)0x3153504du)`: a cast of one integer literal"""
+    lit = r"(-?(?:0[xX][0-9a-fA-F]+|\d+))[uUlL]*"
+    rule = rf"^#define\s+(MPE_\w+)\s+(?:\(?{lit}\)?|\(\(\w+\)\s*{lit}\))\s*(?:/\*.*)?$"
+    found = [(m.group(1), m.group(2) or m.group(3)) for m in re.finditer(rule, open(HEADER).read(), re.M)]
+    return [(name, int(v, 16 if "x" in v.lower() else 10)) for name, v in found]
 
 
 def split_decls(src):
