@@ -23,6 +23,7 @@
 
 #include "mpe_gg20_msg.h"
 #include "mpe_gg20_nonces.h"
+#include "mpe_gg20_pv.h"
 #include "mpe_proofs.h"
 
 namespace mpe {
@@ -93,7 +94,7 @@ struct Dim {
   const uint32_t* ty;    // [B][16]    y + t_b G (zero: t_b is not canonical, or the child key is the point at infinity)
   const uint32_t* tgw;   // [B][S][16] g_w of the session's set + (lambda_j t_b) G
 };
-__device__ __forceinline__ int ind_of(int i, int jj) { return jj < i ? jj : jj + 1; }
+// (ind_of, rank_in: mpe_gg20_pv.h)
 __device__ __forceinline__ int jme_of(int i, int ind) { return i < ind ? i : i - 1; }
 __device__ __forceinline__ int ks_of(const Dim& d, int b) { return d.ks ? d.ks[b] : 0; }
 // the signer set of session b: its index (an index outside the table reads as set 0 — r0_kernel stops such a session with
@@ -102,11 +103,6 @@ __device__ __forceinline__ bool ss_valid(const Dim& d, int b) { return !d.ss || 
 __device__ __forceinline__ int ss_of(const Dim& d, int b) { return d.ss && ss_valid(d, b) ? d.ss[b] : 0; }
 __device__ __forceinline__ uint32_t set4_of(const Dim& d, int b) { return d.ss ? d.sets[ss_of(d, b)] : d.sg4; }
 __device__ __forceinline__ int sg_of(const Dim& d, int b, int i) { return (int)((set4_of(d, b) >> (4 * i)) & 15u); }
-__device__ __forceinline__ int rank_in(uint32_t set4, int S, int party) {
-  int r = -1;
-  for (int i = 0; i < S; ++i) if ((int)((set4 >> (4 * i)) & 15u) == party) r = i;
-  return r;
-}
 // signer ordinal of local slot li in session b (a by-index party that is not in the session's set: ordinal 0, stopped by r0_kernel)
 __device__ __forceinline__ int loc_of(const Dim& d, int b, int li) {
   if (d.lparty < 0) return d.loc[li];
@@ -140,6 +136,11 @@ struct Idx {
   int32_t *ca_mb, *kpub_mb, *kown_mb;                // [B*L*(S-1)*2]
   int32_t *pi_pp, *kown_pp, *st_pp;                  // [B*L*(S-1)]
   int32_t *ca_pv, *pi_pv, *kpub_pv, *st_pv;          // [B*PV*S*(S-1)]   PDL verifications
+  // the verifiers' OWN proofs among them (mpe_gg20_pv.h; null with PV != L, the dedup path): their positions and own-key indices, the
+  // positions of the others, and item -> its place in the order (others, own)
+  int32_t *self_pv, *kown_pv;                        // [B*L*(S-1)]
+  int32_t *rest_pv;                                  // [B*L*(S-1)*(S-1)]
+  int32_t *pos_pv;                                   // [B*L*S*(S-1)]
 };
 __global__ void idx_kernel(Dim d, Idx x, int total) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
@@ -167,6 +168,17 @@ __global__ void idx_kernel(Dim d, Idx x, int total) {
     const int jj = g % P1, r1 = g / P1, i = r1 % S, r2 = r1 / S, vl = r2 % d.PV, b = r2 / d.PV;
     x.ca_pv[g] = i * d.B + b; x.pi_pv[g] = b * L + vl; x.kpub_pv[g] = kpub(d, b, i);
     x.st_pv[g] = ks_of(d, b) * n + sg_of(d, b, ind_of(i, jj));
+  }
+  if (x.self_pv) {                                   // PV == L
+    const int nself = d.B * L * P1, nrest = nself * P1;
+    if (g < nself) {
+      const int bv = pv_self_bv(g, S), b = bv / L, iv = loc_of(d, b, bv % L), at = pv_self_item(g, S, iv);
+      x.self_pv[g] = at; x.kown_pv[g] = kown(d, b, iv); x.pos_pv[at] = nrest + g;
+    }
+    if (g < nrest) {
+      const int bv = pv_rest_bv(g, S), at = pv_rest_item(g, S, loc_of(d, bv / L, bv % L));
+      x.rest_pv[g] = at; x.pos_pv[at] = g;
+    }
   }
 }
 
@@ -907,6 +919,11 @@ static size_t layout(mpe_gg20_session* s, char* base) {
   x.ca_mb = m.i(c.nMB); x.kpub_mb = m.i(c.nMB); x.kown_mb = m.i(c.nMB);
   x.pi_pp = m.i(c.nPP); x.kown_pp = m.i(c.nPP); x.st_pp = m.i(c.nPP);
   x.ca_pv = m.i(c.nPV); x.pi_pv = m.i(c.nPV); x.kpub_pv = m.i(c.nPV); x.st_pv = m.i(c.nPV);
+  x.self_pv = x.kown_pv = x.rest_pv = x.pos_pv = nullptr;
+  if (!s->dedup) {                                   // PV == L: every local party verifies every proof, its own included
+    const size_t nself = pv_self_count(d.B, d.L, d.S);
+    x.self_pv = m.i(nself); x.kown_pv = m.i(nself); x.rest_pv = m.i(c.nPV - nself); x.pos_pv = m.i(c.nPV);
+  }
   if (s->tweaked) { s->tw = m.w((size_t)d.B * 8); s->ty = m.w((size_t)d.B * 16); s->tgw = m.w((size_t)d.B * d.S * 16); }
   s->kq = m.w(c.nPI * 8); s->gq = m.w(c.nPI * 8); s->w = m.w(c.nPI * 8); s->k64 = m.w(c.nPI * 64);
   s->g_gamma = m.w(c.nPI * 16); s->com = m.w(c.nPI * 8); s->c_a = m.w(c.nPI * 128); s->beta = m.w(c.nMB * 8);
@@ -1341,9 +1358,14 @@ static int round5(mpe_gg20_session* s, const uint32_t* d_in, const int64_t* h_of
   Fork g(ctx, st, 2, par, 2);
   if (rc == MPE_OK && c.nPI > 0)
     hipLaunchKernelGGL(r5_prove_kernel, dim3(blocks_for((int)c.nPI, 64)), dim3(64), 0, g.s(1), d, s->R, s->sigma_i, s->lq, s->pedT, Z.heg_s1, Z.heg_s2, heg);
+  // a verifier's own proofs lie under its own Paillier key: their N^2 side goes through p^2 | q^2 (mpe_proofs.h PdlOwn), same verdict
+  PdlOwn own;
+  own.prv = K->prv; own.n_self = (int)pv_self_count(d.B, d.L, d.S);
+  own.self = s->ix.self_pv; own.rest = s->ix.rest_pv; own.pos = s->ix.pos_pv; own.key_idx = s->ix.kown_pv;
+  const bool self_crt = ctx->r5_self_crt && s->ix.self_pv != nullptr && K->prv != nullptr;
   if (rc == MPE_OK)      // phase5_verify_pdl for every prover (mine included), G = the VERIFIER's R (rounds.rs:546-558)
     rc = pdl_verify(ctx, K->pub, K->stm, (int)c.nPV, s->ix.kpub_pv, s->ix.st_pv, rows(s->ca_all, 128, s->ix.ca_pv), rows(d_in + M4R.R_dash.off, SUB4, rdash_pv),
-                    rows(s->R, 16, s->ix.pi_pv), pr, ok_pv, st);
+                    rows(s->R, 16, s->ix.pi_pv), pr, ok_pv, st, self_crt ? &own : nullptr);
   gg_trace(s->ctx, st, "pdl_verify", rc);
   g.join();
   GG_LAUNCH(r5_status_kernel, c.nPI, d, in4, ok_pv, STAT(5), BADR(5));

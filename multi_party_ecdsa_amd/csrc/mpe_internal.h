@@ -54,6 +54,7 @@ struct mpe_ctx {
   int ladder_prio = 1;            // s_setprio of the NEXT ladder launches (mpe_sched.h wave_priority): 1 = the default of ladders, 2 = the pair
                                   // engine's launches (the stretches a small batch waits for), 0 = work started ahead of its round
   int use_crt_n = 1;              // the provers' r^e mod N through p | q (mpe_paillier.h modexp_n_holder; option no_crt_n)
+  bool r5_self_crt = true;        // a verifier checks the PDL proofs made under its OWN key through p^2 | q^2 (mpe_proofs.h PdlOwn; option no_r5_self_crt)
   int no_pdl_ahead = 0;           // lock-step signing of small batches: round 4 computes the PDL proofs' beta^N itself (option)
   int no_r1_dlog_first = 0;       // with the inversion ahead: MessageB's DLog proofs behind the ladders again, not in front of the N~ side (option)
   int no_r1_inversion_ahead = 0;  // lock-step signing of small batches: round 1 inverts the ciphertexts itself, as the per-round calls do (option)

@@ -322,6 +322,7 @@ static const CtxOption kCtxOptions[] = {
     MPE_OPT_BOOL_OFF("no_ec_lane_groups", ec_lane_groups),   // one item per lane in the EC round kernels
     MPE_OPT_BOOL_OFF("no_merge_xn", merge_xn),               // round 0's x^N in separate launches
     MPE_OPT_BOOL_OFF("no_merge_r1", merge_r1),               // round 1's verification and MessageB ladders in separate launches
+    MPE_OPT_BOOL_OFF("no_r5_self_crt", r5_self_crt),         // a verifier's own PDL proofs on the public key like everybody else's
     MPE_OPT_INT("fb_window_bits", 4, 16, fb_window_bits),
     MPE_OPT_INT("window_bits", 0, 6, window_bits),           // 0 = per exponent length; 1 is refused below
     MPE_OPT_INT("wide_div", 1, 64, wide_div),

@@ -347,6 +347,35 @@ static int modexp_nn2(mpe_ctx* ctx, const mpe_paillier* pk, int B, Rows ksel, Ro
   return launch_modexp2(ctx, pk->ms_nn, B, ksel, base, exps, ew, base2, exps2, ew2, out, st);
 }
 
+// base^N * base2^exps2 mod N_k^2 for the HOLDER of key k: the counterpart of modexp_nn2 (a verifier that checks a proof made under its
+// OWN key: round 5's self-verifications, stand-alone mpe_pdl_verify with a private key object).  Per half-key, as modexp_nn does for
+// x^N:  a = base^(q mod (p-1)) mod p in half mode, then ONE two-base ladder a^p * (base2 mod p^2)^exps2 mod p^2 (the kernel absorbs the
+// 128-word second base chunk by chunk like a first one), recombined with the CRT idempotents.  The same residue as the public route for
+// every base < 2^2048 and every 4096-bit base2: x = base^q = a (mod p) also when p | base (q mod (p-1) is never 0: p - 1 is even and
+// larger than 1, q is an odd prime), x = a (mod p) gives x^p = a^p (mod p^2), and the CRT modulo p^2 | q^2 is exact for any residue.
+// The caller has checked use_crt / use_pair / use_pown and pk->has_private.  Scratch: from the context workspace.
+static int modexp_nn2_holder(mpe_ctx* ctx, const mpe_paillier* pk, int B, Rows ksel, Rows base, Rows base2, Rows exps2, int ew2,
+                             uint32_t* out, hipStream_t st) {
+  if (B == 0) return MPE_OK;
+  const int B2 = 2 * B;
+  int32_t* half_of = ws_array<int32_t>(ctx, B2);
+  uint32_t* a = ws_array<uint32_t>(ctx, (size_t)B2 * 64);
+  uint32_t* u = ws_array<uint32_t>(ctx, (size_t)B2 * 64);
+  uint32_t* y = ws_array<uint32_t>(ctx, (size_t)B2 * 128);
+  MPE_TRY(ws_ok(ctx));
+  MPE_LAUNCH_1D(crt_half_kernel, B2, st, B2, ksel, half_of);
+  const Rows hsel{nullptr, half_of, 0, 0};
+  MPE_TRY(launch_pair_modexp(ctx, pk->ps_pp, B2, hsel, Rows{base.p, base.idx, base.stride, base.words ? base.words : 64, 1},
+                             rows(pk->eq1, 32, half_of), 32, no_rows(), no_rows(), 0, a, st, 1));              // a = base^(q mod (p-1)) mod p
+  MPE_TRY(launch_pair_modexp(ctx, pk->ps_pp, B2, hsel, rows(a, 64, nullptr, 32), rows(pk->pq32, 32, half_of), 32,
+                             Rows{base2.p, base2.idx, base2.stride, base2.words ? base2.words : 128, 1},
+                             Rows{exps2.p, exps2.idx, exps2.stride, exps2.words, 1}, ew2, u, st));            // a^p base2^exps2 mod p^2
+  MPE_TRY(launch_modmul(ctx, pk->ms_nn, B2, Rows{nullptr, ksel.idx, ksel.stride, 0, 1}, rows(u, 64, nullptr, 64),
+                        rows(pk->e128, 128, half_of), y, st));
+  MPE_LAUNCH_1D(crt_add_kernel, B, st, B, ksel, pk->NN, y, out);
+  return MPE_OK;
+}
+
 // x^e mod N for the HOLDER of N = p q (the provers' s = r^e beta mod N: range_proofs.rs:84, zk_pdl_with_slack/mod.rs:113): x^e mod p and
 // x^e mod q in half mode on the 1024-bit pair engine (one pass per multiplication on half the limbs: a quarter of the multiply-adds of the
 // 2048-bit ladder, and 36 instead of 72 steps of latency per multiplication for a small batch), recombined with the CRT idempotents as in

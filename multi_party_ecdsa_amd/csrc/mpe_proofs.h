@@ -472,9 +472,38 @@ static int pdl_prove(mpe_ctx* ctx, const mpe_paillier* pk, const mpe_statements*
 // PDLwSlackProof::verify   (zk_pdl_with_slack/mod.rs:127-179).  Small batches: the EC check, the N^2 side and the N~ side
 // run on three streams once the challenge is known.
 // ---------------------------------------------------------------------------------------------
+// The verifier's OWN proofs among the items of a pdl_verify call: their ciphertext lies under a key whose p and q the verifier holds,
+// so s2^N (c^-1)^e mod N^2 goes through p^2 | q^2 (mpe_paillier.h modexp_nn2_holder): the same residue, the same verdict.
+//   n_self, self [n_self]      the positions of those items, ascending or not; self == nullptr: n_self == B, every item
+//   rest [B - n_self]          the positions of the other items (they stay on the public key)
+//   pos [B]                    item -> its row when the rest items' results come first, in list order, and the self items' follow
+//   key_idx [n_self]           the key of `prv` per SELF item, in list order (nullptr: one key, or key j for self item j)
+struct PdlOwn {
+  const mpe_paillier* prv = nullptr;
+  int n_self = 0;
+  const int32_t *self = nullptr, *rest = nullptr, *pos = nullptr, *key_idx = nullptr;
+};
+// out[j] = idx[list[j]]
+__global__ void compose_idx_kernel(int n, const int32_t* __restrict__ list, const int32_t* __restrict__ idx, int32_t* __restrict__ out) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < n) out[j] = idx[list[j]];
+}
+// The rows (or the selector) `r` of a call's items, seen through a list of item positions: row j of the result is row list[j] of r.
+// list == nullptr: the items themselves.  (Rows of the proofs: one row per item, shift 0.)
+static Rows sub_rows(mpe_ctx* ctx, hipStream_t st, int& rc, int n, Rows r, const int32_t* list) {
+  if (!list || n == 0) return r;
+  if (!r.idx) return r.stride ? Rows{r.p, list, r.stride, r.words, 0} : r;
+  int32_t* c = ws_array<int32_t>(ctx, (size_t)n);
+  if (!c) { if (rc == MPE_OK) rc = MPE_E_NOMEM; return r; }
+  if (rc == MPE_OK) hipLaunchKernelGGL(compose_idx_kernel, dim3(blocks_for(n, 64)), dim3(64), 0, st, n, list, r.idx, c);
+  return Rows{r.p, c, r.stride, r.words, 0};
+}
+
+// own: the items whose N^2 side may use the holder's key (PdlOwn above); nullptr, a context that has switched one of the holder's
+// routes off, or a small batch (forked streams): every item on the public key
 static int pdl_verify(mpe_ctx* ctx, const mpe_paillier* pk, const mpe_statements* stm, int B, const int32_t* key_idx,
                       const int32_t* st_idx, Rows cipher, Rows Qp, Rows Gp, const PdlProofRows& pr, uint8_t* ok,
-                      hipStream_t st) {
+                      hipStream_t st, const PdlOwn* own = nullptr) {
   MPE_TRY(ws_begin(ctx, st));
   const Rows ksel = sel_of(key_idx, pk->nkeys), ssel = sel_of(st_idx, stm->count);
   const Rows h1 = tab_rows(stm->h1, 64, st_idx, stm->count), h2 = tab_rows(stm->h2, 64, st_idx, stm->count);
@@ -491,6 +520,11 @@ static int pdl_verify(mpe_ctx* ctx, const mpe_paillier* pk, const mpe_statements
   Fork f(ctx, st, 3, B <= ctx->par_items);
   Seq q{ctx, f.s(0), B}, q1{ctx, f.s(1), B}, q2{ctx, f.s(2), B};
   q.rc = q0.rc;
+  // The verifier's own proofs go through its key's halves, the others stay on the public key: two item lists, each with its view of
+  // the rows the N^2 side reads.  Only where the call runs on ONE stream (a large batch, or a context without forks): the forked
+  // schedule of a small batch is latency-bound and stays as it is.
+  const bool split = !f.on && own && own->prv && own->prv->has_private && own->n_self > 0 && ctx->use_crt && ctx->use_pair &&
+                     ctx->use_pown && ctx->use_multiexp;
   if (B > 0) {
     hipLaunchKernelGGL(fill_u8_kernel, dim3(blocks_for(B, 64)), dim3(64), 0, f.s(1), B, ok, (uint8_t)1);
     hipLaunchKernelGGL(pdl_u1_check_kernel, dim3(blocks_for(B, 64)), dim3(64), 0, f.s(1), B, pr.s1, e, Gp, Qp, pr.u1, ok);   // :138-142
@@ -500,7 +534,21 @@ static int pdl_verify(mpe_ctx* ctx, const mpe_paillier* pk, const mpe_statements
   uint32_t* g1 = q.words(128);
   q.muladd(pr.s1, 25, Nrow, 64, no_rows(), 0, g1, 128);
   uint32_t *u2 = nullptr, *t2s = nullptr, *cies = nullptr;
-  if (f.on) {
+  if (split) {
+    // c^-1 for every item as before (its inv_ok flag carries the verdict), then per list: the public two-base ladder / modexp_nn2_holder.
+    // The results land in list order (the others, then the own ones) and are read back through own->pos.
+    const int ns = own->n_self, nr = B - ns;
+    const int32_t *ls = own->self, *lr = own->rest;                                                  // null: every item is an own one
+    const Rows ksel_r = sub_rows(ctx, st, q.rc, nr, ksel, lr), s2_r = sub_rows(ctx, st, q.rc, nr, with_words(pr.s2, 64), lr);
+    const Rows N_r = sub_rows(ctx, st, q.rc, nr, Nrow, lr), s2_s = sub_rows(ctx, st, q.rc, ns, with_words(pr.s2, 64), ls);
+    const Rows ksel_s = sel_of(own->key_idx, own->prv->nkeys);
+    uint32_t* cred = q.modmul(pk->ms_nn, ksel, cipher, rows(pk->ms_nn->one_words, 0, nullptr, 1));   // c mod N^2
+    uint32_t* cinv = q.modinv(pk->ms_nn, ksel, rows(cred, 128), inv_ok1);
+    uint32_t* m = q.words(128);
+    if (q.rc == MPE_OK) q.rc = mpe::modexp_nn2(ctx, pk, nr, ksel_r, s2_r, N_r, 64, rows(cinv, 128, lr), rows(e, 8, lr), 8, m, st);
+    if (q.rc == MPE_OK) q.rc = modexp_nn2_holder(ctx, own->prv, ns, ksel_s, s2_s, rows(cinv, 128, ls), rows(e, 8, ls), 8, m + (size_t)nr * 128, st);
+    u2 = q.modmul(pk->ms_nn, ksel, rows(g1, 128), rows(m, 128, ls ? own->pos : nullptr));
+  } else if (f.on) {
     // small batch: s2^N starts at once; c^-1 and the short ladder (c^-1)^e follow the u1 check on its stream
     uint32_t* s2n = q.modexp_nn(pk, ksel, with_words(pr.s2, 64), Nrow, 64, false);
     t2s = q.modmul(pk->ms_nn, ksel, rows(g1, 128), rows(s2n, 128));
@@ -680,8 +728,11 @@ int mpe_pdl_verify(mpe_ctx* ctx, const mpe_paillier* pk, const mpe_statements* s
                    const mpe_pdl_proof* proof, uint8_t* d_ok, void* stream) {
   if (!proof_args_ok(ctx, pk, stm, batch, d_key_idx, d_st_idx) || !d_cipher || !d_Q || !d_G || !proof || !d_ok) return MPE_E_ARG;
   if (batch == 0) return MPE_OK;
+  // a key set created with its primes belongs to the caller: every item is a proof under the verifier's own key
+  mpe::PdlOwn own;
+  own.prv = pk; own.n_self = batch; own.key_idx = d_key_idx;
   return mpe::pdl_verify(ctx, pk, stm, batch, d_key_idx, d_st_idx, mpe::rows(d_cipher, 128), mpe::rows(d_Q, 16), mpe::rows(d_G, 16),
-                         mpe::dense(proof), d_ok, (hipStream_t)stream);
+                         mpe::dense(proof), d_ok, (hipStream_t)stream, pk->has_private && ctx->r5_self_crt ? &own : nullptr);
 }
 
 }  // extern "C"
